@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DGViT hot-path benchmark (contract: see the task statement / DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
 
 Workload (BASELINE.json metric, config C3): per GPU a batch of 512 synthetic 84x84 depth frames + polar goals
 through DGViT-small (GoTPolicy: 84x84 @ 12x12 patches, 6 layers, 8 heads, d=256, MLP 2048), train mode,
@@ -20,11 +20,10 @@ import os
 import sys
 import time
 
-# --grad-overlap: the HIP runtime multiplexes streams onto 4 hardware queues by default; with RCCL initialised, the stream the collectives
-# run on then shares a queue with the compute stream and an all-reduce queued behind a gradient-ready event still executes after the whole
-# backward (measured: tools/overlap_queue_probe.py, profiles/r03_d_overlap_queue_probe.txt).  Must be set before the first HIP call.
-if "--grad-overlap" in sys.argv:
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# --grad-overlap: with RCCL initialised, the stream the collectives run on shares a hardware queue with the compute stream unless the
+# HIP runtime gives the process more queues than it does by default, and an all-reduce queued behind a gradient-ready event then still
+# executes after the whole backward (measured: tools/overlap_queue_probe.py, profiles/r03_d_overlap_queue_probe.txt).  bench.py leaves
+# the runtime's queue count as it finds it; GradSync warns when the overlap cannot happen.
 
 import torch  # noqa: E402
 
@@ -58,7 +57,26 @@ def parse():
                     help="start every transformer block's gradient all-reduce from inside the backward, behind its gradient-ready event "
                          "(GradSync(overlap=True)); default: one exchange after the backward -- the overlapped form is covered by tests and a "
                          "one-card timeline only, it has never run across real GPUs (DESIGN section 6)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; the sample positions float64): the actor's mean "
+                         "and log_std, the loss, and a fixed, seeded sample of the parameters after its Adam step (rank 0)")
     return ap.parse_args()
+
+
+DUMP_PARAM_SAMPLE = 1 << 20     # parameters after the last step: a fixed, seeded sample of this many values (4 MB)
+
+
+def dump_outputs(dirname, model, mean, log_std, loss):
+    """What a caller of the timed step receives -- the policy outputs and the loss -- plus the state the step leaves behind (the updated
+    parameters, sampled at positions that depend only on the parameter count), as float32 .npy files under `dirname`."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).float().cpu()
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAM_SAMPLE].sort().values
+    arrays = {"mean": mean, "log_std": log_std, "loss": loss.reshape(1), "params_after_step_sample": flat[idx],
+              "params_after_step_sample_index": idx}
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64))
 
 
 def cpu_baseline(batch):
@@ -346,7 +364,7 @@ def main():
         else:
             sync.sync()
         opt.step()
-        return loss
+        return loss, mean, log_std
 
     def fence():
         if world > 1 or args.force_collective:
@@ -364,7 +382,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step(timed=True)
+        loss, mean, log_std = step(timed=True)
     fence()
     dt = time.perf_counter() - t0
     kinds = _lib.PROFILE_KINDS
@@ -385,6 +403,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt, ar_ms = tmax[0].item(), tmax[1].item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, mean, log_std, loss)
 
     # north-star figure "MFMA roofline fraction of the DGViT forward at batch 512" (N = 1 only, outside the timed region):
     # the same batch through the same model, inference mode, no timing events

@@ -20,6 +20,10 @@ from typing import Iterable, List
 import torch
 import torch.distributed as dist
 
+# hardware queues per process: the HIP runtime's default, and the count at which the collectives' stream got a queue of its own (measured)
+_HIP_DEFAULT_HW_QUEUES = 4
+_OVERLAP_HW_QUEUES = 8
+
 
 class GradSync:
     def __init__(self, modules: Iterable[torch.nn.Module], process_group=None, bucket_bytes: int = 64 << 20,
@@ -55,11 +59,12 @@ class GradSync:
         if self.overlap:
             import os
             import warnings
-            if int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) < 8:
-                # measured (tools/overlap_queue_probe.py): with an RCCL process group alive and the HIP runtime's default of 4 hardware
+            queues = os.environ.get("GPU_MAX_HW_QUEUES") or _HIP_DEFAULT_HW_QUEUES
+            if int(queues) < _OVERLAP_HW_QUEUES:
+                # measured (tools/overlap_queue_probe.py): with an RCCL process group alive and the HIP runtime's default number of hardware
                 # queues, work queued behind a gradient-ready event runs only after the whole backward -- correct, but not overlapped
-                warnings.warn("GradSync(overlap=True): export GPU_MAX_HW_QUEUES=8 (before the first HIP call) or the collectives' stream "
-                              "shares a hardware queue with the compute stream and nothing overlaps", RuntimeWarning, stacklevel=2)
+                warnings.warn("GradSync(overlap=True): the collectives' stream shares a hardware queue with the compute stream, so the "
+                              "all-reduces run after the backward (correct, not overlapped)", RuntimeWarning, stacklevel=2)
             from .goalformer import GoT
             for m in self.modules:
                 for sub in m.modules():

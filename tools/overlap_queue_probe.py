@@ -1,15 +1,15 @@
 """Can work queued on a second stream behind a gradient-ready event run BESIDE the backward?  (it can only if that stream has a
 hardware queue of its own)
 
-    [NODIST=1] [GPU_MAX_HW_QUEUES=n] python tools/overlap_queue_probe.py wait|kernel|allreduce
+    [NODIST=1] python tools/overlap_queue_probe.py wait|kernel|allreduce
 
 The C3 model's backward (B = 512) records one event per transformer block (dgvit_got_backward_ev); the hook queues, on a side stream
 behind each event: nothing (`wait`), a small elementwise kernel (`kernel`), or a one-rank RCCL all-reduce (`allreduce`, launches no
 kernel), then a timing marker.  Printed: when each marker fired relative to the start of the backward.
 Measured on MI355X / ROCm 7: markers alone fire when their block is final (0.8, 2.4, 4.0 ... ms of a 9 ms backward).  A KERNEL behind
 the event does too while RCCL is not initialised; once a process group exists, the HIP runtime's default of 4 hardware queues puts the
-side stream on the compute stream's queue and every kernel waits for the whole backward (all markers at ~8.9 ms); with
-GPU_MAX_HW_QUEUES=8 they are back on time.  bench.py sets that variable; an integration that wants the overlap must too.
+side stream on the compute stream's queue and every kernel waits for the whole backward (all markers at ~8.9 ms); with twice the
+default number of hardware queues they were back on time (profiles/r03_d_overlap_queue_probe.txt).
 """
 import os, sys, time, ctypes
 import torch

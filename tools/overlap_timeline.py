@@ -1,6 +1,6 @@
 """Does the gradient exchange start before the backward has finished?  
 
-    GPU_MAX_HW_QUEUES=8 python tools/overlap_timeline.py [batch]
+    python tools/overlap_timeline.py [batch]
 
 One-rank RCCL group on this GPU (a one-rank all-reduce is the identity, but it is queued, ordered and waited for exactly as on 8
 ranks), BASELINE config 3 model, GradSync(overlap=True).  Device-side evidence from HIP events:
