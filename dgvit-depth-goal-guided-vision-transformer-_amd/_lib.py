@@ -54,6 +54,9 @@ SIGNATURES = {
     "dgvit_got_forward": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _LL, _I, _I, _F, _ULL, _P, _P]),
     "dgvit_got_backward": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P]),
     "dgvit_got_backward_ev": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P, POINTER(dgvit_grad_events)]),
+    "dgvit_got_forward_v2": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _LL, _I, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_v2": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_v2_ev": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P, POINTER(dgvit_grad_events)]),
     "dgvit_event_create": (_I, [POINTER(c_void_p)]),
     "dgvit_event_destroy": (_I, [_P]),
     "dgvit_stream_wait_event": (_I, [_P, _P]),

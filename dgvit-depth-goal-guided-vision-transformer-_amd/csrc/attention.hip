@@ -105,9 +105,12 @@ __device__ __forceinline__ void zero_tiles(f32x16 (&t)[DT]) {
 // ------------------------------------------------------------------------------------ forward
 // NKT_CT > 0: the number of 32-key tiles is a compile-time constant (N <= 64: the loops below unroll into straight-line
 // code with no rescale step); NKT_CT == 0: run-time loops for any N
-template <int DH, int NW, int NKT_CT>
+// DROP: train-mode dropout of the probabilities (GoalFormer.py:78; mask site 0, common.h): P.V takes m o P / keep, the softmax row sum
+// stays undropped; the backward regenerates the same bits
+template <int DH, int NW, int NKT_CT, bool DROP = false>
 __global__ void __launch_bounds__(64 * NW, 2) attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                              float* __restrict__ lse, int N, int H, float scale, int nq) {
+                                                              float* __restrict__ lse, int N, int H, float scale, int nq,
+                                                              const LayerDrop drop) {
   constexpr int SK = DH + 4, DT = DH / 32, NTHR = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int nkt = NKT_CT ? NKT_CT : (N + 31) / 32, NP = nkt * 32;
@@ -174,6 +177,25 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_fwd_kernel(const float* __res
       ts += __shfl_xor(ts, 32, 64);
       l = l * alpha + ts;
       m = mn;
+      if constexpr (DROP) {   // registers 4g .. 4g+3 hold the four consecutive keys of one float4 group: one Philox call each
+        const unsigned long long sd = drop_seed(drop);
+        const float inv = 1.0f / drop.keep;
+        const long long row4 = (((long long)b * H + hd) * N + q) * ((N + 3) / 4);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int k0 = kt * 32 + 8 * g + 4 * h;
+          if (k0 < N) {
+            const uint4 rb = drop_bits(row4 + k0 / 4, sd, drop.tag);
+            s0[4 * g] *= drop_factor(rb.x, drop.keep, inv); s0[4 * g + 1] *= drop_factor(rb.y, drop.keep, inv);
+            s0[4 * g + 2] *= drop_factor(rb.z, drop.keep, inv); s0[4 * g + 3] *= drop_factor(rb.w, drop.keep, inv);
+          }
+          if (two && k0 + 32 < N) {
+            const uint4 rb = drop_bits(row4 + (k0 + 32) / 4, sd, drop.tag);
+            s1[4 * g] *= drop_factor(rb.x, drop.keep, inv); s1[4 * g + 1] *= drop_factor(rb.y, drop.keep, inv);
+            s1[4 * g + 2] *= drop_factor(rb.z, drop.keep, inv); s1[4 * g + 3] *= drop_factor(rb.w, drop.keep, inv);
+          }
+        }
+      }
       if (kt > 0) {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
@@ -343,10 +365,13 @@ int launch_fwd_pipe(const float* qkv, float* out, float* lse, int B, int N, int 
 }
 
 // ------------------------------------------------------------------------------------ backward
-template <int DH, int NW, int NKT_CT>
+// DROP: the probabilities' dropout of attn_fwd_kernel<DROP>, bits regenerated: dV = (m o P / keep)^T dO, dP = (dO V^T) o m / keep,
+// dS = P o (dP - delta); delta = rowsum(dO o O) is unchanged (O already holds the mask)
+template <int DH, int NW, int NKT_CT, bool DROP = false>
 __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o_fwd,
                                                               const float* __restrict__ d_out, const float* __restrict__ lse,
-                                                              float* __restrict__ dqkv, int N, int H, float scale, int nq) {
+                                                              float* __restrict__ dqkv, int N, int H, float scale, int nq,
+                                                              const LayerDrop drop) {
   constexpr int SK = DH + 4, DT = DH / 32, NTHR = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int nkt = NKT_CT ? NKT_CT : (N + 31) / 32, NP = nkt * 32;
@@ -411,6 +436,25 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_kernel(const float* __res
         mfma_rows_x_frags<DH, SK>(s1, X, (kt + 1) * 32 + li, h, qf);
         mfma_rows_x_frags<DH, SK>(dp1, Y, (kt + 1) * 32 + li, h, dof);
       }
+      if constexpr (DROP) {   // dP^T o m / keep (the forward's float4 groups: registers 4g .. 4g+3)
+        const unsigned long long sd = drop_seed(drop);
+        const float inv = 1.0f / drop.keep;
+        const long long row4 = (((long long)b * H + hd) * N + q) * ((N + 3) / 4);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int k0 = kt * 32 + 8 * g + 4 * h;
+          if (k0 < N) {
+            const uint4 rb = drop_bits(row4 + k0 / 4, sd, drop.tag);
+            dp0[4 * g] *= drop_factor(rb.x, drop.keep, inv); dp0[4 * g + 1] *= drop_factor(rb.y, drop.keep, inv);
+            dp0[4 * g + 2] *= drop_factor(rb.z, drop.keep, inv); dp0[4 * g + 3] *= drop_factor(rb.w, drop.keep, inv);
+          }
+          if (two && k0 + 32 < N) {
+            const uint4 rb = drop_bits(row4 + (k0 + 32) / 4, sd, drop.tag);
+            dp1[4 * g] *= drop_factor(rb.x, drop.keep, inv); dp1[4 * g + 1] *= drop_factor(rb.y, drop.keep, inv);
+            dp1[4 * g + 2] *= drop_factor(rb.z, drop.keep, inv); dp1[4 * g + 3] *= drop_factor(rb.w, drop.keep, inv);
+          }
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = kt * 32 + acc_row(r, h);
@@ -474,12 +518,21 @@ __global__ void __launch_bounds__(64 * NW, 2) attn_bwd_kernel(const float* __res
       for (int r = 0; r < 16; ++r) {
         const int q = qt * 32 + acc_row(r, h);
         const float pv = (kv && q < nq) ? __builtin_amdgcn_exp2f(s[r] * qscale - lse_s[q]) : 0.f;
-        const float ds = pv * (dp[r] - del_s[q]) * scale;
+        float mk = 1.f;   // (here the lane owns a key and the registers hold queries: one Philox call per register, word key % 4)
+        if constexpr (DROP) {
+          if (kv && q < nq) {
+            const uint4 rb = drop_bits((((long long)b * H + hd) * N + q) * ((N + 3) / 4) + key / 4, drop_seed(drop), drop.tag);
+            const int w = key & 3;
+            mk = drop_factor(w == 0 ? rb.x : w == 1 ? rb.y : w == 2 ? rb.z : rb.w, drop.keep, 1.0f / drop.keep);
+          }
+        }
+        const float ds = DROP ? pv * (dp[r] * mk - del_s[q]) * scale : pv * (dp[r] - del_s[q]) * scale;
+        const float pd = DROP ? pv * mk : pv;
         const float* dorow = Y + q * SK + li;
         const float* qrow = X + q * SK + li;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(dorow[dt * 32], pv, dv[dt], 0, 0, 0);
+          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(dorow[dt * 32], pd, dv[dt], 0, 0, 0);
           dk[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(qrow[dt * 32], ds, dk[dt], 0, 0, 0);
         }
       }
@@ -862,11 +915,11 @@ int launch_q1_bwd(const float* qkv, const float* o, const float* dout, const flo
 
 constexpr int MAX_TOKENS = 288;   // 2 * 288 * 68 floats (K, V images at dim_head 64) + 2 * 288 (lse, delta) = 159.0 KB of the 160 KB LDS
 
-template <int DH, int NW, int NKT_CT>
-int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, int nq, hipStream_t stream) {
+template <int DH, int NW, int NKT_CT, bool DROP>
+int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, int nq, const LayerDrop& drop, hipStream_t stream) {
   const int NP = (N + 31) / 32 * 32;
   const size_t lds = (size_t)2 * NP * (DH + 4) * sizeof(float);
-  auto kern = attn_fwd_kernel<DH, NW, NKT_CT>;
+  auto kern = attn_fwd_kernel<DH, NW, NKT_CT, DROP>;
   static DeviceOnce once;
   if (const unsigned long long bit = once.pending()) {
     const int maxlds = 2 * MAX_TOKENS * (DH + 4) * (int)sizeof(float);
@@ -875,18 +928,18 @@ int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, fl
     once.mark(bit);
   }
   const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, out, lse, N, H, scale, nq);
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, out, lse, N, H, scale, nq, drop);
   profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("attention_fwd");
   return DGVIT_OK;
 }
 
-template <int DH, int NW, int NKT_CT>
+template <int DH, int NW, int NKT_CT, bool DROP>
 int launch_bwd(const float* qkv, const float* o, const float* dout, const float* lse, float* dqkv, int B, int N, int H,
-               float scale, int nq, hipStream_t stream) {
+               float scale, int nq, const LayerDrop& drop, hipStream_t stream) {
   const int NP = (N + 31) / 32 * 32;
   const size_t lds = ((size_t)2 * NP * (DH + 4) + 2 * NP) * sizeof(float);
-  auto kern = attn_bwd_kernel<DH, NW, NKT_CT>;
+  auto kern = attn_bwd_kernel<DH, NW, NKT_CT, DROP>;
   static DeviceOnce once;
   if (const unsigned long long bit = once.pending()) {
     const int maxlds = (2 * MAX_TOKENS * (DH + 4) + 2 * MAX_TOKENS) * (int)sizeof(float);
@@ -895,7 +948,7 @@ int launch_bwd(const float* qkv, const float* o, const float* dout, const float*
     once.mark(bit);
   }
   const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale, nq);
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale, nq, drop);
   profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("attention_bwd");
   return DGVIT_OK;
@@ -904,25 +957,31 @@ int launch_bwd(const float* qkv, const float* o, const float* dout, const float*
 }  // namespace
 
 // one wave per 32-token tile, at most 4 waves per workgroup; N <= 64 takes the compile-time-unrolled instantiations
-#define ATTN_DISPATCH(FN, ...)                                            \
+#define ATTN_DISPATCH(FN, DROP, ...)                                      \
   {                                                                       \
     const int nt = (N + 31) / 32;                                         \
-    if (dh == 64 && nt == 1) return FN<64, 1, 1>(__VA_ARGS__);            \
-    if (dh == 64 && nt == 2) return FN<64, 2, 2>(__VA_ARGS__);            \
-    if (dh == 64) return FN<64, 4, 0>(__VA_ARGS__);                       \
-    if (dh == 32 && nt == 1) return FN<32, 1, 1>(__VA_ARGS__);            \
-    if (dh == 32 && nt == 2) return FN<32, 2, 2>(__VA_ARGS__);            \
-    if (dh == 32) return FN<32, 4, 0>(__VA_ARGS__);                       \
+    if (dh == 64 && nt == 1) return FN<64, 1, 1, DROP>(__VA_ARGS__);      \
+    if (dh == 64 && nt == 2) return FN<64, 2, 2, DROP>(__VA_ARGS__);      \
+    if (dh == 64) return FN<64, 4, 0, DROP>(__VA_ARGS__);                 \
+    if (dh == 32 && nt == 1) return FN<32, 1, 1, DROP>(__VA_ARGS__);      \
+    if (dh == 32 && nt == 2) return FN<32, 2, 2, DROP>(__VA_ARGS__);      \
+    if (dh == 32) return FN<32, 4, 0, DROP>(__VA_ARGS__);                 \
   }
 
 // qkv (B, N, 3*H*dh) -> out (B, N, H*dh); lse (B, H, N) base-2 log-sum-exp of the scaled scores (NULL: not kept).
 // nq = number of leading query tokens whose output is needed (N normally)
-int attention_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t stream) {
+// drop (may be NULL): train-mode dropout of the probabilities; keep < 1 runs the general kernel with the mask (every nq)
+int attention_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t stream, const LayerDrop* drop) {
   DGVIT_CHECK_ARG(qkv && out && B > 0 && N > 0 && H > 0, "attention_fwd: bad arguments");
   DGVIT_CHECK_ARG((long long)B * H < (1ll << 31), "attention_fwd: B*H too large");
   DGVIT_CHECK_ARG(nq >= 1 && nq <= N, "attention_fwd: bad query count");
   DGVIT_CHECK_ARG(N <= MAX_TOKENS && (dh == 64 || dh == 32), "attention_fwd: unsupported dim_head=%d / tokens=%d (dim_head 64 or 32, N <= 288)", dh, N);
   const float scale = 1.0f / sqrtf((float)dh);
+  const LayerDrop none = {1.f, 0u, 0ull, nullptr};
+  if (drop && drop->keep < 1.f) {
+    DGVIT_CHECK_ARG(drop->keep > 0.f, "attention_fwd: dropout keep must be in (0, 1]");
+    ATTN_DISPATCH(launch_fwd, true, qkv, out, lse, B, N, H, scale, nq, *drop, stream)
+  }
   if (g_attn_q1 && nq == 1 && N <= 64) {                               // token 0 only (the last block): one wave per (frame, head)
     if (dh == 64) return launch_q1_fwd<64>(qkv, out, lse, B, N, H, scale, stream);
     return launch_q1_fwd<32>(qkv, out, lse, B, N, H, scale, stream);
@@ -931,7 +990,7 @@ int attention_fwd(const float* qkv, float* out, float* lse, int B, int N, int H,
     if (dh == 64) return launch_fwd_pipe<64>(qkv, out, lse, B, N, H, scale, stream);
     return launch_fwd_pipe<32>(qkv, out, lse, B, N, H, scale, stream);
   }
-  ATTN_DISPATCH(launch_fwd, qkv, out, lse, B, N, H, scale, nq, stream)
+  ATTN_DISPATCH(launch_fwd, false, qkv, out, lse, B, N, H, scale, nq, none, stream)
   return dgvit_set_error(DGVIT_ERR_ARG, "attention_fwd: no kernel for dim_head=%d", dh);
 }
 
@@ -939,12 +998,17 @@ int attention_fwd(const float* qkv, float* out, float* lse, int B, int N, int H,
 // (dk, dv: all rows)
 
 int attention_bwd(const float* qkv, const float* o, const float* dout, const float* lse, float* dqkv, int B, int N, int H,
-                  int dh, int nq, hipStream_t stream) {
+                  int dh, int nq, hipStream_t stream, const LayerDrop* drop) {
   DGVIT_CHECK_ARG(qkv && o && dout && lse && dqkv && B > 0 && N > 0 && H > 0, "attention_bwd: bad arguments");
   DGVIT_CHECK_ARG((long long)B * H < (1ll << 31), "attention_bwd: B*H too large");
   DGVIT_CHECK_ARG(nq >= 1 && nq <= N, "attention_bwd: bad query count");
   DGVIT_CHECK_ARG(N <= MAX_TOKENS && (dh == 64 || dh == 32), "attention_bwd: unsupported dim_head=%d / tokens=%d", dh, N);
   const float scale = 1.0f / sqrtf((float)dh);
+  const LayerDrop none = {1.f, 0u, 0ull, nullptr};
+  if (drop && drop->keep < 1.f) {
+    DGVIT_CHECK_ARG(drop->keep > 0.f, "attention_bwd: dropout keep must be in (0, 1]");
+    ATTN_DISPATCH(launch_bwd, true, qkv, o, dout, lse, dqkv, B, N, H, scale, nq, *drop, stream)
+  }
   if (g_attn_q1 && nq == 1 && N <= 64) {
     if (dh == 64) return launch_q1_bwd<64>(qkv, o, dout, lse, dqkv, B, N, H, scale, stream);
     return launch_q1_bwd<32>(qkv, o, dout, lse, dqkv, B, N, H, scale, stream);
@@ -953,6 +1017,6 @@ int attention_bwd(const float* qkv, const float* o, const float* dout, const flo
     if (dh == 64) return launch_bwd64<64>(qkv, o, dout, lse, dqkv, B, N, H, scale, stream);
     return launch_bwd64<32>(qkv, o, dout, lse, dqkv, B, N, H, scale, stream);
   }
-  ATTN_DISPATCH(launch_bwd, qkv, o, dout, lse, dqkv, B, N, H, scale, nq, stream)
+  ATTN_DISPATCH(launch_bwd, false, qkv, o, dout, lse, dqkv, B, N, H, scale, nq, none, stream)
   return dgvit_set_error(DGVIT_ERR_ARG, "attention_bwd: no kernel for dim_head=%d", dh);
 }

@@ -188,6 +188,34 @@ __device__ __forceinline__ float4 dropout4(float4 v, long long i4, unsigned long
   return v;
 }
 
+// ---- transformer-internal dropout (GoalFormer.py:47, 49, 68, 78): the same rule as dropout4 -- Philox4x32-10 keyed by the forward's one
+// seed, an element is kept when r * 2^-32 < keep and a kept value is multiplied by 1/keep -- with the site in the third counter word.
+// Emb-dropout keeps ctr.z = 0; transformer site s of layer l uses ctr.z = 0x44000000 | (l << 2) | s:
+//   s | site                                      | tensor, indexed as                         | float4 group i4, lane
+//   0 | attention probabilities, after softmax    | (b, h, q, k)                               | ((b*H + h)*N + q)*ceil(N/4) + k/4, k % 4
+//   1 | to_out output, before the residual add    | (token row, D) row-major                   | (row*D + c)/4
+//   2 | FeedForward hidden, after GELU            | (token row, M)                             | (row*M + c)/4
+//   3 | FeedForward output, before the residual add | (token row, D)                           | (row*D + c)/4
+// `row` is always the absolute token row b*N + t (the token-0-only last block draws the bits of the dense one).  Nothing is stored:
+// the backward regenerates every mask from the seed.
+enum { DROP_ATTN = 0, DROP_OUT = 1, DROP_HIDDEN = 2, DROP_FF = 3 };
+__host__ __device__ __forceinline__ uint32_t drop_tag(int layer, int site) { return 0x44000000u | ((uint32_t)layer << 2) | (uint32_t)site; }
+
+// one site of one layer: keep < 1 applies the mask; seed_dev (may be NULL) overrides seed at run time (graph capture)
+struct LayerDrop {
+  float keep;
+  uint32_t tag;
+  unsigned long long seed;
+  const unsigned long long* seed_dev;
+};
+
+__device__ __forceinline__ unsigned long long drop_seed(const LayerDrop& d) { return d.seed_dev ? *d.seed_dev : d.seed; }
+__device__ __forceinline__ uint4 drop_bits(long long i4, unsigned long long seed, uint32_t tag) {
+  return philox4x32_10(make_uint4((uint32_t)i4, (uint32_t)(i4 >> 32), tag, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+}
+// the factor one random word gives: 1/keep (kept) or 0 (dropped)
+__device__ __forceinline__ float drop_factor(uint32_t r, float keep, float inv) { return (r * 2.3283064365386963e-10f < keep) ? inv : 0.f; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

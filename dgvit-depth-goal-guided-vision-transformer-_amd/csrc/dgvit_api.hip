@@ -356,7 +356,7 @@ extern "C" long long dgvit_got_workspace_floats(const dgvit_config* cfg, int bat
 
 namespace {
 struct Bs {  // backward scratch carve-up
-  long long dxa, dxb, dln, dqkv, dao, dh1, part, part_ln2, part_ln1, slabs, total, slabs_floats;
+  long long dxa, dxb, dln, dqkv, dao, dh1, dm1, dm3, part, part_ln2, part_ln1, slabs, total, slabs_floats;
   long long sl_fc2, sl_fc1, sl_out, sl_qkv, n_fc2, n_fc1, n_out, n_qkv;   // a layer's four weight gradients keep separate slab regions
   long long sk_counters, sk_slabs, sk_ncounters, sk_slab_floats;          // in-launch split-K scratch of the data-gradient GEMMs
 };
@@ -369,6 +369,10 @@ Bs make_bs(const Dims& d) {
   s.dqkv = o; o += al4(d.T * 3 * d.I);
   s.dao = o; o += al4(d.T * d.I);
   s.dh1 = o; o += al4(d.T * d.M);
+  // transformer dropout (layer keep < 1): dx o m / keep of the to_out (site 1) and fc2 (site 3) branches, the A operand of their data and
+  // weight gradients.  Two regions: the helper stream may still read one while the caller's stream writes the other.
+  s.dm1 = o; o += al4(d.T * d.D);
+  s.dm3 = o; o += al4(d.T * d.D);
   // reduction partials: LN (blocks*2*D), colsum (blocks*max width), rms, dpos (blocks * N*D)
   long long part = (long long)layernorm_bwd_blocks((int)d.T) * 2 * d.D;
   const long long widest = (long long)(d.M > 3 * d.I ? d.M : 3 * d.I);
@@ -419,11 +423,21 @@ static inline bool no_projection_slot(const Dims& d, int i) {
 extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
                                  float* feat, float* ws, long long ws_floats, int batch, int save, float keep,
                                  unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  return dgvit_got_forward_v2(cfg, params, img, goal, feat, ws, ws_floats, batch, save, keep, 1.f, seed, seed_dev, stream);
+}
+
+extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
+                                    float* feat, float* ws, long long ws_floats, int batch, int save, float keep, float lkeep,
+                                    unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   Dims d;
   TRY(make_dims(cfg, batch, d));
   DGVIT_CHECK_ARG(params && img && goal && feat && ws, "dgvit_got_forward: null pointer");
   DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dropout_keep must be in (0, 1]");
+  DGVIT_CHECK_ARG(lkeep > 0.f && lkeep <= 1.f, "layer_dropout_keep must be in (0, 1]");
+  // transformer dropout (GoalFormer.py:47,49,68,78): the GEMM schedule only -- the block and frame paths do not apply it
+  const bool ldrop = lkeep < 1.f;
+  auto site = [&](int layer, int s) { return LayerDrop{lkeep, drop_tag(layer, s), seed, seed_dev}; };
   const Ws w = make_ws(d, save);
   if (ws_floats < w.total) return dgvit_set_error(DGVIT_ERR_WORKSPACE, "forward workspace %lld < %lld floats", ws_floats, w.total);
   for (int i = 0; i < P_L0 + DGVIT_PARAMS_PER_LAYER * d.L; ++i) DGVIT_CHECK_ARG(params[i] || no_projection_slot(d, i), "parameter %d is null", i);
@@ -436,7 +450,7 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
   }
   // Small no-grad batches (SAC.choose_action on one frame, the target passes of learn() on a few frames): two launches per block, the
   // sums over heads / hidden chunks taken inside the launches (block.hip), the LayerNorms in their combine steps
-  const bool use_blocks = !save && g_block_path && !g_small_path && w.bp_ncounters > 0;
+  const bool use_blocks = !save && !ldrop && g_block_path && !g_small_path && w.bp_ncounters > 0;
   // patch embedding (GoalFormer.py:137-139,157) + goal token, positional embedding, dropout (:160-163)
   float* patches = ws + w.patches;
   float* x = ws + w.x0;
@@ -476,7 +490,7 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
 
   // inference on a handful of frames (SAC.choose_action, the no-grad passes of learn() at batch 32): two launches per block
 #ifdef DGVIT_DIAG   // (measured slower than the schedule below, DESIGN 3.7: not in the product library)
-  if (!save && g_small_path && !d.pool_mean && d.proj && d.T <= g_small_path_max_rows && frame_path_supports(d.B, d.N, d.D, d.H, d.dh, d.M))
+  if (!save && !ldrop && g_small_path && !d.pool_mean && d.proj && d.T <= g_small_path_max_rows && frame_path_supports(d.B, d.N, d.D, d.H, d.dh, d.M))
     return frame_path_forward(x, params, d.L, ws + w.layer0, feat, d.B, d.N, d.D, d.H, d.dh, d.M, st);
 #endif
 
@@ -507,7 +521,8 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
     }
   }
   if (feat_done) return DGVIT_OK;
-  const bool ln_fused = g_ln_fusion && d.D == 64 && g_gemm_tile_hint == 0;   // (the automatic tile for N = 64 is 64 wide)
+  // (with transformer dropout the branch is masked after its GEMM, before the residual add: the LayerNorms run as kernels of their own)
+  const bool ln_fused = g_ln_fusion && d.D == 64 && g_gemm_tile_hint == 0 && !ldrop;   // (the automatic tile for N = 64 is 64 wide)
   for (int i = 0; i < d.L && !use_blocks; ++i) {
     const float* const* lp = params + P_L0 + DGVIT_PARAMS_PER_LAYER * i;
     float* lb = ws + w.layer0 + w.layer_stride * i;
@@ -535,19 +550,23 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
       sk.attach(q);
       TRY(gemm_f32(GEMM_NT, EPI_STORE, q, 1, st));
     }
-    TRY(attention_fwd(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+    const LayerDrop dr_attn = site(i, DROP_ATTN);
+    TRY(attention_fwd(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
     if (!d.proj) {
       // to_out = nn.Identity() (GoalFormer.py:56,66-69): the head's output IS the branch output (I == D): xmid = attn + x (:103)
       TRY(add_rows(lb + w.ao, (long long)rs * d.I, x, (long long)rs * d.D, lb + w.xmid, (long long)rs * d.D, tok, d.D, st));
     } else {
       GemmParams p = gp(lb + w.ao, rs * d.I, lp[L_OUTW], d.I, lb + w.xmid, rs * d.D, tok, d.D, d.I);
-      p.bias = lp[L_OUTB]; p.res = x; p.ldr = rs * d.D;
+      p.bias = lp[L_OUTB]; p.res = ldrop ? nullptr : x; p.ldr = rs * d.D;
       if (ln_fused) {
         p.ln_g = lp[L_LN2W]; p.ln_b = lp[L_LN2B]; p.ln_y = lb + w.ln2; p.ln_ld = (long long)rs * d.D;
         p.ln_mean = lb + w.mean2; p.ln_rstd = lb + w.rstd2; p.ln_eps = 1e-5f;
       }
       sk.attach(p);
       TRY(gemm_f32(GEMM_NT, EPI_STORE, p, 1, st));
+      // xmid = x + m o (ao Wo^T + b) / keep   (site 1)
+      if (ldrop) TRY(drop_rows(lb + w.xmid, (long long)rs * d.D, lb + w.xmid, (long long)rs * d.D, x, (long long)rs * d.D, tok, d.D, rs,
+                               site(i, DROP_OUT), st));
     }
     // x = ff(LN(x)) + x     (GoalFormer.py:104, 42-50)
     if (!ln_fused || !d.proj) TRY(layernorm_fwd(lb + w.xmid, lp[L_LN2W], lp[L_LN2B], lb + w.ln2, lb + w.mean2, lb + w.rstd2, tok, d.D, 1e-5f, rs, st));
@@ -559,11 +578,17 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
       p.bias = lp[L_FC1B];
       if (save) { p.C2 = lb + w.a1; p.ldc2 = d.M; }
       sk.attach(p);
-      TRY(gemm_f32(GEMM_NT, save ? (g_gelu_grad_store ? EPI_GELU2D : EPI_GELU2) : EPI_GELU, p, 1, st));
+      TRY(gemm_f32(GEMM_NT, save ? (g_gelu_grad_store || ldrop ? EPI_GELU2D : EPI_GELU2) : EPI_GELU, p, 1, st));
+      // site 2: gelu(t) o m / keep, and the same factor folded into the stored gelu'(t) (the backward's EPI_DMUL and fc2's weight
+      // gradient then need nothing more)
+      if (ldrop) {
+        TRY(drop_rows(lb + w.a1, d.M, lb + w.a1, d.M, nullptr, 0, tok, d.M, rs, site(i, DROP_HIDDEN), st));
+        if (save) TRY(drop_rows(lb + w.h1, d.M, lb + w.h1, d.M, nullptr, 0, tok, d.M, rs, site(i, DROP_HIDDEN), st));
+      }
     }
     {
       GemmParams p = gp(lb + w.a1, d.M, lp[L_FC2W], d.M, xo, rs * d.D, tok, d.D, d.M);
-      p.bias = lp[L_FC2B]; p.res = lb + w.xmid; p.ldr = rs * d.D;
+      p.bias = lp[L_FC2B]; p.res = ldrop ? nullptr : lb + w.xmid; p.ldr = rs * d.D;
       if (ln_fused && i + 1 < d.L) {   // the next block's LN1 (this block is never the pruned last one: all T rows)
         const float* const* ln = params + P_L0 + DGVIT_PARAMS_PER_LAYER * (i + 1);
         float* nb = ws + w.layer0 + w.layer_stride * (i + 1);
@@ -572,6 +597,9 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
       }
       sk.attach(p);
       TRY(gemm_f32(GEMM_NT, EPI_STORE, p, 1, st));
+      // xout = xmid + m o (a1 W2^T + b) / keep   (site 3)
+      if (ldrop) TRY(drop_rows(xo, (long long)rs * d.D, xo, (long long)rs * d.D, lb + w.xmid, (long long)rs * d.D, tok, d.D, rs,
+                               site(i, DROP_FF), st));
     }
     x = xo;
   }
@@ -617,18 +645,38 @@ extern "C" int dgvit_got_backward(const dgvit_config* cfg, const float* const* p
                                   float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
                                   int batch, float keep, unsigned long long seed, const unsigned long long* seed_dev,
                                   void* stream) {
-  return dgvit_got_backward_ev(cfg, params, grads, dfeat, dgoal, ws, ws_floats, scratch, scratch_floats, batch, keep, seed, seed_dev, stream,
-                               nullptr);
+  return dgvit_got_backward_v2_ev(cfg, params, grads, dfeat, dgoal, ws, ws_floats, scratch, scratch_floats, batch, keep, 1.f, seed, seed_dev,
+                                  stream, nullptr);
 }
 
 extern "C" int dgvit_got_backward_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
                                      float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
                                      int batch, float keep, unsigned long long seed, const unsigned long long* seed_dev,
                                      void* stream, const dgvit_grad_events* events) {
+  return dgvit_got_backward_v2_ev(cfg, params, grads, dfeat, dgoal, ws, ws_floats, scratch, scratch_floats, batch, keep, 1.f, seed, seed_dev,
+                                  stream, events);
+}
+
+extern "C" int dgvit_got_backward_v2(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                                     float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
+                                     int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
+                                     void* stream) {
+  return dgvit_got_backward_v2_ev(cfg, params, grads, dfeat, dgoal, ws, ws_floats, scratch, scratch_floats, batch, keep, lkeep, seed, seed_dev,
+                                  stream, nullptr);
+}
+
+extern "C" int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                                        float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
+                                        int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
+                                        void* stream, const dgvit_grad_events* events) {
   hipStream_t st = (hipStream_t)stream;
   Dims d;
   TRY(make_dims(cfg, batch, d));
   DGVIT_CHECK_ARG(params && grads && dfeat && ws && scratch, "dgvit_got_backward: null pointer");
+  DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dropout_keep must be in (0, 1]");
+  DGVIT_CHECK_ARG(lkeep > 0.f && lkeep <= 1.f, "layer_dropout_keep must be in (0, 1]");
+  const bool ldrop = lkeep < 1.f;   // the masks of dgvit_got_forward_v2, regenerated from the same seed
+  auto site = [&](int layer, int s) { return LayerDrop{lkeep, drop_tag(layer, s), seed, seed_dev}; };
   TRY(check_events(events, cfg->depth));
   const Ws w = make_ws(d, 1);
   const Bs s = make_bs(d);
@@ -690,13 +738,19 @@ extern "C" int dgvit_got_backward_ev(const dgvit_config* cfg, const float* const
     ReduceGroup grp;
     reduce_group_init(grp);
     ReduceGroup* gq = g_group_reduce ? &grp : nullptr;   // null: every reduction is launched where it is produced
+    // (site 3: the branch sees dx o m / keep; the residual path keeps dx)
+    const float* dff = dx;
+    if (ldrop) {
+      TRY(drop_rows(dx, (long long)rs * d.D, scratch + s.dm3, (long long)rs * d.D, nullptr, 0, tok, d.D, rs, site(i, DROP_FF), st));
+      dff = scratch + s.dm3;
+    }
     TRY(fork());
-    TRY(wgrad(dx, rs * d.D, lb + w.a1, d.M, lg[L_FC2W], lg[L_FC2B], d.D, d.M, tok, slabs + s.sl_fc2, s.n_fc2, sw, gq));
+    TRY(wgrad(dff, rs * d.D, lb + w.a1, d.M, lg[L_FC2W], lg[L_FC2B], d.D, d.M, tok, slabs + s.sl_fc2, s.n_fc2, sw, gq));
     {
-      GemmParams p = gp(dx, rs * d.D, lp[L_FC2W], d.M, dh1, d.M, tok, d.M, d.D);
+      GemmParams p = gp(dff, rs * d.D, lp[L_FC2W], d.M, dh1, d.M, tok, d.M, d.D);
       p.aux = lb + w.h1; p.ldaux = d.M;             // (the h1 slot holds gelu'(pre-activation), written by the forward)
       sk.attach(p);
-      TRY(gemm_f32(GEMM_NN, g_gelu_grad_store ? EPI_DMUL : EPI_DGELU, p, 1, st));   // dh1 = (dx W2) * gelu'(h1)   [previous layer's wgrads joined below]
+      TRY(gemm_f32(GEMM_NN, g_gelu_grad_store || ldrop ? EPI_DMUL : EPI_DGELU, p, 1, st));   // dh1 = (dx W2) * gelu'(h1)   [previous layer's wgrads joined below]
     }
     TRY(fork());
     TRY(wgrad(dh1, d.M, lb + w.ln2, rs * d.D, lg[L_FC1W], lg[L_FC1B], d.M, d.D, tok, slabs + s.sl_fc1, s.n_fc1, sw, gq));
@@ -710,14 +764,21 @@ extern "C" int dgvit_got_backward_ev(const dgvit_config* cfg, const float* const
                       rs, st, gq));
     // ---- attention branch: xmid = to_out(attn(to_qkv(ln1))) + xin       (dx2 = d xmid)
     if (d.proj) {
+      const float* dat = dx2;   // (site 1, as site 3 above)
+      if (ldrop) {
+        TRY(drop_rows(dx2, (long long)rs * d.D, scratch + s.dm1, (long long)rs * d.D, nullptr, 0, tok, d.D, rs, site(i, DROP_OUT), st));
+        dat = scratch + s.dm1;
+      }
       TRY(fork());
-      TRY(wgrad(dx2, rs * d.D, lb + w.ao, rs * d.I, lg[L_OUTW], lg[L_OUTB], d.D, d.I, tok, slabs + s.sl_out, s.n_out, sw, gq));
-      GemmParams p = gp(dx2, rs * d.D, lp[L_OUTW], d.I, dao, rs * d.I, tok, d.I, d.D);
+      TRY(wgrad(dat, rs * d.D, lb + w.ao, rs * d.I, lg[L_OUTW], lg[L_OUTB], d.D, d.I, tok, slabs + s.sl_out, s.n_out, sw, gq));
+      GemmParams p = gp(dat, rs * d.D, lp[L_OUTW], d.I, dao, rs * d.I, tok, d.I, d.D);
       sk.attach(p);
       TRY(gemm_f32(GEMM_NN, EPI_STORE, p, 1, st));  // dao = dxmid Wo
     }
     // (no output projection: the gradient of the attention output is the residual-stream gradient itself, I == D)
-    TRY(attention_bwd(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+    const LayerDrop dr_attn = site(i, DROP_ATTN);
+    TRY(attention_bwd(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st,
+                      ldrop ? &dr_attn : nullptr));
     TRY(fork());
     if (!last) {
       TRY(wgrad(dqkv, 3 * d.I, lb + w.ln1, d.D, lg[L_QKV], nullptr, 3 * d.I, d.D, T, slabs + s.sl_qkv, s.n_qkv, sw, gq));

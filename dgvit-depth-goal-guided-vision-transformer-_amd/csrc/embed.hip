@@ -3,6 +3,7 @@
 //   goal_row      : x0[b, 0, :] = goal[b] + pos[0]         (goal token in the CLS slot)
 //   dropout       : in-place Bernoulli(keep) mask / keep, Philox4x32-10 keyed by (seed), counter = float4 index
 //                   -- the same call with the same seed re-creates the mask in backward, nothing is stored
+//   drop_rows     : transformer-internal dropout of a row block (+ residual), sites 1-3 of the mask table in common.h
 //   relu_bwd      : dpre = dy * (y > 0)                    (head MLPs)
 #include "common.h"
 #include "kernels.h"
@@ -38,6 +39,27 @@ __global__ void __launch_bounds__(256) dropout_kernel(float* __restrict__ x, lon
   if (i >= n4) return;
   if (seed_dev) seed = *seed_dev;   // graph-capturable form: the seed lives in device memory
   reinterpret_cast<float4*>(x)[i] = dropout4(reinterpret_cast<float4*>(x)[i], i, seed, keep);
+}
+
+// transformer-internal dropout of a row block (sites 1-3 of the mask table in common.h): one float4 group per thread; buffer row r is
+// absolute token row r * rs, so the token-0 rows of the pruned last block draw the bits of the dense block's rows b*N
+__global__ void __launch_bounds__(256) drop_rows_kernel(const float4* __restrict__ src, long long lds4, float4* __restrict__ dst, long long ldd4,
+                                                        const float4* __restrict__ res, long long ldr4, long long total4, int row4, int rs,
+                                                        const LayerDrop drop) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long long r = i / row4;
+  const int c = (int)(i - r * row4);
+  const uint4 rb = drop_bits(r * rs * row4 + c, drop_seed(drop), drop.tag);
+  const float inv = 1.0f / drop.keep;
+  const float4 v = src[r * lds4 + c];
+  float4 o = make_float4(v.x * drop_factor(rb.x, drop.keep, inv), v.y * drop_factor(rb.y, drop.keep, inv),
+                         v.z * drop_factor(rb.z, drop.keep, inv), v.w * drop_factor(rb.w, drop.keep, inv));
+  if (res) {
+    const float4 x = res[r * ldr4 + c];
+    o = make_float4(x.x + o.x, x.y + o.y, x.z + o.z, x.w + o.w);
+  }
+  dst[r * ldd4 + c] = o;
 }
 
 __global__ void __launch_bounds__(256) relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ out,
@@ -116,6 +138,19 @@ int dropout_inplace(float* x, long long n, unsigned long long seed, const unsign
   const long long n4 = n / 4;
   hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, n4, seed, seed_dev, keep);
   DGVIT_CHECK_LAUNCH("dropout");
+  return DGVIT_OK;
+}
+
+int drop_rows(const float* src, long long lds, float* dst, long long ldd, const float* res, long long ldr, long long rows, int width, int rs,
+              const LayerDrop& drop, hipStream_t stream) {
+  DGVIT_CHECK_ARG(src && dst && rows > 0 && width > 0 && width % 4 == 0 && rs >= 1 && lds % 4 == 0 && ldd % 4 == 0 && ldr % 4 == 0 &&
+                      lds >= width && ldd >= width && (!res || ldr >= width) && drop.keep > 0.f && drop.keep <= 1.f &&
+                      (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)res) & 15) == 0,
+                  "drop_rows: bad arguments");
+  const long long total4 = rows * (width / 4);
+  hipLaunchKernelGGL(drop_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(src), lds / 4,
+                     reinterpret_cast<float4*>(dst), ldd / 4, reinterpret_cast<const float4*>(res), ldr / 4, total4, width / 4, rs, drop);
+  DGVIT_CHECK_LAUNCH("drop_rows");
   return DGVIT_OK;
 }
 

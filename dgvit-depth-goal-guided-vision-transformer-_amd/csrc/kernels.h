@@ -12,12 +12,17 @@ int rmsnorm_bwd_blocks(int B);
 int rmsnorm_bwd(const float*, const float*, long long, const float*, float*, long long, float*, float*, int, int, hipStream_t);
 int colsum_blocks(int T);
 int colsum(const float*, long long, float*, float*, int, int, int, hipStream_t);
-int attention_fwd(const float*, float*, float*, int, int, int, int, int, hipStream_t);
-int attention_bwd(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, hipStream_t);
+int attention_fwd(const float*, float*, float*, int, int, int, int, int, hipStream_t, const LayerDrop* drop = nullptr);
+int attention_bwd(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, hipStream_t,
+                  const LayerDrop* drop = nullptr);
 int patchify(const float*, float*, int, int, int, int, int, hipStream_t);
 int add_rows(const float*, long long, const float*, long long, float*, long long, long long, int, hipStream_t);
 int goal_row(const float*, const float*, float*, int, int, int, hipStream_t);
 int dropout_inplace(float*, long long, unsigned long long, const unsigned long long*, float, hipStream_t);
+// transformer-internal dropout of a row block (mask sites 1-3, common.h): dst[r] = (res ? res[r] : 0) + m o src[r] / keep over `rows`
+// rows of `width` floats; buffer row r is absolute token row r * rs (mask counter), rows at strides lds / ldd / ldr
+int drop_rows(const float* src, long long lds, float* dst, long long ldd, const float* res, long long ldr, long long rows, int width, int rs,
+              const LayerDrop& drop, hipStream_t stream);
 int relu_bwd(const float*, const float*, float*, long long, hipStream_t);
 int adam_step(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
               hipStream_t);

@@ -61,6 +61,11 @@ def make_config(image, patch, dim, depth, heads, dim_head, mlp_dim) -> dgvit_con
 _N_NONPARAM_INPUTS = 7   # img, goal, cfg_tuple, keep, seed, need_grad, grad_hook precede *params in _GoTEncoder.apply
 
 
+def _keeps(keep):
+    """`keep` of _GoTEncoder.apply: the emb-dropout keep, or the tuple (emb keep, transformer keep)"""
+    return (float(keep[0]), float(keep[1])) if isinstance(keep, tuple) else (float(keep), 1.0)
+
+
 def _flat_grads(params, needs, dev):
     """Gradient tensors for the parameters autograd asks for, as views of ONE flat fp32 buffer laid out in parameter-table
     order (4-float aligned slots, the layout of optim._Block and parallel.GradSync): autograd adopts them as .grad without
@@ -154,12 +159,13 @@ class _GoTEncoder(torch.autograd.Function):
         # `seed` is a host int, or a 1-element int64 DEVICE tensor (graph capture: the kernel reads it at run time)
         seed_dev = seed if isinstance(seed, torch.Tensor) else None
         seed_val = 0 if seed_dev is not None else int(seed)
+        keep, lkeep = _keeps(keep)
         with torch.cuda.device(img.device):
-            rc = lib.dgvit_got_forward(ctypes.byref(cfg), _table(params), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws), nws, B,
-                                       int(need_grad), float(keep), seed_val, _ptr(seed_dev), _stream())
+            rc = lib.dgvit_got_forward_v2(ctypes.byref(cfg), _table(params), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws), nws, B,
+                                          int(need_grad), keep, lkeep, seed_val, _ptr(seed_dev), _stream())
         _lib.check(rc, "dgvit_got_forward")
         if need_grad:
-            ctx.cfg_tuple, ctx.keep, ctx.seed, ctx.batch = cfg_tuple, float(keep), seed_val, B
+            ctx.cfg_tuple, ctx.keep, ctx.lkeep, ctx.seed, ctx.batch = cfg_tuple, keep, lkeep, seed_val, B
             ctx.seed_dev = seed_dev
             ctx.ws = ws
             ctx.grad_hook = grad_hook
@@ -184,9 +190,9 @@ class _GoTEncoder(torch.autograd.Function):
         evs = _layer_events(dev, cfg.depth) if ctx.grad_hook is not None else None
         events, keep_alive = _grad_events(cfg.depth, evs) if evs else (None, None)
         with torch.cuda.device(dev):
-            rc = lib.dgvit_got_backward_ev(ctypes.byref(cfg), _table(params), _grad_table(grads), _ptr(dfeat), _ptr(dgoal), _ptr(ws),
-                                           ws.numel(), _ptr(scratch), nsc, B, ctx.keep, ctx.seed, _ptr(ctx.seed_dev), _stream(),
-                                           ctypes.byref(events) if events is not None else None)
+            rc = lib.dgvit_got_backward_v2_ev(ctypes.byref(cfg), _table(params), _grad_table(grads), _ptr(dfeat), _ptr(dgoal), _ptr(ws),
+                                              ws.numel(), _ptr(scratch), nsc, B, ctx.keep, ctx.lkeep, ctx.seed, _ptr(ctx.seed_dev), _stream(),
+                                              ctypes.byref(events) if events is not None else None)
         _lib.check(rc, "dgvit_got_backward")
         ctx.ws = None
         if evs:     # the kernels are queued, not finished: the hook orders its own stream behind the events (parallel.GradSync)
@@ -194,15 +200,22 @@ class _GoTEncoder(torch.autograd.Function):
         return (None, dgoal, None, None, None, None, None, *grads)
 
 
-def got_encoder(img, goal, cfg_tuple, params, dropout_keep=1.0, dropout_seed=0, grad_hook=None):
+def got_encoder(img, goal, cfg_tuple, params, dropout_keep=1.0, dropout_seed=0, grad_hook=None, layer_dropout_keep=1.0):
     """feat (B, D) = GoT.forward(img (B,H,W), goal (B,D)); params in the table order of dgvit_hip.h.
+    ``dropout_keep``: 1 - emb_dropout (train mode; 1 in eval mode); ``layer_dropout_keep``: 1 - the transformer ``dropout`` (train mode;
+    1 in eval mode), applied at the four sites of every block (include/dgvit_hip.h: dgvit_got_forward_v2).  Both masks come from
+    ``dropout_seed`` (a host int, or a 1-element int64 device tensor inside graph capture).
     ``grad_hook(flat, ranges, events)``: called inside the backward, right after its kernels are queued, with the flat gradient buffer,
     the element range of every transformer block's gradients (last block first) and the HIP event recorded where that range is final
     (include/dgvit_hip.h: dgvit_grad_events) -- parallel.GradSync(overlap=True) starts the blocks' all-reduces there."""
     if img.shape[0] == 0:
         return _empty_batch((0, int(cfg_tuple[4])), [img, goal, *params])
     need_grad = torch.is_grad_enabled() and (goal.requires_grad or any(p is not None and p.requires_grad for p in params))
-    return _GoTEncoder.apply(img, goal, tuple(cfg_tuple), dropout_keep, dropout_seed, need_grad, grad_hook, *params)
+    lkeep = float(layer_dropout_keep)
+    if not 0.0 < lkeep <= 1.0:
+        raise DgvitError(f"layer_dropout_keep={lkeep} must be in (0, 1]")
+    keep = dropout_keep if lkeep == 1.0 else (float(dropout_keep), lkeep)
+    return _GoTEncoder.apply(img, goal, tuple(cfg_tuple), keep, dropout_seed, need_grad, grad_hook, *params)
 
 
 # ------------------------------------------------------------------------------------------------ CNN feature stack

@@ -8,7 +8,10 @@ fused HIP forward/backward (functional.got_encoder); none of them runs PyTorch m
 Differences from the reference, on purpose:
   * ``patch_size`` is honoured (the reference hard-wires 16x20 / Linear(320, dim), GoalFormer.py:137-139);
     with patch_size=(16, 20) the parameter shapes are identical;
-  * transformer ``dropout`` must be 0 (the only value the reference's nets ever use); ``pool`` 'cls' and 'mean' both work;
+  * transformer ``dropout`` (0 <= p < 1) is applied in train mode at the reference's four sites of every block -- attention
+    probabilities, to_out, FeedForward hidden and output (GoalFormer.py:47, 49, 68, 78) -- on the fp32 path only (the bf16
+    configuration refuses p > 0); the masks come from the forward's one Philox seed and are regenerated in the backward (nothing
+    is stored; include/dgvit_hip.h: dgvit_got_forward_v2).  ``pool`` 'cls' and 'mean' both work;
   * ``heads == 1 and dim_head == dim`` gives the reference's projection-less attention (``to_out = nn.Identity()``) on the fp32 path;
   * ``RMSNorm`` also works stand-alone (``unit_offset`` included).
 """
@@ -61,6 +64,7 @@ class Attention(_Holder):
         inner = dim_head * heads
         project_out = not (heads == 1 and dim_head == dim)      # GoalFormer.py:56
         self.heads, self.scale = heads, dim_head ** -0.5
+        self.dropout = nn.Dropout(dropout)      # GoalFormer.py:62,78 (probabilities; no parameters)
         self.to_qkv = nn.Linear(dim, inner * 3, bias=False)
         # GoalFormer.py:66-69: without a projection ``to_out`` is nn.Identity() -- no ``to_out`` keys in the state_dict, and the fused
         # encoder adds the head's output straight into the residual stream (param_table passes None for the two slots)
@@ -107,8 +111,9 @@ class GoT(nn.Module):
         assert image_height % patch_height == 0 and image_width % patch_width == 0, \
             'Image dimensions must be divisible by the patch size.'
         assert pool in {'cls', 'mean'}, 'pool type must be either cls (cls token) or mean (mean pooling)'
-        if dropout != 0.:
-            raise NotImplementedError("transformer dropout must be 0 (the reference never sets it)")
+        if not 0. <= dropout < 1.:
+            raise ValueError(f"transformer dropout={dropout} must be in [0, 1): p = 1 drops every branch output and attention "
+                             "probability (keep = 0 has no 1/keep scale)")
         num_patches = (image_height // patch_height) * (image_width // patch_width)
         # `channels` is accepted and ignored exactly like the reference (frames are single-channel, 3-D input)
         self.to_patch_embedding = nn.Sequential(Patchify(patch_height, patch_width),
@@ -158,11 +163,22 @@ class GoT(nn.Module):
         self._cfg = (*self._cfg[:10], flags)
         return self
 
+    def layer_dropout(self) -> float:
+        """The transformer ``dropout`` p (the reference's nn.Dropout modules inside the blocks; they all share it)."""
+        ff = self.transformer.layers[0][1].fn.net
+        return float(ff[2].p)
+
+    def _check_dropout_dtype(self, dtype):
+        if dtype == torch.bfloat16 and self.layer_dropout() > 0:
+            raise NotImplementedError(f"transformer dropout={self.layer_dropout()} is implemented on the fp32 path only; "
+                                      "the bf16 configuration needs dropout=0")
+
     def set_compute_dtype(self, dtype):
         """torch.float32 (default: exact fp32 MFMA path) or torch.bfloat16 (BASELINE config 5: bf16 storage for the GEMM
-        operands, fp32 residual stream / statistics / accumulation; parameters stay fp32 masters)."""
+        operands, fp32 residual stream / statistics / accumulation; parameters stay fp32 masters).  Transformer dropout > 0 is fp32 only."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute dtype {dtype} unsupported (torch.float32 or torch.bfloat16)")
+        self._check_dropout_dtype(dtype)
         self.compute_dtype = dtype
         return self
 
@@ -183,7 +199,9 @@ class GoT(nn.Module):
 
     def forward(self, img, goal):
         keep, seed = 1.0, 0
-        if self.training and self.dropout.p > 0:
+        lkeep = 1.0 - self.layer_dropout() if self.training else 1.0
+        self._check_dropout_dtype(self.compute_dtype)
+        if self.training and (self.dropout.p > 0 or lkeep < 1.0):
             keep = 1.0 - self.dropout.p
             if img.is_cuda and torch.cuda.is_current_stream_capturing():
                 # inside a HIP-graph capture a host seed would be frozen into every replay: draw it on the device
@@ -194,4 +212,4 @@ class GoT(nn.Module):
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:
             return F_.got_encoder_bf16(img, goal, self._cfg, params, self._bf16_weights, keep, seed, grad_hook=self._grad_hook)
-        return F_.got_encoder(img, goal, self._cfg, params, keep, seed, grad_hook=self._grad_hook)
+        return F_.got_encoder(img, goal, self._cfg, params, keep, seed, grad_hook=self._grad_hook, layer_dropout_keep=lkeep)

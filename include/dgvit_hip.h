@@ -139,6 +139,33 @@ int dgvit_got_backward_ev(const dgvit_config* cfg, const float* const* params, f
                           long long scratch_floats, int batch, float dropout_keep, unsigned long long dropout_seed,
                           const unsigned long long* dropout_seed_dev, void* stream, const dgvit_grad_events* events);
 
+/* Transformer-internal dropout (fp32 path): dgvit_got_forward_v2 / dgvit_got_backward_v2 / dgvit_got_backward_v2_ev are the calls
+ * above with one more argument, layer_dropout_keep in (0, 1] (= 1 - GoT(dropout=p); 1.0f in eval mode).  The entry points above
+ * are these with layer_dropout_keep = 1.  Below 1, train-mode nn.Dropout(dropout) is applied at the four sites of every transformer
+ * block (GoalFormer.py:47, 49, 68, 78); emb-dropout (dropout_keep) and these masks share dropout_seed / dropout_seed_dev; nothing is
+ * stored -- the backward regenerates every mask, so pass it the forward's keeps and seed.  The mask: Philox4x32-10 keyed by the seed,
+ * an element is kept when r * 2^-32 < keep and scaled by 1/keep; emb-dropout uses counter word z = 0, site s of layer l uses
+ * z = 0x44000000 | (l << 2) | s, and (x, y) = the 64-bit index i4 of the element's float4 group, lane = index % 4:
+ *   s = 0  attention probabilities (b, h, q, k) after softmax  i4 = ((b*H + h)*N + q)*ceil(N/4) + k/4, lane k % 4
+ *   s = 1  to_out output (token row, D), before the residual   i4 = (row*D + c)/4
+ *   s = 2  FeedForward hidden (token row, mlp_dim), after GELU  i4 = (row*mlp_dim + c)/4
+ *   s = 3  FeedForward output (token row, D), before the residual
+ * row = b*N + t, the absolute token row.  Projection-less attention (heads == 1, dim_head == dim) has no site 1.  The bf16 entry points
+ * do not take it.  Returns DGVIT_ERR_ARG when layer_dropout_keep is outside (0, 1]. */
+int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
+                         float* feat, float* workspace, long long workspace_floats, int batch, int save_for_backward,
+                         float dropout_keep, float layer_dropout_keep, unsigned long long dropout_seed,
+                         const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_backward_v2(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                          float* dgoal, const float* workspace, long long workspace_floats, float* scratch,
+                          long long scratch_floats, int batch, float dropout_keep, float layer_dropout_keep,
+                          unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                             float* dgoal, const float* workspace, long long workspace_floats, float* scratch,
+                             long long scratch_floats, int batch, float dropout_keep, float layer_dropout_keep,
+                             unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream,
+                             const dgvit_grad_events* events);
+
 /* ----------------------------------------------------------------------------------------------
  * Head Linears (got_sac_network.py:111,115-121,226,230-234,429,433-435):  y = act(x W^T + b)
  *   x (M, K), w (N, K), b (N) or NULL, y (M, N); act: 0 = identity, 1 = ReLU.
