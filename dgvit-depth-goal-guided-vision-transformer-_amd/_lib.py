@@ -23,6 +23,7 @@ class dgvit_config(Structure):
 
 FLAG_DENSE_LAST_BLOCK = 1    # include/dgvit_hip.h: DGVIT_FLAG_*
 FLAG_WGRAD_OVERLAP = 2
+FLAG_LONG_SEQUENCE = 4      # fp32 encoder: K / V-tiled attention for N > 288 tokens
 
 
 class dgvit_mlp_desc(Structure):
@@ -78,6 +79,9 @@ SIGNATURES = {
     "dgvit_rmsnorm_backward": (_I, [_P, _P, _LL, _P, _P, _LL, _P, _P, _LL, _I, _I, _P]),
     "dgvit_attention_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dgvit_attention_forward_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_attention_backward_tiled_scratch_floats": (_LL, [_I, _I, _I]),
+    "dgvit_attention_backward_tiled": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
     "dgvit_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_dropout": (_I, [_P, _LL, _ULL, _F, _P]),
     "dgvit_cnn_workspace_floats": (_LL, [_I, _I, _I]),

@@ -25,6 +25,7 @@ int g_block_stamp_layer = -1, g_block_stamp_now = 1;
 #endif
 static inline bool dense_last_block(const dgvit_config* c) { return (c->flags & DGVIT_FLAG_DENSE_LAST_BLOCK) != 0; }
 static inline bool wgrad_overlap(const dgvit_config* c) { return (c->flags & DGVIT_FLAG_WGRAD_OVERLAP) != 0; }
+static inline bool long_sequence(const dgvit_config* c) { return (c->flags & DGVIT_FLAG_LONG_SEQUENCE) != 0; }
 
 // ---------------------------------------------------------------------------------------------- helper stream
 // dgvit_got_backward forks every weight-gradient GEMM (+ its slab reduction) onto one internal non-blocking
@@ -147,6 +148,7 @@ int wgrad(const float* A, int lda, const float* B, int ldb, float* dW, float* db
 struct Dims {
   int B, P, N, D, I, M, L, H, dh, pd, pool_mean;
   int proj;       // 0: heads == 1 and dim_head == dim -- the reference's Attention has no output projection (to_out = nn.Identity(), GoalFormer.py:56,66-69)
+  int tiled;      // DGVIT_FLAG_LONG_SEQUENCE and N > 288: the attention runs on the K / V-tiled kernels (attention_long.hip)
   long long T;
 };
 
@@ -191,7 +193,12 @@ int make_dims(const dgvit_config* c, int batch, Dims& d) {
   d.pool_mean = c->pool_mean ? 1 : 0;
   d.proj = !(d.H == 1 && d.dh == d.D);
   d.T = (long long)batch * d.N;
-  DGVIT_CHECK_ARG(d.N <= 288, "tokens N=%d exceeds the fused-attention limit (288)", d.N);
+  DGVIT_CHECK_ARG(d.N <= 288 || long_sequence(c),
+                  "tokens N=%d exceeds the fused-attention limit (288); set DGVIT_FLAG_LONG_SEQUENCE in dgvit_config.flags "
+                  "(GoT.set_schedule(long_sequence=True)) for the K/V-tiled attention", d.N);
+  // (N <= 288 keeps the fused kernels with the flag set too: bit-identical results; the small-batch block path (N <= 128) and the
+  //  one-query kernel (N <= 64) are never reached by a tiled shape)
+  d.tiled = long_sequence(c) && d.N > 288;
   DGVIT_CHECK_ARG(d.T < (1ll << 31) && d.T * (long long)(3 * d.I > d.M ? 3 * d.I : d.M) < (1ll << 40), "batch too large");
   return DGVIT_OK;
 }
@@ -357,6 +364,7 @@ extern "C" long long dgvit_got_workspace_floats(const dgvit_config* cfg, int bat
 namespace {
 struct Bs {  // backward scratch carve-up
   long long dxa, dxb, dln, dqkv, dao, dh1, dm1, dm3, part, part_ln2, part_ln1, slabs, total, slabs_floats;
+  long long delta, delta_floats;   // the tiled attention backward's rowsum(dO o O) (0 floats unless Dims::tiled)
   long long sl_fc2, sl_fc1, sl_out, sl_qkv, n_fc2, n_fc1, n_out, n_qkv;   // a layer's four weight gradients keep separate slab regions
   long long sk_counters, sk_slabs, sk_ncounters, sk_slab_floats;          // in-launch split-K scratch of the data-gradient GEMMs
 };
@@ -400,6 +408,7 @@ Bs make_bs(const Dims& d) {
   s.sk_ncounters = sn.tiles; s.sk_slab_floats = sn.slab;
   s.sk_counters = o; o += al4(sn.tiles);
   s.sk_slabs = o; o += al4(sn.slab);
+  s.delta = o; s.delta_floats = d.tiled ? attention_bwd_tiled_scratch(d.B, d.N, d.H) : 0; o += al4(s.delta_floats);
   s.total = o;
   return s;
 }
@@ -551,7 +560,10 @@ extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const*
       TRY(gemm_f32(GEMM_NT, EPI_STORE, q, 1, st));
     }
     const LayerDrop dr_attn = site(i, DROP_ATTN);
-    TRY(attention_fwd(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+    if (d.tiled)
+      TRY(attention_fwd_tiled(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+    else
+      TRY(attention_fwd(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
     if (!d.proj) {
       // to_out = nn.Identity() (GoalFormer.py:56,66-69): the head's output IS the branch output (I == D): xmid = attn + x (:103)
       TRY(add_rows(lb + w.ao, (long long)rs * d.I, x, (long long)rs * d.D, lb + w.xmid, (long long)rs * d.D, tok, d.D, st));
@@ -777,8 +789,12 @@ extern "C" int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* co
     }
     // (no output projection: the gradient of the attention output is the residual-stream gradient itself, I == D)
     const LayerDrop dr_attn = site(i, DROP_ATTN);
-    TRY(attention_bwd(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st,
-                      ldrop ? &dr_attn : nullptr));
+    if (d.tiled)
+      TRY(attention_bwd_tiled(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, scratch + s.delta, s.delta_floats, d.B, d.N, d.H,
+                              d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+    else
+      TRY(attention_bwd(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st,
+                        ldrop ? &dr_attn : nullptr));
     TRY(fork());
     if (!last) {
       TRY(wgrad(dqkv, 3 * d.I, lb + w.ln1, d.D, lg[L_QKV], nullptr, 3 * d.I, d.D, T, slabs + s.sl_qkv, s.n_qkv, sw, gq));
@@ -956,6 +972,17 @@ extern "C" int dgvit_attention_forward(const float* qkv, float* out, float* lse,
 extern "C" int dgvit_attention_backward(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
                                         int B, int N, int H, int dh, void* stream) {
   return attention_bwd(qkv, out, dout, lse, dqkv, B, N, H, dh, N, (hipStream_t)stream);
+}
+extern "C" int dgvit_attention_forward_tiled(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, void* stream) {
+  return attention_fwd_tiled(qkv, out, lse, B, N, H, dh, nq, (hipStream_t)stream);
+}
+extern "C" int dgvit_attention_backward_tiled(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* scratch,
+                                              long long scratch_floats, int B, int N, int H, int dh, int nq, void* stream) {
+  return attention_bwd_tiled(qkv, out, dout, lse, dqkv, scratch, scratch_floats, B, N, H, dh, nq, (hipStream_t)stream);
+}
+extern "C" long long dgvit_attention_backward_tiled_scratch_floats(int B, int N, int H) {
+  if (B <= 0 || N <= 0 || H <= 0) return -1;
+  return attention_bwd_tiled_scratch(B, N, H);
 }
 extern "C" int dgvit_patchify(const float* img, float* patches, int B, int ih, int iw, int ph, int pw, void* stream) {
   return patchify(img, patches, B, ih, iw, ph, pw, (hipStream_t)stream);

@@ -15,6 +15,12 @@ int colsum(const float*, long long, float*, float*, int, int, int, hipStream_t);
 int attention_fwd(const float*, float*, float*, int, int, int, int, int, hipStream_t, const LayerDrop* drop = nullptr);
 int attention_bwd(const float*, const float*, const float*, const float*, float*, int, int, int, int, int, hipStream_t,
                   const LayerDrop* drop = nullptr);
+// attention_long.hip: K / V-tiled attention for any N (the encoder takes it for N > 288 under DGVIT_FLAG_LONG_SEQUENCE); the backward
+// needs attention_bwd_tiled_scratch(B, N, H) floats of scratch (delta = rowsum(dO o O) of every row)
+int attention_fwd_tiled(const float*, float*, float*, int, int, int, int, int, hipStream_t, const LayerDrop* drop = nullptr);
+long long attention_bwd_tiled_scratch(int B, int N, int H);
+int attention_bwd_tiled(const float*, const float*, const float*, const float*, float*, float*, long long, int, int, int, int, int,
+                        hipStream_t, const LayerDrop* drop = nullptr);
 int patchify(const float*, float*, int, int, int, int, int, hipStream_t);
 int add_rows(const float*, long long, const float*, long long, float*, long long, long long, int, hipStream_t);
 int goal_row(const float*, const float*, float*, int, int, int, hipStream_t);

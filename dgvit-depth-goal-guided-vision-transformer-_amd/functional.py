@@ -558,6 +558,35 @@ def op_attention_bwd(qkv, out, dout, lse, heads, dim_head):
     return dqkv
 
 
+def op_attention_fwd_tiled(qkv, heads, dim_head, nq=None):
+    """The K / V-tiled attention kernels (any N; the encoder's path for N > 288 under long_sequence): out and lse rows < nq (default N)
+    are written (the other rows stay uninitialised)."""
+    lib = _lib.load()
+    qkv = _dev(qkv, "qkv")
+    B, N, W = qkv.shape
+    assert W == 3 * heads * dim_head
+    nq = N if nq is None else nq
+    out = torch.empty(B, N, heads * dim_head, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(B, heads, N, dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.dgvit_attention_forward_tiled(_ptr(qkv), _ptr(out), _ptr(lse), B, N, heads, dim_head, nq, _stream()),
+               "dgvit_attention_forward_tiled")
+    return out, lse
+
+
+def op_attention_bwd_tiled(qkv, out, dout, lse, heads, dim_head, nq=None, dqkv=None):
+    """Gradient on the tiled kernels: dq rows < nq (default N) and every dk / dv row are written into `dqkv` (default: a new
+    uninitialised tensor)."""
+    lib = _lib.load()
+    B, N, _ = qkv.shape
+    nq = N if nq is None else nq
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    nsc = lib.dgvit_attention_backward_tiled_scratch_floats(B, N, heads)
+    sc = torch.empty(max(nsc, 1), dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.dgvit_attention_backward_tiled(_ptr(qkv), _ptr(out), _ptr(_dev(dout, "dout")), _ptr(lse), _ptr(dqkv), _ptr(sc), nsc,
+                                                  B, N, heads, dim_head, nq, _stream()), "dgvit_attention_backward_tiled")
+    return dqkv
+
+
 def op_patchify(img, patch):
     lib = _lib.load()
     img = _dev(img, "img")

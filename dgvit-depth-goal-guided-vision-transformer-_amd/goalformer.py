@@ -153,15 +153,31 @@ class GoT(nn.Module):
         self._bf16_weights.invalidate()
         return self
 
-    def set_schedule(self, dense_last_block: bool = False, wgrad_overlap: bool = False):
+    def set_schedule(self, dense_last_block: bool = False, wgrad_overlap: bool = False, long_sequence: bool = False):
         """Per-module schedule options, passed to the C ABI with every call (``dgvit_config.flags``; nothing global).
         ``dense_last_block``: run the whole last block instead of its token-0 rows only (identical results; A/B measurements).
         ``wgrad_overlap``: the backward runs the weight-gradient GEMMs on a helper stream beside the data-gradient chain
-        (+3..5 % frames/s at BASELINE config 3; per-kernel timings stop being interpretable)."""
-        from ._lib import FLAG_DENSE_LAST_BLOCK, FLAG_WGRAD_OVERLAP
-        flags = (FLAG_DENSE_LAST_BLOCK if dense_last_block else 0) | (FLAG_WGRAD_OVERLAP if wgrad_overlap else 0)
+        (+3..5 % frames/s at BASELINE config 3; per-kernel timings stop being interpretable).
+        ``long_sequence``: lift the fp32 encoder's 288-token limit -- for N > 288 the attention runs on K / V-tiled kernels (N <= 288 is
+        unchanged, bit for bit); the backward needs B*H*N floats more scratch.  fp32 only (the bf16 configuration stops at 256 tokens)."""
+        from ._lib import FLAG_DENSE_LAST_BLOCK, FLAG_LONG_SEQUENCE, FLAG_WGRAD_OVERLAP
+        if long_sequence:
+            self._check_long_sequence_dtype(self.compute_dtype, True)
+        flags = ((FLAG_DENSE_LAST_BLOCK if dense_last_block else 0) | (FLAG_WGRAD_OVERLAP if wgrad_overlap else 0)
+                 | (FLAG_LONG_SEQUENCE if long_sequence else 0))
         self._cfg = (*self._cfg[:10], flags)
         return self
+
+    def long_sequence(self) -> bool:
+        """Whether ``set_schedule(long_sequence=True)`` is in effect."""
+        from ._lib import FLAG_LONG_SEQUENCE
+        return bool(self._cfg[10] & FLAG_LONG_SEQUENCE)
+
+    @staticmethod
+    def _check_long_sequence_dtype(dtype, long_sequence):
+        if dtype == torch.bfloat16 and long_sequence:
+            raise NotImplementedError("long_sequence (the K/V-tiled attention for more than 288 tokens) is implemented on the fp32 path "
+                                      "only; the bf16 configuration keeps its 256-token limit")
 
     def layer_dropout(self) -> float:
         """The transformer ``dropout`` p (the reference's nn.Dropout modules inside the blocks; they all share it)."""
@@ -179,6 +195,7 @@ class GoT(nn.Module):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute dtype {dtype} unsupported (torch.float32 or torch.bfloat16)")
         self._check_dropout_dtype(dtype)
+        self._check_long_sequence_dtype(dtype, self.long_sequence())
         self.compute_dtype = dtype
         return self
 

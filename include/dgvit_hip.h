@@ -11,7 +11,7 @@
  *   - nothing allocates, frees or synchronises; all work is enqueued on `stream` (a hipStream_t passed
  *     as void*, 0 = the null stream); callable from any host thread (autograd's backward thread too);
  *   - no mutable global state besides one-time initialisation (a helper stream, per-device kernel attributes): there are no
- *     setter functions; the two schedule options are fields of dgvit_config (`flags`) and travel with every call.  The A/B and
+ *     setter functions; the schedule options (DGVIT_FLAG_*) are fields of dgvit_config (`flags`) and travel with every call.  The A/B and
  *     diagnostic knobs of tools/ exist only in the separately built libdgvit_hip_diag.so (include/dgvit_hip_diag.h);
  *   - return value 0 = success, negative = error; dgvit_last_error() gives the thread-local message;
  *   - sizes are element counts unless a name says bytes.
@@ -44,7 +44,7 @@ int dgvit_device_count(void);
 /* ----------------------------------------------------------------------------------------------
  * Encoder shape = the GoT constructor arguments (GoalFormer.py:124-154).  patch_h/patch_w are honoured
  * (the reference hard-wires 16x20, GoalFormer.py:137-139).  dim_head must be 64 or 32; tokens
- * N = (image_h/patch_h)*(image_w/patch_w) + 1 <= 288.
+ * N = (image_h/patch_h)*(image_w/patch_w) + 1 <= 288, or any N with DGVIT_FLAG_LONG_SEQUENCE (fp32 path).
  * -------------------------------------------------------------------------------------------- */
 typedef struct dgvit_config {
   int image_h, image_w;
@@ -66,6 +66,11 @@ typedef struct dgvit_config {
  * MI355X, but concurrent kernels stretch each other's durations, so per-kernel timings (dgvit_profile_*, rocprof) stop being
  * interpretable.  Off: everything stays on the caller's stream. */
 #define DGVIT_FLAG_WGRAD_OVERLAP 2
+/* Lifts the N <= 288 token limit of the fp32 encoder: for N > 288 the attention forward and backward run on K / V-tiled kernels that
+ * stream 64-row tiles through LDS (dgvit_attention_forward_tiled below); N <= 288 keeps the fused kernels, bit-identical to the flag
+ * being unset.  The backward scratch (dgvit_got_backward_scratch_floats) grows by B*H*N floats when N > 288 and the flag is set; with
+ * the flag unset every size, result and refusal is unchanged.  The bf16 configuration keeps its N <= 256 limit. */
+#define DGVIT_FLAG_LONG_SEQUENCE 4
 
 /* Parameter / gradient tables: arrays of DGVIT_NUM_GLOBAL_PARAMS + DGVIT_PARAMS_PER_LAYER*depth device
  * pointers in this order (reference state_dict key in brackets, prefix "trans."):
@@ -249,6 +254,14 @@ int dgvit_rmsnorm_backward(const float* dy, const float* x, long long ldx, const
 int dgvit_attention_forward(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, void* stream);
 int dgvit_attention_backward(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
                              int B, int N, int H, int dh, void* stream);
+/* The same attention core on the K / V-tiled kernels the encoder uses for N > 288 under DGVIT_FLAG_LONG_SEQUENCE, for any N >= 1
+ * (dh 64 or 32).  nq = number of leading query rows needed (1..N): forward writes out / lse rows < nq and reads every key; backward
+ * writes dq rows < nq only and dk / dv for every row.  The backward is deterministic (no atomics) and needs
+ * dgvit_attention_backward_tiled_scratch_floats(B, N, H) floats of scratch. */
+int dgvit_attention_forward_tiled(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, void* stream);
+long long dgvit_attention_backward_tiled_scratch_floats(int B, int N, int H);
+int dgvit_attention_backward_tiled(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* scratch,
+                                   long long scratch_floats, int B, int N, int H, int dh, int nq, void* stream);
 
 /* 'b (h p1) (w p2) -> b (h w) (p1 p2)' (GoalFormer.py:138) */
 int dgvit_patchify(const float* img, float* patches, int B, int image_h, int image_w, int patch_h, int patch_w,
