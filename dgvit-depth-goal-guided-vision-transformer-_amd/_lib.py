@@ -58,6 +58,8 @@ SIGNATURES = {
     "dgvit_got_forward_v2": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _LL, _I, _I, _F, _F, _ULL, _P, _P]),
     "dgvit_got_backward_v2": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
     "dgvit_got_backward_v2_ev": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P, POINTER(dgvit_grad_events)]),
+    "dgvit_got_backward_v3": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_v3_ev": (_I, [_CFG, _TABLE, _TABLE, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P, POINTER(dgvit_grad_events)]),
     "dgvit_event_create": (_I, [POINTER(c_void_p)]),
     "dgvit_event_destroy": (_I, [_P]),
     "dgvit_stream_wait_event": (_I, [_P, _P]),
@@ -89,6 +91,7 @@ SIGNATURES = {
     "dgvit_cnn_backward_scratch_floats": (_LL, [_I, _I, _I]),
     "dgvit_cnn_forward": (_I, [_P, _TABLE, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_cnn_backward": (_I, [_P, _TABLE, _TABLE, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
+    "dgvit_cnn_backward_v2": (_I, [_P, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_gather_rows": (_I, [_P, _P, _P, _LL, _LL, _LL, _P]),
     "dgvit_depth_preprocess_scratch_floats": (_LL, [_I, _I, _I]),
     "dgvit_depth_to_state": (_I, [_P, _P, _F, _ULL, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
@@ -105,6 +108,9 @@ SIGNATURES = {
     "dgvit_got_bf16_backward_scratch_bytes": (_LL, [_CFG, _I]),
     "dgvit_got_backward_bf16": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P]),
     "dgvit_got_backward_bf16_ev": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P, POINTER(dgvit_grad_events)]),
+    "dgvit_got_backward_bf16_v2": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_bf16_v2_ev": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _ULL, _P, _P,
+                                           POINTER(dgvit_grad_events)]),
     "dgvit_wgrad_bf16_scratch_floats": (_LL, [_I, _I, _I]),
     "dgvit_wgrad_bf16": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
     "dgvit_cast_f32_bf16": (_I, [_P, _P, _LL, _P]),

@@ -56,7 +56,9 @@ enum GemmEpilogue {
   EPI_SPLITK = 5,  // C = slab[z][m][n] = acc   (reduced later by dgvit_reduce_slabs)
   EPI_GELU2D = 6,  // t = acc + bias ; C = gelu_erf'(t) ; C2 = gelu_erf(t)        (training forward of fc1: the factor the backward needs)
   EPI_DMUL = 7,    // C = acc * aux[m][n]                                          (its data gradient: dh = (dy W2) * gelu'(h), factor stored)
-  EPI_GELU = 8     // C = gelu_erf(acc + bias)                                     (no-grad forward of fc1: the pre-activation is never stored)
+  EPI_GELU = 8,    // C = gelu_erf(acc + bias)                                     (no-grad forward of fc1: the pre-activation is never stored)
+  EPI_UNPATCH = 9  // img[b][py*ph + i][px*pw + j] = acc[m][n], m = b*P + py*gw + px, n = i*pw + j  (image gradient: the inverse of the patch
+                   //   gather; NN only, geometry in the g_* fields with g_img == null, C = the (B, H, W) image)
 };
 
 struct GemmParams {

@@ -7,7 +7,8 @@
 // weight permuted to [cout][(kh,kw,cin)], bias + ReLU fused in its epilogue; the output rows ARE the next layer's
 // NHWC input.  Backward: dW = dY^T cols (split-K GEMM, bias gradient fused), dcols = dY W (GEMM), and a gather-style
 // col2im (each input pixel sums the <= 9 windows that cover it: deterministic, no atomics) with the previous
-// layer's ReLU mask fused.  The single-channel first layer pads K = 25 to 28 so that it takes the float4 path.
+// layer's ReLU mask fused; its unmasked single-channel form turns conv1's column gradient into the frame gradient.
+// The single-channel first layer pads K = 25 to 28 so that it takes the float4 path.
 #include "common.h"
 #include "kernels.h"
 
@@ -50,9 +51,13 @@ __global__ void __launch_bounds__(256) im2col_c1_kernel(const float* __restrict_
 }
 
 // dx[b][y][x][c] = relu'(xin) * sum over windows (oh,ow,kh,kw) with oh*2+kh == y, ow*2+kw == x of dcols[...]
+// RELU == false: no mask (the image gradient of conv1: the frame is not the output of a ReLU); xin is not read.  V: channels per thread,
+// 4 (C % 4 == 0, float4) or 1 (the single-channel frame).  dcols rows are KP floats (conv1: the 25 real taps of 28; the padding is never read).
+template <int V, bool RELU>
 __global__ void __launch_bounds__(256) col2im_relu_kernel(const float* __restrict__ dcols, const float* __restrict__ xin,
-                                                          float* __restrict__ dx, int B, int H, int W, int C, int OH, int OW) {
-  const int c4n = C / 4;
+                                                          float* __restrict__ dx, int B, int H, int W, int C, int OH, int OW, int KP) {
+  typedef float vec_t __attribute__((ext_vector_type(V)));
+  const int c4n = C / V;
   const long long total = (long long)B * H * W * c4n;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
@@ -61,21 +66,23 @@ __global__ void __launch_bounds__(256) col2im_relu_kernel(const float* __restric
   const int xw = (int)(r % W); r /= W;
   const int y = (int)(r % H);
   const long long b = r / H;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  const long long rowlen = (long long)KS * KS * C;
+  vec_t s = (vec_t)0.f;
+  const long long rowlen = KP;
   for (int kh = y & 1; kh < KS; kh += 2) {
     const int oh = (y - kh) / 2;
     if (y - kh < 0 || oh >= OH) continue;
     for (int kw = xw & 1; kw < KS; kw += 2) {
       const int ow = (xw - kw) / 2;
       if (xw - kw < 0 || ow >= OW) continue;
-      const float4 v = *reinterpret_cast<const float4*>(dcols + ((b * OH + oh) * OW + ow) * rowlen + (kh * KS + kw) * C + c4 * 4);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      s += *reinterpret_cast<const vec_t*>(dcols + ((b * OH + oh) * OW + ow) * rowlen + (kh * KS + kw) * C + c4 * V);
     }
   }
-  const float4 m = reinterpret_cast<const float4*>(xin)[idx];
-  s.x = m.x > 0.f ? s.x : 0.f; s.y = m.y > 0.f ? s.y : 0.f; s.z = m.z > 0.f ? s.z : 0.f; s.w = m.w > 0.f ? s.w : 0.f;
-  reinterpret_cast<float4*>(dx)[idx] = s;
+  if constexpr (RELU) {
+    const vec_t m = reinterpret_cast<const vec_t*>(xin)[idx];
+#pragma unroll
+    for (int e = 0; e < V; ++e) s[e] = m[e] > 0.f ? s[e] : 0.f;
+  }
+  reinterpret_cast<vec_t*>(dx)[idx] = s;
 }
 
 // reference layout (cout, cin, KS, KS) <-> packed (cout, KP) with k = (kh*KS + kw)*cin + c; KP >= KS*KS*cin, tail zero.
@@ -163,7 +170,16 @@ int im2col(const float* x, float* cols, int B, int H, int W, int C, int OH, int 
 
 int col2im_relu(const float* dcols, const float* xin, float* dx, int B, int H, int W, int C, int OH, int OW, hipStream_t st) {
   DGVIT_CHECK_ARG(C % 4 == 0, "col2im: channels must be a multiple of 4");
-  hipLaunchKernelGGL(col2im_relu_kernel, dim3(nblk((long long)B * H * W * (C / 4))), dim3(256), 0, st, dcols, xin, dx, B, H, W, C, OH, OW);
+  hipLaunchKernelGGL((col2im_relu_kernel<4, true>), dim3(nblk((long long)B * H * W * (C / 4))), dim3(256), 0, st, dcols, xin, dx, B, H, W, C,
+                     OH, OW, KS * KS * C);
+  DGVIT_CHECK_LAUNCH("col2im");
+  return DGVIT_OK;
+}
+
+int col2im_frame(const float* dcols, float* dx, int B, int H, int W, int OH, int OW, int KP, hipStream_t st) {
+  DGVIT_CHECK_ARG(KP >= KS * KS, "col2im: column rows of %d floats hold fewer than the %d taps", KP, KS * KS);
+  hipLaunchKernelGGL((col2im_relu_kernel<1, false>), dim3(nblk((long long)B * H * W)), dim3(256), 0, st, dcols, nullptr, dx, B, H, W, 1, OH,
+                     OW, KP);
   DGVIT_CHECK_LAUNCH("col2im");
   return DGVIT_OK;
 }

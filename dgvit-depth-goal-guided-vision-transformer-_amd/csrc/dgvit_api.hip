@@ -653,6 +653,17 @@ extern "C" int dgvit_stream_wait_event(void* stream, void* event) {
   return DGVIT_OK;
 }
 
+// Gradient with respect to the frame (dgvit_got_backward_v3, dgvit_got_backward_bf16_v2): dimg = unpatchify(dpatch W_pe), dpatch (B * P, D)
+// the packed patch rows of the token-assembly gradient.  ONE NN GEMM whose epilogue stores straight into the (B, H, W) image (EPI_UNPATCH,
+// the inverse of the forward's patch gather): no (B * P, pd) buffer, no permutation pass.  Not split (no counters): the launch is thousands
+// of tiles at training batches, and a split would need scratch the size queries do not have.
+static int image_grad(const dgvit_config* c, const Dims& d, const float* dpatch, const float* wpe, float* dimg, hipStream_t st) {
+  GemmParams p = gp(dpatch, d.D, wpe, d.pd, dimg, d.pd, d.B * d.P, d.pd, d.D);
+  p.g_wi = c->image_w; p.g_hw = c->image_h * c->image_w; p.g_ph = c->patch_h; p.g_pw = c->patch_w;
+  p.g_gw = c->image_w / c->patch_w; p.g_P = d.P;
+  return gemm_f32(GEMM_NN, EPI_UNPATCH, p, 1, st);
+}
+
 extern "C" int dgvit_got_backward(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
                                   float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
                                   int batch, float keep, unsigned long long seed, const unsigned long long* seed_dev,
@@ -673,12 +684,28 @@ extern "C" int dgvit_got_backward_v2(const dgvit_config* cfg, const float* const
                                      float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
                                      int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
                                      void* stream) {
-  return dgvit_got_backward_v2_ev(cfg, params, grads, dfeat, dgoal, ws, ws_floats, scratch, scratch_floats, batch, keep, lkeep, seed, seed_dev,
-                                  stream, nullptr);
+  return dgvit_got_backward_v3_ev(cfg, params, grads, dfeat, dgoal, nullptr, ws, ws_floats, scratch, scratch_floats, batch, keep, lkeep, seed,
+                                  seed_dev, stream, nullptr);
 }
 
 extern "C" int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
                                         float* dgoal, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
+                                        int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
+                                        void* stream, const dgvit_grad_events* events) {
+  return dgvit_got_backward_v3_ev(cfg, params, grads, dfeat, dgoal, nullptr, ws, ws_floats, scratch, scratch_floats, batch, keep, lkeep, seed,
+                                  seed_dev, stream, events);
+}
+
+extern "C" int dgvit_got_backward_v3(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                                     float* dgoal, float* dimg, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
+                                     int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
+                                     void* stream) {
+  return dgvit_got_backward_v3_ev(cfg, params, grads, dfeat, dgoal, dimg, ws, ws_floats, scratch, scratch_floats, batch, keep, lkeep, seed,
+                                  seed_dev, stream, nullptr);
+}
+
+extern "C" int dgvit_got_backward_v3_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                                        float* dgoal, float* dimg, const float* ws, long long ws_floats, float* scratch, long long scratch_floats,
                                         int batch, float keep, float lkeep, unsigned long long seed, const unsigned long long* seed_dev,
                                         void* stream, const dgvit_grad_events* events) {
   hipStream_t st = (hipStream_t)stream;
@@ -832,11 +859,13 @@ extern "C" int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* co
     HIP_TRY(hipMemcpy2DAsync(dgoal, sizeof(float) * d.D, dx, sizeof(float) * d.N * d.D, sizeof(float) * d.D, d.B,
                              hipMemcpyDeviceToDevice, st));
   if (grads[P_POS]) TRY(colsum(dx, (long long)d.N * d.D, grads[P_POS], part, d.B, d.N * d.D, 0, st));  // dpos = sum over frames
-  if (!grads[P_PW] && !grads[P_PB]) return DGVIT_OK;
+  const bool patch_grads = grads[P_PW] || grads[P_PB];
+  if (!patch_grads && !dimg) return DGVIT_OK;
   // patch rows of dx0 (token rows 1..P of every frame) packed densely, then dW_pe = dx_patch^T patches, db_pe = column sums
   HIP_TRY(hipMemcpy2DAsync(dln, sizeof(float) * d.P * d.D, dx + d.D, sizeof(float) * d.N * d.D, sizeof(float) * d.P * d.D, d.B,
                            hipMemcpyDeviceToDevice, st));
-  TRY(wgrad(dln, d.D, ws + w.patches, d.pd, grads[P_PW], grads[P_PB], d.D, d.pd, d.B * d.P, slabs, s.slabs_floats, st));
+  if (patch_grads) TRY(wgrad(dln, d.D, ws + w.patches, d.pd, grads[P_PW], grads[P_PB], d.D, d.pd, d.B * d.P, slabs, s.slabs_floats, st));
+  if (dimg) TRY(image_grad(cfg, d, dln, params[P_PW], dimg, st));   // (whether or not W_pe / b_pe are frozen)
   return DGVIT_OK;
 }
 
@@ -1110,11 +1139,21 @@ extern "C" int dgvit_cnn_forward(const float* img, const float* const* params, f
 extern "C" int dgvit_cnn_backward(const float* img, const float* const* params, float* const* grads, const float* dfeat,
                                   const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H,
                                   int W, void* stream) {
+  DGVIT_CHECK_ARG(grads, "dgvit_cnn_backward: null pointer");
+  for (int i = 0; i < 6; ++i) DGVIT_CHECK_ARG(grads[i], "cnn parameter/gradient %d is null", i);
+  return dgvit_cnn_backward_v2(img, params, grads, dfeat, nullptr, ws, ws_floats, scratch, scratch_floats, B, H, W, stream);
+}
+
+// grads[i] == NULL: frozen parameter (its weight gradient is skipped); dimg != NULL: the frame gradient too (conv1's column gradient and an
+// unmasked col2im onto the single-channel frame)
+extern "C" int dgvit_cnn_backward_v2(const float* img, const float* const* params, float* const* grads, const float* dfeat, float* dimg,
+                                     const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H,
+                                     int W, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   ConvDims d;
   TRY(make_conv_dims(B, H, W, d));
   DGVIT_CHECK_ARG(img && params && grads && dfeat && ws && scratch, "dgvit_cnn_backward: null pointer");
-  for (int i = 0; i < 6; ++i) DGVIT_CHECK_ARG(params[i] && grads[i], "cnn parameter/gradient %d is null", i);
+  for (int i = 0; i < 6; ++i) DGVIT_CHECK_ARG(params[i], "cnn parameter %d is null", i);
   if (ws_floats < dgvit_cnn_workspace_floats(B, H, W) || scratch_floats < dgvit_cnn_backward_scratch_floats(B, H, W))
     return dgvit_set_error(DGVIT_ERR_WORKSPACE, "dgvit_cnn_backward: workspace or scratch too small");
   const float* act[4] = {img, ws, ws + al4(d.M[1] * 16), ws + al4(d.M[1] * 16) + al4(d.M[2] * 64)};
@@ -1133,9 +1172,19 @@ extern "C" int dgvit_cnn_backward(const float* img, const float* const* params, 
   for (int l = 2; l >= 0; --l) {
     const int cout = d.C[l + 1], KP = d.KP[l];
     const int M = (int)d.M[l + 1];
-    TRY(im2col(act[l], cols, B, d.H[l], d.W[l], d.C[l], d.H[l + 1], d.W[l + 1], KP, st));
-    TRY(wgrad(dy, cout, cols, KP, dwp, grads[2 * l + 1], cout, KP, M, slabs, slab_floats, st));
-    TRY(weight_pack(dwp, grads[2 * l], cout, d.C[l], KP, 1, st));
+    if (grads[2 * l] || grads[2 * l + 1]) {
+      TRY(im2col(act[l], cols, B, d.H[l], d.W[l], d.C[l], d.H[l + 1], d.W[l + 1], KP, st));
+      TRY(wgrad(dy, cout, cols, KP, grads[2 * l] ? dwp : nullptr, grads[2 * l + 1], cout, KP, M, slabs, slab_floats, st));
+      if (grads[2 * l]) TRY(weight_pack(dwp, grads[2 * l], cout, d.C[l], KP, 1, st));
+    }
+    if (l == 0 && dimg) {
+      // conv1: dcols (M1 x 28) = dy W1 (the padded taps' weights are zero), then each pixel sums the <= 9 windows that cover it -- no
+      // ReLU mask, the frame is an input
+      TRY(weight_pack(params[0], wp, cout, 1, KP, 0, st));
+      GemmParams p = gp(dy, cout, wp, KP, cols, KP, M, KP, cout);
+      TRY(gemm_f32(GEMM_NN, EPI_STORE, p, 1, st));
+      TRY(col2im_frame(cols, dimg, B, H, W, d.H[1], d.W[1], KP, st));
+    }
     if (l > 0) {
       TRY(weight_pack(params[2 * l], wp, cout, d.C[l], KP, 0, st));
       GemmParams p = gp(dy, cout, wp, KP, cols, KP, M, KP, cout);   // dcols = dy W  (cols buffer reused)
@@ -1526,8 +1575,8 @@ extern "C" int dgvit_got_backward_bf16(const dgvit_config* cfg, const float* con
                                        float* const* grads, const float* dfeat, float* dgoal, const float* img,
                                        const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
                                        float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-  return dgvit_got_backward_bf16_ev(cfg, params, wpack, grads, dfeat, dgoal, img, workspace, ws_bytes, scratch, scratch_bytes, batch, keep, seed,
-                                    seed_dev, stream, nullptr);
+  return dgvit_got_backward_bf16_v2_ev(cfg, params, wpack, grads, dfeat, dgoal, nullptr, img, workspace, ws_bytes, scratch, scratch_bytes, batch,
+                                       keep, seed, seed_dev, stream, nullptr);
 }
 
 extern "C" int dgvit_got_backward_bf16_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
@@ -1535,6 +1584,23 @@ extern "C" int dgvit_got_backward_bf16_ev(const dgvit_config* cfg, const float* 
                                           const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
                                           float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream,
                                           const dgvit_grad_events* events) {
+  return dgvit_got_backward_bf16_v2_ev(cfg, params, wpack, grads, dfeat, dgoal, nullptr, img, workspace, ws_bytes, scratch, scratch_bytes, batch,
+                                       keep, seed, seed_dev, stream, events);
+}
+
+extern "C" int dgvit_got_backward_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                          float* const* grads, const float* dfeat, float* dgoal, float* dimg, const float* img,
+                                          const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
+                                          float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  return dgvit_got_backward_bf16_v2_ev(cfg, params, wpack, grads, dfeat, dgoal, dimg, img, workspace, ws_bytes, scratch, scratch_bytes, batch,
+                                       keep, seed, seed_dev, stream, nullptr);
+}
+
+extern "C" int dgvit_got_backward_bf16_v2_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                             float* const* grads, const float* dfeat, float* dgoal, float* dimg, const float* img,
+                                             const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
+                                             float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream,
+                                             const dgvit_grad_events* events) {
   hipStream_t st = (hipStream_t)stream;
   Dims d;
   TRY(make_dims(cfg, batch, d));
@@ -1630,12 +1696,18 @@ extern "C" int dgvit_got_backward_bf16_ev(const dgvit_config* cfg, const float* 
     HIP_TRY(hipMemcpy2DAsync(dgoal, sizeof(float) * d.D, dx, sizeof(float) * d.N * d.D, sizeof(float) * d.D, d.B,
                              hipMemcpyDeviceToDevice, st));
   if (grads[P_POS]) TRY(colsum(dx, (long long)d.N * d.D, grads[P_POS], part, d.B, d.N * d.D, 0, st));
-  if (!grads[P_PW] && !grads[P_PB]) return DGVIT_OK;
+  const bool patch_grads = grads[P_PW] || grads[P_PB];
+  if (!patch_grads && !dimg) return DGVIT_OK;
   HIP_TRY(hipMemcpy2DAsync(dx2, sizeof(float) * d.P * d.D, dx + d.D, sizeof(float) * d.N * d.D, sizeof(float) * d.P * d.D, d.B,
                            hipMemcpyDeviceToDevice, st));
-  float* patches32 = (float*)(sc + s.patches32);
-  TRY(patchify(img, patches32, d.B, cfg->image_h, cfg->image_w, cfg->patch_h, cfg->patch_w, st));
-  return ::wgrad(dx2, d.D, patches32, d.pd, grads[P_PW], grads[P_PB], d.D, d.pd, d.B * d.P, slabs, s.slab_floats, st);
+  if (patch_grads) {
+    float* patches32 = (float*)(sc + s.patches32);
+    TRY(patchify(img, patches32, d.B, cfg->image_h, cfg->image_w, cfg->patch_h, cfg->patch_w, st));
+    TRY(::wgrad(dx2, d.D, patches32, d.pd, grads[P_PW], grads[P_PB], d.D, d.pd, d.B * d.P, slabs, s.slab_floats, st));
+  }
+  // the frame gradient in fp32 from the fp32 gradient and the fp32 master patch weight (the fp32 path's GEMM and epilogue)
+  if (dimg) TRY(image_grad(cfg, d, dx2, params[P_PW], dimg, st));
+  return DGVIT_OK;
 }
 
 // operator-level exports of the bf16 kernels (parity tests, benches)

@@ -288,6 +288,14 @@ __device__ __forceinline__ void stamp(const GemmParams& p, int slot, int tid) {
 #define DIAG_STAMPS(p) false
 #endif
 
+// EPI_UNPATCH: image offset of element (m, k) of the (B * P, ph * pw) patch matrix -- the address the patch gather (Fetch::plan_gather) reads
+// it from, so the store is that loader's inverse.  Patches do not overlap: every pixel is written exactly once, no atomics.
+__device__ __forceinline__ long long unpatch_off(const GemmParams& p, int m, int k) {
+  const int b = m / p.g_P, pi = m - b * p.g_P, py = pi / p.g_gw, px = pi - py * p.g_gw;
+  const int i = k / p.g_pw, j = k - i * p.g_pw;
+  return (long long)b * p.g_hw + (long long)(py * p.g_ph + i) * p.g_wi + px * p.g_pw + j;
+}
+
 template <class T, int LAYOUT, int VEC, int EPI, bool GATHER = false>
 __global__ void __launch_bounds__(T::NT, T::MINB) gemm_f32_kernel(const GemmParams p) {
   constexpr int BM = T::BM, BN = T::BN, BK = T::BK, NT = T::NT;
@@ -379,7 +387,7 @@ __global__ void __launch_bounds__(T::NT, T::MINB) gemm_f32_kernel(const GemmPara
   // The bias row piece is fetched BEFORE the main loop (4 registers): at the epilogue it would be a dependent round trip of
   // several thousand cycles under load, paid by every tile.
   // which epilogue (uniform over the launch except for split tiles): see "direct epilogue" below
-  constexpr bool DIRECT_OK = LAYOUT != GEMM_TN && VEC == 4 && !GATHER && EPI != EPI_SPLITK && (BKC || TN <= 2);
+  constexpr bool DIRECT_OK = LAYOUT != GEMM_TN && VEC == 4 && !GATHER && EPI != EPI_SPLITK && EPI != EPI_UNPATCH && (BKC || TN <= 2);
   const bool direct = DIRECT_OK && nz == 1 && evec && p.c_rgrp == 0 && p.res_mod == 0 && (!TWO_OUT || p.ldc2 == p.ldc) && !DIAG_BIT(p, 8) &&
                       !(LN_OK && p.ln_y);   // (the fused LayerNorm reduces over the 16 lanes that hold a row of the LDS image)
   int dcol[TN];     // direct epilogue: this lane's column(s) inside the tile
@@ -682,6 +690,12 @@ __global__ void __launch_bounds__(T::NT, T::MINB) gemm_f32_kernel(const GemmPara
   };
   // one output row piece (row m, columns n .. n+3, v = the k-complete sums): fused epilogue arithmetic and the global stores
   auto finish = [&](int m, float (&v)[4]) {
+    if constexpr (EPI == EPI_UNPATCH) {   // (scalar path: a piece may cross a patch row when pw % 4 != 0)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n + e < p.N) Cz[unpatch_off(p, m, n + e)] = v[e];
+      return;
+    }
     float w2[4];
     long long crow = m;
     if (EPI == EPI_STORE && p.c_rgrp > 0) crow = (long long)m + m / p.c_rgrp + 1;
@@ -858,7 +872,10 @@ __global__ void __launch_bounds__(T::NT, T::MINB) gemm_f32_kernel(const GemmPara
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = ACT_GRAD ? v[e] * a4[e] : (a4[e] > 0.f ? v[e] : 0.f);
         }
-        if (m < p.M && nvalid) {
+        if (EPI == EPI_UNPATCH && m < p.M && nvalid) {
+          // pw % 4 == 0 (gemm_f32 sets evec only then): the four columns n .. n+3 are adjacent pixels of one image row
+          *reinterpret_cast<float4*>(Cz + unpatch_off(p, m, n)) = make_float4(v[0], v[1], v[2], v[3]);
+        } else if (EPI != EPI_UNPATCH && m < p.M && nvalid) {
           long long crow = m;
           if (EPI == EPI_STORE && p.c_rgrp > 0) crow = (long long)m + m / p.c_rgrp + 1;
           int ncol = n;
@@ -1327,7 +1344,8 @@ int launch_persistent(const GemmParams& p, hipStream_t stream, bool* taken) {
   constexpr int NK = 16;   // k-tiles per output tile the pipelined kernel is built for: K = 256 at BK = 16, K = 512 at BK = 32
   // built for the two tiles the automatic choice uses in these forms (every instantiation is a fully unrolled 16-iteration loop)
   constexpr bool TILE_OK = (T::BM == 64 && T::BN == 128 && T::BK == 16) || (T::BM == 64 && T::BN == 64 && T::BK == 32);
-  if constexpr ((LAYOUT == GEMM_NT || LAYOUT == GEMM_NN) && EPI != EPI_SPLITK && TILE_OK) {
+  // (the pipelined kernel knows the row-major epilogues only: EPI_UNPATCH never takes it)
+  if constexpr ((LAYOUT == GEMM_NT || LAYOUT == GEMM_NN) && EPI != EPI_SPLITK && EPI != EPI_UNPATCH && TILE_OK) {
     constexpr int BM = T::BM, BN = T::BN, BK = T::BK;
     if (p.K != NK * BK) return DGVIT_OK;
     constexpr size_t lds = T::LDS_BYTES;
@@ -1408,7 +1426,7 @@ int launch(const GemmParams& p0, int nsplit, hipStream_t stream) {
     }
   }
 #ifdef DGVIT_DIAG
-  if constexpr (VEC == 4 && !GATHER && EPI != EPI_SPLITK && LAYOUT != GEMM_TN) {
+  if constexpr (VEC == 4 && !GATHER && EPI != EPI_SPLITK && EPI != EPI_UNPATCH && LAYOUT != GEMM_TN) {
     // whole tiles only, vector epilogue, plain row mapping: the persistent kernel (tile loop in the workgroup, next tile's fetch
     // under the epilogue) when a resident slot gets several tiles
     if (g_gemm_persist && (p.nsplit == 1 || g_gemm_persist == 2) && nsplit == 1 && p.evec && p.c_rgrp == 0 && p.res_mod == 0 &&
@@ -1451,17 +1469,21 @@ int pick_tile(const GemmParams& p, int nsplit, bool vec4, int tile_hint, hipStre
   if constexpr (LAYOUT == GEMM_NT && (EPI == EPI_STORE || EPI == EPI_RELU)) {
     if (p.g_img) return launch<TileCfg<64, 64, 32>, LAYOUT, 4, EPI, true>(p, nsplit, stream);   // patch / window gather in the A loader
   }
-  if (!vec4) return launch<TileCfg<64, 64, 32>, LAYOUT, 1, EPI>(p, nsplit, stream);
-  int choice = tile_hint;
-  if (choice == 64) choice = 64064032;
-  if (choice == 128) choice = 128128032;
-  if (choice == 0) choice = auto_tile(LAYOUT, p.M, p.N);
-  if (!p.evec) choice = 64064032;   // the one tile that carries the element-wise epilogue (odd N / ldc, unaligned outputs)
+  if constexpr (EPI == EPI_UNPATCH) {   // the one tile that carries both the float4 and the element-wise image stores
+    return vec4 ? launch<TileCfg<64, 64, 32>, LAYOUT, 4, EPI>(p, nsplit, stream) : launch<TileCfg<64, 64, 32>, LAYOUT, 1, EPI>(p, nsplit, stream);
+  } else {
+    if (!vec4) return launch<TileCfg<64, 64, 32>, LAYOUT, 1, EPI>(p, nsplit, stream);
+    int choice = tile_hint;
+    if (choice == 64) choice = 64064032;
+    if (choice == 128) choice = 128128032;
+    if (choice == 0) choice = auto_tile(LAYOUT, p.M, p.N);
+    if (!p.evec) choice = 64064032;   // the one tile that carries the element-wise epilogue (odd N / ldc, unaligned outputs)
 #define X(BM_, BN_, BK_) \
-  if (choice == BM_ * 1000000 + BN_ * 1000 + BK_) return launch<TileCfg<BM_, BN_, BK_>, LAYOUT, 4, EPI>(p, nsplit, stream);
-  DGVIT_TILES(X)
+    if (choice == BM_ * 1000000 + BN_ * 1000 + BK_) return launch<TileCfg<BM_, BN_, BK_>, LAYOUT, 4, EPI>(p, nsplit, stream);
+    DGVIT_TILES(X)
 #undef X
-  return dgvit_set_error(DGVIT_ERR_ARG, "gemm: unknown tile %d", choice);
+    return dgvit_set_error(DGVIT_ERR_ARG, "gemm: unknown tile %d", choice);
+  }
 }
 
 
@@ -1511,6 +1533,13 @@ int gemm_f32(int layout, int epi, const GemmParams& p, int nsplit, hipStream_t s
   q.evec = p.N % 4 == 0 && p.ldc % 4 == 0 && al16(p.C) && (!p.res || (p.ldr % 4 == 0 && al16(p.res))) &&
            (!p.C2 || (p.ldc2 % 4 == 0 && al16(p.C2))) && (!p.aux || (p.ldaux % 4 == 0 && al16(p.aux))) &&
            (epi != EPI_SPLITK || p.slab_stride % 4 == 0);
+  if (epi == EPI_UNPATCH) {
+    DGVIT_CHECK_ARG(layout == GEMM_NN && !p.g_img && !p.bias && !p.res && !p.counters && p.g_P > 0 && p.g_gw > 0 && p.g_pw > 0 && p.g_ph > 0 &&
+                        p.N == p.g_ph * p.g_pw && p.M % p.g_P == 0 && p.g_P % p.g_gw == 0 && p.g_wi == p.g_gw * p.g_pw &&
+                        (long long)p.g_hw == (long long)(p.g_P / p.g_gw) * p.g_ph * p.g_wi,
+                    "gemm: the unpatch epilogue needs the NN form, no bias / residual / split and a consistent patch geometry");
+    q.evec = p.g_pw % 4 == 0 && al16(p.C);   // float4 stores stay inside one patch row (image width = gw * pw: every row start aligned)
+  }
   const int th = g_gemm_tile_hint;
 #define CASE(L, E) \
   if (layout == L && epi == E) return pick_tile<L, E>(q, nsplit, vec4, th, stream);
@@ -1523,6 +1552,7 @@ int gemm_f32(int layout, int epi, const GemmParams& p, int nsplit, hipStream_t s
   CASE(GEMM_NN, EPI_DGELU)
   CASE(GEMM_NN, EPI_DMUL)
   CASE(GEMM_NN, EPI_DRELU)
+  CASE(GEMM_NN, EPI_UNPATCH)
   CASE(GEMM_TN, EPI_SPLITK)
 #undef CASE
   return dgvit_set_error(DGVIT_ERR_ARG, "gemm: unsupported layout/epilogue %d/%d", layout, epi);

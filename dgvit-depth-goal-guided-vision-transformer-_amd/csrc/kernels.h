@@ -35,6 +35,8 @@ int adam_step(float*, const float*, float*, float*, long long, float, float, flo
 int soft_update(float*, const float*, long long, float, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
+// the single-channel frame gradient from conv1's column gradient (rows of KP floats, 25 real taps): no ReLU mask
+int col2im_frame(const float*, float*, int, int, int, int, int, int, hipStream_t);
 int weight_pack(const float*, float*, int, int, int, int, hipStream_t);
 int avgpool(const float*, float*, int, int, int, hipStream_t);
 int avgpool_bwd_relu(const float*, const float*, float*, int, int, int, hipStream_t);

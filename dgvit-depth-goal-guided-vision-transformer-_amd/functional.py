@@ -136,6 +136,19 @@ def _take_workspace(ctx, what):
     return ws
 
 
+def _image_grad(ctx, cfg, B, dev):
+    """The (B, H, W) frame gradient buffer when autograd asks for it (img.requires_grad), else None: the C ABI then skips it"""
+    if not ctx.needs_input_grad[0]:
+        return None
+    return torch.empty(B, cfg.image_h, cfg.image_w, dtype=torch.float32, device=dev)
+
+
+def _wants_hook(ctx, grads):
+    """the gradient-ready hook runs only when there are parameter gradients to hand it (a frozen encoder asked for its frame gradient
+    has none)"""
+    return ctx.grad_hook is not None and any(g is not None for g in grads)
+
+
 class _GoTEncoder(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, goal, cfg_tuple, keep, seed, need_grad, grad_hook, *params):
@@ -185,19 +198,20 @@ class _GoTEncoder(torch.autograd.Function):
         # parallel.GradSync all-reduces the buffer in place (one large RCCL call instead of 70 small tensors)
         grads = _flat_grads(params, ctx.needs_input_grad[_N_NONPARAM_INPUTS:], dev)
         dgoal = torch.empty(B, cfg.dim, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        dimg = _image_grad(ctx, cfg, B, dev)
         nsc = lib.dgvit_got_backward_scratch_floats(ctypes.byref(cfg), B)
         scratch = torch.empty(nsc, dtype=torch.float32, device=dev)
-        evs = _layer_events(dev, cfg.depth) if ctx.grad_hook is not None else None
+        evs = _layer_events(dev, cfg.depth) if _wants_hook(ctx, grads) else None
         events, keep_alive = _grad_events(cfg.depth, evs) if evs else (None, None)
         with torch.cuda.device(dev):
-            rc = lib.dgvit_got_backward_v2_ev(ctypes.byref(cfg), _table(params), _grad_table(grads), _ptr(dfeat), _ptr(dgoal), _ptr(ws),
-                                              ws.numel(), _ptr(scratch), nsc, B, ctx.keep, ctx.lkeep, ctx.seed, _ptr(ctx.seed_dev), _stream(),
-                                              ctypes.byref(events) if events is not None else None)
+            rc = lib.dgvit_got_backward_v3_ev(ctypes.byref(cfg), _table(params), _grad_table(grads), _ptr(dfeat), _ptr(dgoal), _ptr(dimg),
+                                              _ptr(ws), ws.numel(), _ptr(scratch), nsc, B, ctx.keep, ctx.lkeep, ctx.seed, _ptr(ctx.seed_dev),
+                                              _stream(), ctypes.byref(events) if events is not None else None)
         _lib.check(rc, "dgvit_got_backward")
         ctx.ws = None
         if evs:     # the kernels are queued, not finished: the hook orders its own stream behind the events (parallel.GradSync)
             _call_grad_hook(ctx.grad_hook, grads, cfg.depth, evs)
-        return (None, dgoal, None, None, None, None, None, *grads)
+        return (dimg, dgoal, None, None, None, None, None, *grads)
 
 
 def got_encoder(img, goal, cfg_tuple, params, dropout_keep=1.0, dropout_seed=0, grad_hook=None, layer_dropout_keep=1.0):
@@ -210,7 +224,7 @@ def got_encoder(img, goal, cfg_tuple, params, dropout_keep=1.0, dropout_seed=0, 
     (include/dgvit_hip.h: dgvit_grad_events) -- parallel.GradSync(overlap=True) starts the blocks' all-reduces there."""
     if img.shape[0] == 0:
         return _empty_batch((0, int(cfg_tuple[4])), [img, goal, *params])
-    need_grad = torch.is_grad_enabled() and (goal.requires_grad or any(p is not None and p.requires_grad for p in params))
+    need_grad = torch.is_grad_enabled() and (img.requires_grad or goal.requires_grad or any(p is not None and p.requires_grad for p in params))
     lkeep = float(layer_dropout_keep)
     if not 0.0 < lkeep <= 1.0:
         raise DgvitError(f"layer_dropout_keep={lkeep} must be in (0, 1]")
@@ -252,22 +266,23 @@ class _CnnStack(torch.autograd.Function):
         img, *params = ctx.saved_tensors
         dfeat = _dev(dfeat, "dfeat")
         B, H, W = img.shape
-        grads = [torch.empty_like(p) for p in params]
+        grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[2:])]   # None: frozen, skipped
+        dimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
         nsc = lib.dgvit_cnn_backward_scratch_floats(B, H, W)
         scratch = torch.empty(nsc, dtype=torch.float32, device=img.device)
         with torch.cuda.device(img.device):
-            rc = lib.dgvit_cnn_backward(_ptr(img), _table(params), _table(grads), _ptr(dfeat), _ptr(ws), ws.numel(),
-                                        _ptr(scratch), nsc, B, H, W, _stream())
+            rc = lib.dgvit_cnn_backward_v2(_ptr(img), _table(params), _table(grads), _ptr(dfeat), _ptr(dimg), _ptr(ws), ws.numel(),
+                                           _ptr(scratch), nsc, B, H, W, _stream())
         _lib.check(rc, "dgvit_cnn_backward")
         ctx.ws = None
-        return (None, None, *grads)
+        return (dimg, None, *grads)
 
 
 def cnn_features(img, conv_params):
     """(B, H, W) frames -> (B, 256) pooled features; conv_params = [w1, b1, w2, b2, w3, b3] (reference layouts)."""
     if img.shape[0] == 0:
         return _empty_batch((0, 256), [img, *conv_params])
-    need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in conv_params)
+    need_grad = torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in conv_params))
     return _CnnStack.apply(img, need_grad, *conv_params)
 
 
@@ -827,19 +842,20 @@ class _GoTEncoderBf16(torch.autograd.Function):
         B, dev = ctx.batch, dfeat.device
         grads = _flat_grads(params, ctx.needs_input_grad[_N_NONPARAM_INPUTS + 1:], dev)   # one flat buffer (see _GoTEncoder.backward)
         dgoal = torch.empty(B, cfg.dim, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        dimg = _image_grad(ctx, cfg, B, dev)
         nsc = lib.dgvit_got_bf16_backward_scratch_bytes(ctypes.byref(cfg), B)
         scratch = torch.empty(nsc, dtype=torch.uint8, device=dev)
-        evs = _layer_events(dev, cfg.depth) if ctx.grad_hook is not None else None
+        evs = _layer_events(dev, cfg.depth) if _wants_hook(ctx, grads) else None
         events, keep_alive = _grad_events(cfg.depth, evs) if evs else (None, None)
         with torch.cuda.device(dev):
-            rc = lib.dgvit_got_backward_bf16_ev(ctypes.byref(cfg), _table(params), _ptr(ctx.wpack), _grad_table(grads), _ptr(dfeat), _ptr(dgoal),
-                                                _ptr(ctx.img), _ptr(ws), ws.numel(), _ptr(scratch), nsc, B, ctx.keep, ctx.seed,
-                                                _ptr(ctx.seed_dev), _stream(), ctypes.byref(events) if events is not None else None)
+            rc = lib.dgvit_got_backward_bf16_v2_ev(ctypes.byref(cfg), _table(params), _ptr(ctx.wpack), _grad_table(grads), _ptr(dfeat),
+                                                   _ptr(dgoal), _ptr(dimg), _ptr(ctx.img), _ptr(ws), ws.numel(), _ptr(scratch), nsc, B, ctx.keep,
+                                                   ctx.seed, _ptr(ctx.seed_dev), _stream(), ctypes.byref(events) if events is not None else None)
         _lib.check(rc, "dgvit_got_backward_bf16")
         ctx.ws = ctx.wpack = ctx.img = None
         if evs:
             _call_grad_hook(ctx.grad_hook, grads, cfg.depth, evs)
-        return (None, dgoal, None, None, None, None, None, None, *grads)
+        return (dimg, dgoal, None, None, None, None, None, None, *grads)
 
 
 def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout_keep=1.0, dropout_seed=0, grad_hook=None):
@@ -849,5 +865,5 @@ def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout
                                   "runs on the fp32 path only)")
     if img.shape[0] == 0:
         return _empty_batch((0, int(cfg_tuple[4])), [img, goal, *params])
-    need_grad = torch.is_grad_enabled() and (goal.requires_grad or any(p.requires_grad for p in params))
+    need_grad = torch.is_grad_enabled() and (img.requires_grad or goal.requires_grad or any(p.requires_grad for p in params))
     return _GoTEncoderBf16.apply(img, goal, tuple(cfg_tuple), dropout_keep, dropout_seed, need_grad, grad_hook, weights, *params)

@@ -171,6 +171,23 @@ int dgvit_got_backward_v2_ev(const dgvit_config* cfg, const float* const* params
                              unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream,
                              const dgvit_grad_events* events);
 
+/* Gradient with respect to the depth frame: dgvit_got_backward_v3 / dgvit_got_backward_v3_ev are dgvit_got_backward_v2 / _v2_ev with
+ * one more argument, dimg (B, image_h, image_w) floats, written (not accumulated); NULL = not wanted (the _v2 entry points are these
+ * with NULL).  dimg = unpatchify(dx0[patch rows] . W_pe), dx0 the gradient of the assembled tokens, so it INCLUDES the emb-dropout
+ * mask (the same mask and 1/keep as dgvit_got_forward's); the transformer-internal masks act on it through dx0 like on every other
+ * gradient.  It does not need the patch weight's or bias's gradient: with grads[1] == grads[2] == NULL (a frozen model; saliency maps)
+ * only dimg and whatever else grads[] asks for are formed.  Workspace and scratch sizes are those of the _v2 calls; NULL dimg leaves
+ * the launches and every other output exactly as _v2 has them. */
+int dgvit_got_backward_v3(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                          float* dgoal, float* dimg, const float* workspace, long long workspace_floats, float* scratch,
+                          long long scratch_floats, int batch, float dropout_keep, float layer_dropout_keep,
+                          unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_backward_v3_ev(const dgvit_config* cfg, const float* const* params, float* const* grads, const float* dfeat,
+                             float* dgoal, float* dimg, const float* workspace, long long workspace_floats, float* scratch,
+                             long long scratch_floats, int batch, float dropout_keep, float layer_dropout_keep,
+                             unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream,
+                             const dgvit_grad_events* events);
+
 /* ----------------------------------------------------------------------------------------------
  * Head Linears (got_sac_network.py:111,115-121,226,230-234,429,433-435):  y = act(x W^T + b)
  *   x (M, K), w (N, K), b (N) or NULL, y (M, N); act: 0 = identity, 1 = ReLU.
@@ -285,6 +302,12 @@ int dgvit_cnn_forward(const float* img, const float* const* params, float* feat,
 int dgvit_cnn_backward(const float* img, const float* const* params, float* const* grads, const float* dfeat,
                        const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H, int W,
                        void* stream);
+/* ... and the gradient with respect to the frame: dimg (B, H, W) floats, written, or NULL = not wanted (dgvit_cnn_backward is this with
+ * NULL and every grads[i] required).  A NULL grads[i] marks a frozen parameter: its weight-gradient work is skipped, so a frozen
+ * network with dimg set forms only the frame gradient.  Same scratch as dgvit_cnn_backward. */
+int dgvit_cnn_backward_v2(const float* img, const float* const* params, float* const* grads, const float* dfeat, float* dimg,
+                          const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H, int W,
+                          void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * the step BEFORE the path.  The reference samples numpy batches from cpprb and copies
@@ -362,6 +385,17 @@ int dgvit_got_backward_bf16_ev(const dgvit_config* cfg, const float* const* para
                                const float* dfeat, float* dgoal, const float* img, const void* workspace, long long workspace_bytes,
                                void* scratch, long long scratch_bytes, int batch, float dropout_keep, unsigned long long dropout_seed,
                                const unsigned long long* dropout_seed_dev, void* stream, const dgvit_grad_events* events);
+/* ... with the frame gradient: dimg (B, image_h, image_w) fp32, NULL = not wanted; formed in fp32 from the fp32 token-assembly gradient
+ * and the fp32 master patch weight, emb-dropout mask included (as dgvit_got_backward_v3).  Same workspace and scratch sizes. */
+int dgvit_got_backward_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, float* const* grads,
+                               const float* dfeat, float* dgoal, float* dimg, const float* img, const void* workspace,
+                               long long workspace_bytes, void* scratch, long long scratch_bytes, int batch, float dropout_keep,
+                               unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_backward_bf16_v2_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, float* const* grads,
+                                  const float* dfeat, float* dgoal, float* dimg, const float* img, const void* workspace,
+                                  long long workspace_bytes, void* scratch, long long scratch_bytes, int batch, float dropout_keep,
+                                  unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev, void* stream,
+                                  const dgvit_grad_events* events);
 /* operator-level entry points of the bf16 kernels (parity tests, benches) */
 /* dW (Mo, Ko) fp32 = dY^T X and db (Mo, may be NULL) = column sums of dY, for dY (T, Mo) and X (T, Ko) bf16, token-major
  * (Mo, Ko % 8 == 0): the TN layout of the ring GEMM (transposed LDS reads), split over tokens into fp32 slabs that are summed in
