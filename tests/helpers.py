@@ -113,3 +113,42 @@ def check_grad_digest(fx, tag, named_grads, rtol, atol, strip=""):
         n_checked += 1
     assert n_checked > 0
     return n_checked
+
+
+# ------------------------------------------------------------------------------------------------ bf16 GEMM checks on sampled rows
+# The batch bench.py's c5_bf16 times (checked against bench.py by tests/test_c5_bench_batch_host.py).
+C5_BENCH_BATCH = 440
+
+# Element bounds of the bf16 GEMM epilogues, |got - ref| <= rel * |ref| + abs, for the operand scaling of tests/test_gpu_bf16.py: A ~ N(0, 1),
+# B ~ N(0, 1) / sqrt(K) (unit-variance outputs), fp32 bias ~ N(0, 1).  A bf16 output carries one rounding (half an ulp: at most 2^-8 of
+# |ref|, reached just above a power of two) plus fp32 accumulation error, which the absolute term covers; fp32 outputs carry accumulation
+# error only, which grows like sqrt(K).  These are the bounds tests/test_gpu_bf16.py uses for the same epilogues.
+def bf16_epilogue_bound(kind, ref, K):
+    if kind == "bf16":            # epilogue 0, and the pre-activation copy of epilogue 5
+        return 2 ** -8 * ref.abs() + 1e-5
+    if kind == "gelu":            # epilogues 1 and 5 (sigmoid form of GELU: within 2.6e-5 of the erf form)
+        return 2 ** -8 * ref.abs() + 5e-5
+    if kind == "dgelu":           # epilogue 3
+        return 2 ** -8 * ref.abs() + 3e-5
+    if kind == "f32":             # epilogue 4
+        return torch.full_like(ref, 2e-5 * K ** 0.5)
+    if kind == "f32_res":         # epilogue 2 with bias and residual, for UNSCALED B ~ N(0, 1) (outputs ~ sqrt(K)), as in test_gpu_bf16.py
+        return torch.full_like(ref, 1e-4 * K ** 0.5)
+    raise ValueError(kind)
+
+
+def sampled_rows(M, extra=300, seed=0, more=()):
+    """Rows of an M-row GEMM output to check against a CPU reference: every row of the first and of the last (ragged) 256-row panel,
+    the rows in ``more``, and a seeded random sample of ``extra`` others.  Sorted int64 tensor."""
+    rows = set(range(min(256, M))) | set(range((M - 1) // 256 * 256, M)) | {r for r in more if 0 <= r < M}
+    rng = np.random.RandomState(seed)
+    rows |= set(int(r) for r in rng.randint(0, M, size=extra))
+    return torch.tensor(sorted(rows), dtype=torch.int64)
+
+
+def gemm_ref_rows(a, b64, rows, bias=None):
+    """fp64 CPU reference of rows ``rows`` of A B^T (+ bias): A is the bf16 device operand (M, >= K), b64 the CPU float64 copy of B."""
+    K = b64.shape[1]
+    ar = a[rows.to(a.device), :K].double().cpu()
+    h = ar @ b64.T
+    return h if bias is None else h + bias.double().cpu()
