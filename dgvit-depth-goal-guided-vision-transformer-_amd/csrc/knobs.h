@@ -7,11 +7,17 @@
 // is not in the binary.  The two schedule options a caller may legitimately want per call travel in dgvit_config.flags.
 //
 // Diagnostic build (-DDGVIT_DIAG -> libdgvit_hip_diag.so, for tools/ and the A/B equality tests): the same names are plain
-// process-global variables, set through the entry points of include/dgvit_hip_diag.h.  Not thread-safe by design.
+// process-global variables, set through the entry points of include/dgvit_hip_diag.h.  Not thread-safe by design.  This list is the
+// only statement of the defaults: diag_api.hip defines the variables from it (DGVIT_KNOB_DEFINE), together with a constant
+// <name>_default that its setters fall back to.
 #pragma once
 
 #ifdef DGVIT_DIAG
+#ifdef DGVIT_KNOB_DEFINE
+#define DGVIT_KNOB(type, name, def) type name = def; constexpr type name##_default = def;
+#else
 #define DGVIT_KNOB(type, name, def) extern type name;
+#endif
 #define DGVIT_DIAG_ONLY(...) __VA_ARGS__
 #define KNOB_IF(k) if (k)
 #else
