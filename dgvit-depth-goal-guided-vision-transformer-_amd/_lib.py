@@ -24,6 +24,8 @@ class dgvit_config(Structure):
 FLAG_DENSE_LAST_BLOCK = 1    # include/dgvit_hip.h: DGVIT_FLAG_*
 FLAG_WGRAD_OVERLAP = 2
 FLAG_LONG_SEQUENCE = 4      # fp32 encoder: K / V-tiled attention for N > 288 tokens
+MAPS_GOAL = 0               # include/dgvit_hip.h: DGVIT_MAPS_* (the rows of an attention-maps call)
+MAPS_ALL = 1
 
 
 class dgvit_mlp_desc(Structure):
@@ -117,6 +119,11 @@ SIGNATURES = {
     "dgvit_gemm_bf16": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P]),
     "dgvit_layernorm_forward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dgvit_attention_forward_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    # attention maps (include/dgvit_hip.h: Attention maps)
+    "dgvit_got_forward_maps": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _I, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_forward_maps_bf16": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _P, _I, _P, _LL, _I, _F, _ULL, _P, _P]),
+    "dgvit_attention_probs": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_attention_probs_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dgvit_profile_start": (_I, [_I]),
     "dgvit_profile_stop": (_I, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_longlong)]),

@@ -93,6 +93,9 @@ int layernorm_bwd_bf16(const bf16_t* dy, const float* x, const float* mean, cons
 int colsum_bf16_blocks(int rows);
 int colsum_bf16(const bf16_t* src, long long ld, float* out, float* part, int rows, int cols, hipStream_t st);
 int transpose_cast_f32_bf16(const float* src, bf16_t* dst, int rows, int cols, hipStream_t st);
+// attention_maps.hip: the maps kernels on bf16 qkv (dh 64), layouts as attention_probs (kernels.h)
+int attention_probs_bf16(const bf16_t* qkv, const float* lse, float* probs, long long frame_stride, int B, int N, int H, int dh, int rows,
+                         hipStream_t st);
 int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st);
 
 int attention_bwd_bf16(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,

@@ -219,7 +219,11 @@ struct Fwd {
   unsigned long long seed;
   const unsigned long long* seed_dev;
   hipStream_t st;
+  float* maps = nullptr;   // attention maps (dgvit_got_forward_maps): (B, L, H, N) or (B, L, H, N, N); null in every other call
+  int maps_rows = DGVIT_MAPS_GOAL;
   LayerDrop site(int layer, int s) const { return LayerDrop{lkeep, drop_tag(layer, s), seed, seed_dev}; }
+  // the last block runs dense under the flag, and for maps of every query row (rows other than 0 do not exist in the token-0 block)
+  bool dense_last() const { return dense_last_block(cfg) || (maps && maps_rows == DGVIT_MAPS_ALL); }
 };
 
 // Inference: the patch rearrangement (GoalFormer.py:138) happens inside the GEMM's A-tile loader -- depth patches go from the
@@ -321,7 +325,7 @@ int gemm_layer(const Fwd& f, int i, float*& x) {
   // The output only reads token 0 of the last block (GoalFormer.py:167): there, K and V are needed for every
   // token but Q, the attention output, to_out and the whole feed-forward only for row b*N of each frame.
   // `tok` = rows processed, `rs` = row step (in token rows) of those rows inside the (T, .) buffers.
-  const bool last = !dense_last_block(f.cfg) && !d.pool_mean && i == d.L - 1;
+  const bool last = !f.dense_last() && !d.pool_mean && i == d.L - 1;
   const int tok = last ? d.B : T, rs = last ? d.N : 1;
   // x = attn(LN(x)) + x   (GoalFormer.py:103, 36-37, 71-82)
   // D <= 64 (the shipped model): a 64-wide GEMM tile holds whole rows of the residual stream, so each LayerNorm runs inside the
@@ -342,10 +346,16 @@ int gemm_layer(const Fwd& f, int i, float*& x) {
     TRY(gemm_f32(GEMM_NT, EPI_STORE, q, 1, st));
   }
   const LayerDrop dr_attn = f.site(i, DROP_ATTN);
+  float* lse = save || f.maps ? lb + w.lse : nullptr;   // (a maps call reads the row statistics back)
   if (d.tiled)
-    TRY(attention_fwd_tiled(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+    TRY(attention_fwd_tiled(lb + w.qkv, lb + w.ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
   else
-    TRY(attention_fwd(lb + w.qkv, lb + w.ao, save ? lb + w.lse : nullptr, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+    TRY(attention_fwd(lb + w.qkv, lb + w.ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
+  if (f.maps) {   // this layer's probabilities, before the next layer overwrites the shared qkv / lse of a no-grad pass
+    const long long per_head = f.maps_rows == DGVIT_MAPS_ALL ? (long long)d.N * d.N : d.N;
+    TRY(attention_probs(lb + w.qkv, lse, f.maps + (long long)i * d.H * per_head, (long long)d.L * d.H * per_head, d.B, d.N, d.H, d.dh,
+                        f.maps_rows, st));
+  }
   if (!d.proj) {
     // to_out = nn.Identity() (GoalFormer.py:56,66-69): the head's output IS the branch output (I == D): xmid = attn + x (:103)
     TRY(add_rows(lb + w.ao, (long long)rs * d.I, x, (long long)rs * d.D, lb + w.xmid, (long long)rs * d.D, tok, d.D, st));
@@ -407,10 +417,13 @@ extern "C" int dgvit_got_forward(const dgvit_config* cfg, const float* const* pa
   return dgvit_got_forward_v2(cfg, params, img, goal, feat, ws, ws_floats, batch, save, keep, 1.f, seed, seed_dev, stream);
 }
 
-extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
-                                    float* feat, float* ws, long long ws_floats, int batch, int save, float keep, float lkeep,
-                                    unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-  Fwd f = {cfg, {}, {}, params, ws, {}, save, lkeep, lkeep < 1.f, seed, seed_dev, (hipStream_t)stream};
+namespace {
+int got_forward(Fwd& f, const float* img, const float* goal, float* feat, long long ws_floats, int batch, float keep) {
+  const dgvit_config* cfg = f.cfg;
+  const float* const* params = f.params;
+  float* ws = f.ws;
+  const int save = f.save;
+  const float lkeep = f.lkeep;
   const Dims& d = f.d;
   TRY(make_dims(cfg, batch, f.d));
   DGVIT_CHECK_ARG(params && img && goal && feat && ws, "dgvit_got_forward: null pointer");
@@ -426,7 +439,7 @@ extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const*
   }
 
   // Which path runs: the two-launch small-batch blocks, (diagnostic build) the per-frame path, or the GEMM schedule
-  const bool use_blocks = !save && !f.ldrop && g_block_path && !g_small_path && w.bp_ncounters > 0;
+  const bool use_blocks = !save && !f.ldrop && !f.maps && g_block_path && !g_small_path && w.bp_ncounters > 0;
   const bool gather = patch_gather(cfg, d, img, params[P_PW], save);
   // ... with the loader gather no GEMM of this call splits, so nothing needs the counters before the first block's attention kernel,
   // which can then zero them itself AND assemble the token rows (goal row, emb-dropout): three launches fewer.  Built, parity-tested
@@ -437,12 +450,34 @@ extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const*
   TRY(token_assembly(f, img, goal, keep, gather, fused_first));
   float* x = ws + w.x0;
 #ifdef DGVIT_DIAG   // (measured slower than the schedule below, DESIGN 3.7: not in the product library)
-  if (!save && !f.ldrop && g_small_path && !d.pool_mean && d.proj && d.T <= g_small_path_max_rows && frame_path_supports(d.B, d.N, d.D, d.H, d.dh, d.M))
+  if (!save && !f.ldrop && !f.maps && g_small_path && !d.pool_mean && d.proj && d.T <= g_small_path_max_rows && frame_path_supports(d.B, d.N, d.D, d.H, d.dh, d.M))
     return frame_path_forward(x, params, d.L, ws + w.layer0, feat, d.B, d.N, d.D, d.H, d.dh, d.M, f.st);
 #endif
   if (use_blocks) return block_path_forward(f, goal, keep, fused_first, x, feat);
   for (int i = 0; i < d.L; ++i) TRY(gemm_layer(f, i, x));
   return pool_rmsnorm_fwd(d, x, ws + w.pooled, params[P_RMS], feat, f.st);
+}
+}  // namespace
+
+extern "C" int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
+                                    float* feat, float* ws, long long ws_floats, int batch, int save, float keep, float lkeep,
+                                    unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  Fwd f = {cfg, {}, {}, params, ws, {}, save, lkeep, lkeep < 1.f, seed, seed_dev, (hipStream_t)stream};
+  return got_forward(f, img, goal, feat, ws_floats, batch, keep);
+}
+
+// the no-grad forward with each layer's attention probabilities (include/dgvit_hip.h: Attention maps)
+extern "C" int dgvit_got_forward_maps(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal, float* feat,
+                                      float* maps, int rows, float* ws, long long ws_floats, int batch, float keep, float lkeep,
+                                      unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  Dims d;
+  TRY(make_dims(cfg, batch, d));
+  DGVIT_CHECK_ARG(maps, "dgvit_got_forward_maps: null maps pointer");
+  DGVIT_CHECK_ARG(rows == DGVIT_MAPS_GOAL || rows == DGVIT_MAPS_ALL, "dgvit_got_forward_maps: rows=%d must be DGVIT_MAPS_GOAL (0) or DGVIT_MAPS_ALL (1)", rows);
+  Fwd f = {cfg, {}, {}, params, ws, {}, 0, lkeep, lkeep < 1.f, seed, seed_dev, (hipStream_t)stream};
+  f.maps = maps;
+  f.maps_rows = rows;
+  return got_forward(f, img, goal, feat, ws_floats, batch, keep);
 }
 
 // ---------------------------------------------------------------------------------------------- backward

@@ -224,6 +224,8 @@ struct FwdB {
   unsigned char* ws;
   int save;
   hipStream_t st;
+  float* maps = nullptr;   // attention maps (dgvit_got_forward_maps_bf16); null in every other call
+  int maps_rows = DGVIT_MAPS_GOAL;
   float* f32(unsigned char* base, long long off) const { return save ? (float*)(base + off) : (float*)nullptr; }
 };
 
@@ -271,7 +273,8 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
   bf16_t* delta = (bf16_t*)(ws + w.delta);
   if (i == 0) TRY(layernorm_fwd_bf16(x, lp[L_LN1W], lp[L_LN1B], ln, f.f32(lb, w.mean1), f.f32(lb, w.rstd1), T, d.D, 1e-5f, 1, st));
   // inference: the last block only needs token 0 downstream of K/V (see gemm_layer in encoder.hip); training keeps it dense
-  const bool last = !dense_last_block(f.cfg) && !save && !d.pool_mean && i == d.L - 1;
+  const bool dense = dense_last_block(f.cfg) || (f.maps && f.maps_rows == DGVIT_MAPS_ALL);   // (maps of every row: see encoder.hip)
+  const bool last = !dense && !save && !d.pool_mean && i == d.L - 1;
   const int tok = last ? d.B : T, rs = last ? d.N : 1;
   float* xo = save ? (float*)(lb + w.xout) : (x == (float*)(ws + w.xa) ? (float*)(ws + w.xb) : (float*)(ws + w.xa));
   if (!last) {
@@ -283,7 +286,13 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
     GemmBf16Params q = gpb(ln, rs * d.D, lw + wp.qkv, d.D, qkv, rs * 3 * d.I, tok, d.I, d.D);
     TRY(gemm_bf16(BEPI_BF16, q, st));
   }
-  TRY(attention_fwd_bf16(qkv, ao, f.f32(lb, w.lse), d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+  float* lse = f.maps ? (float*)(lb + w.lse) : f.f32(lb, w.lse);   // (the no-grad layout has the slot too)
+  TRY(attention_fwd_bf16(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+  if (f.maps) {   // before the shared qkv / lse are overwritten by the next layer
+    const long long per_head = f.maps_rows == DGVIT_MAPS_ALL ? (long long)d.N * d.N : d.N;
+    TRY(attention_probs_bf16(qkv, lse, f.maps + (long long)i * d.H * per_head, (long long)d.L * d.H * per_head, d.B, d.N, d.H, d.dh,
+                             f.maps_rows, st));
+  }
   {
     GemmBf16Params p = gpb(ao, rs * d.I, lw + wp.out, d.I, delta, rs * d.D, tok, d.D, d.I);
     p.bias = lp[L_OUTB];
@@ -330,11 +339,13 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
 
 }  // namespace
 
-extern "C" int dgvit_got_forward_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
-                                      const float* img, const float* goal, float* feat, void* workspace, long long ws_bytes,
-                                      int batch, int save, float keep, unsigned long long seed,
-                                      const unsigned long long* seed_dev, void* stream) {
-  FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, save, (hipStream_t)stream};
+namespace {
+int got_forward_bf16(FwdB& f, const float* img, const float* goal, float* feat, const void* workspace, long long ws_bytes, int batch, float keep,
+                     unsigned long long seed, const unsigned long long* seed_dev) {
+  const dgvit_config* cfg = f.cfg;
+  const float* const* params = f.params;
+  const unsigned short* wpack = f.wpack;
+  const int save = f.save;
   const Dims& d = f.d;
   TRY(make_dims(cfg, batch, f.d));
   TRY(check_bf16_dims(d));
@@ -349,6 +360,30 @@ extern "C" int dgvit_got_forward_bf16(const dgvit_config* cfg, const float* cons
   TRY(token_assembly_bf16(f, img, goal, keep, seed, seed_dev, x));
   for (int i = 0; i < d.L; ++i) TRY(layer_fwd_bf16(f, i, x));
   return pool_rmsnorm_fwd(d, x, (float*)(f.ws + f.w.pooled), params[P_RMS], feat, f.st);
+}
+}  // namespace
+
+extern "C" int dgvit_got_forward_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                      const float* img, const float* goal, float* feat, void* workspace, long long ws_bytes,
+                                      int batch, int save, float keep, unsigned long long seed,
+                                      const unsigned long long* seed_dev, void* stream) {
+  FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, save, (hipStream_t)stream};
+  return got_forward_bf16(f, img, goal, feat, workspace, ws_bytes, batch, keep, seed, seed_dev);
+}
+
+// the no-grad bf16 forward with each layer's attention probabilities (include/dgvit_hip.h: Attention maps)
+extern "C" int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
+                                           const float* goal, float* feat, float* maps, int rows, void* workspace, long long ws_bytes, int batch,
+                                           float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  Dims d;
+  TRY(make_dims(cfg, batch, d));
+  TRY(check_bf16_dims(d));
+  DGVIT_CHECK_ARG(maps, "dgvit_got_forward_maps_bf16: null maps pointer");
+  DGVIT_CHECK_ARG(rows == DGVIT_MAPS_GOAL || rows == DGVIT_MAPS_ALL, "dgvit_got_forward_maps_bf16: rows=%d must be DGVIT_MAPS_GOAL (0) or DGVIT_MAPS_ALL (1)", rows);
+  FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, 0, (hipStream_t)stream};
+  f.maps = maps;
+  f.maps_rows = rows;
+  return got_forward_bf16(f, img, goal, feat, workspace, ws_bytes, batch, keep, seed, seed_dev);
 }
 
 // Gradient of dgvit_got_forward_bf16 (save_for_backward = 1).  Data-gradient GEMMs take the transposed weight copies of

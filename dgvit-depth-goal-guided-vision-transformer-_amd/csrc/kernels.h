@@ -22,6 +22,10 @@ int attention_fwd_tiled(const float*, float*, float*, int, int, int, int, int, h
 long long attention_bwd_tiled_scratch(int B, int N, int H);
 int attention_bwd_tiled(const float*, const float*, const float*, const float*, float*, float*, long long, int, int, int, int, int,
                         hipStream_t, const LayerDrop* drop = nullptr);
+// attention_maps.hip: P = exp2(q.k * scale * log2e - lse) of one layer from its qkv buffer and the forward's lse; rows DGVIT_MAPS_GOAL
+// (query 0: probs[b * frame_stride + h * N + k]) or DGVIT_MAPS_ALL (probs[b * frame_stride + (h * N + q) * N + k])
+int attention_probs(const float* qkv, const float* lse, float* probs, long long frame_stride, int B, int N, int H, int dh, int rows,
+                    hipStream_t st);
 int patchify(const float*, float*, int, int, int, int, int, hipStream_t);
 int add_rows(const float*, long long, const float*, long long, float*, long long, long long, int, hipStream_t);
 int goal_row(const float*, const float*, float*, int, int, int, hipStream_t);

@@ -149,21 +149,28 @@ def _wants_hook(ctx, grads):
     return ctx.grad_hook is not None and any(g is not None for g in grads)
 
 
+def _encoder_inputs(cfg, img, goal, params):
+    """(img, goal, params) on the device, contiguous, checked against the config (the forward's and the maps call's refusals)"""
+    img, goal = _dev(img, "img"), _dev(goal, "goal")
+    params = [None if p is None else _dev(p, f"param[{i}]") for i, p in enumerate(params)]   # (None: unused to_out slots, dgvit_hip.h)
+    nparam = _lib.NUM_GLOBAL_PARAMS + _lib.PARAMS_PER_LAYER * cfg.depth
+    if len(params) != nparam:
+        raise DgvitError(f"expected {nparam} parameter tensors, got {len(params)}")
+    if img.dim() != 3 or img.shape[1] != cfg.image_h or img.shape[2] != cfg.image_w:
+        raise DgvitError(f"img must be (B, {cfg.image_h}, {cfg.image_w}), got {tuple(img.shape)}")
+    B = img.shape[0]
+    if goal.shape != (B, cfg.dim):
+        raise DgvitError(f"goal must be ({B}, {cfg.dim}), got {tuple(goal.shape)}")
+    return img, goal, params
+
+
 class _GoTEncoder(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, goal, cfg_tuple, keep, seed, need_grad, grad_hook, *params):
         lib = _lib.load()
         cfg = dgvit_config(*cfg_tuple)
-        img, goal = _dev(img, "img"), _dev(goal, "goal")
-        params = [None if p is None else _dev(p, f"param[{i}]") for i, p in enumerate(params)]   # (None: unused to_out slots, dgvit_hip.h)
-        nparam = _lib.NUM_GLOBAL_PARAMS + _lib.PARAMS_PER_LAYER * cfg.depth
-        if len(params) != nparam:
-            raise DgvitError(f"expected {nparam} parameter tensors, got {len(params)}")
-        if img.dim() != 3 or img.shape[1] != cfg.image_h or img.shape[2] != cfg.image_w:
-            raise DgvitError(f"img must be (B, {cfg.image_h}, {cfg.image_w}), got {tuple(img.shape)}")
+        img, goal, params = _encoder_inputs(cfg, img, goal, params)
         B = img.shape[0]
-        if goal.shape != (B, cfg.dim):
-            raise DgvitError(f"goal must be ({B}, {cfg.dim}), got {tuple(goal.shape)}")
         nws = lib.dgvit_got_workspace_floats(ctypes.byref(cfg), B, int(need_grad))
         if nws < 0:
             _lib.check(-1, "dgvit_got_workspace_floats")
@@ -803,16 +810,8 @@ class _GoTEncoderBf16(torch.autograd.Function):
     def forward(ctx, img, goal, cfg_tuple, keep, seed, need_grad, grad_hook, weights, *params):
         lib = _lib.load()
         cfg = dgvit_config(*cfg_tuple)
-        img, goal = _dev(img, "img"), _dev(goal, "goal")
-        params = [_dev(p, f"param[{i}]") for i, p in enumerate(params)]
-        nparam = _lib.NUM_GLOBAL_PARAMS + _lib.PARAMS_PER_LAYER * cfg.depth
-        if len(params) != nparam:
-            raise DgvitError(f"expected {nparam} parameter tensors, got {len(params)}")
-        if img.dim() != 3 or img.shape[1] != cfg.image_h or img.shape[2] != cfg.image_w:
-            raise DgvitError(f"img must be (B, {cfg.image_h}, {cfg.image_w}), got {tuple(img.shape)}")
+        img, goal, params = _encoder_inputs(cfg, img, goal, params)
         B = img.shape[0]
-        if goal.shape != (B, cfg.dim):
-            raise DgvitError(f"goal must be ({B}, {cfg.dim}), got {tuple(goal.shape)}")
         wpack = weights.get(cfg, params, with_transposes=bool(need_grad))
         nws = lib.dgvit_got_bf16_workspace_bytes(ctypes.byref(cfg), B, int(need_grad))
         if nws < 0:
@@ -858,12 +857,121 @@ class _GoTEncoderBf16(torch.autograd.Function):
         return (dimg, dgoal, None, None, None, None, None, None, *grads)
 
 
-def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout_keep=1.0, dropout_seed=0, grad_hook=None):
-    """GoT.forward in the bf16 configuration (bf16 storage of GEMM operands, fp32 master parameters and gradients)."""
+def _refuse_no_projection_bf16(params):
     if any(p is None for p in params):
         raise NotImplementedError("the bf16 configuration needs an attention with an output projection (heads == 1 with dim_head == dim "
                                   "runs on the fp32 path only)")
+
+
+def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout_keep=1.0, dropout_seed=0, grad_hook=None):
+    """GoT.forward in the bf16 configuration (bf16 storage of GEMM operands, fp32 master parameters and gradients)."""
+    _refuse_no_projection_bf16(params)
     if img.shape[0] == 0:
         return _empty_batch((0, int(cfg_tuple[4])), [img, goal, *params])
     need_grad = torch.is_grad_enabled() and (img.requires_grad or goal.requires_grad or any(p.requires_grad for p in params))
     return _GoTEncoderBf16.apply(img, goal, tuple(cfg_tuple), dropout_keep, dropout_seed, need_grad, grad_hook, weights, *params)
+
+
+# ------------------------------------------------------------------------------------------------ attention maps
+def maps_rows(rows) -> int:
+    """'goal' (query 0, the goal token) or 'all' (every query row) -> DGVIT_MAPS_GOAL / DGVIT_MAPS_ALL"""
+    if isinstance(rows, str) and rows in ("goal", "all"):
+        return _lib.MAPS_GOAL if rows == "goal" else _lib.MAPS_ALL
+    raise ValueError(f"rows={rows!r} must be 'goal' or 'all'")
+
+
+def _maps_shape(cfg, B, rows):
+    N = (cfg.image_h // cfg.patch_h) * (cfg.image_w // cfg.patch_w) + 1
+    return (B, cfg.depth, cfg.heads, N) + ((N,) if rows == _lib.MAPS_ALL else ())
+
+
+def _empty_maps(cfg, rows, img, goal, params):
+    for t in (img, goal, *params):
+        if isinstance(t, torch.Tensor):
+            _dev(t, "input")          # (a device-only path, as the forward's empty batch)
+    return img.new_zeros(0, cfg.dim), img.new_zeros(_maps_shape(cfg, 0, rows))
+
+
+def _seed_args(seed):
+    """(host seed, device seed tensor or None) as the encoder forwards take them"""
+    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    return (0 if seed_dev is not None else int(seed)), seed_dev
+
+
+@torch.no_grad()
+def got_attention_maps(img, goal, cfg_tuple, params, rows="goal", dropout_keep=1.0, dropout_seed=0, layer_dropout_keep=1.0):
+    """(feat (B, D), maps) of the fp32 encoder without autograd (dgvit_got_forward_maps).  feat is got_encoder's result under no_grad for
+    the same keeps and seed; maps (fp32) is (B, L, H, N) for rows='goal' -- softmax(q k^T dh^-1/2)[query 0, key k] of head h in layer l,
+    taken before the attention-dropout site -- or (B, L, H, N, N) for rows='all'."""
+    r = maps_rows(rows)
+    cfg = dgvit_config(*cfg_tuple)
+    lkeep = float(layer_dropout_keep)
+    if not 0.0 < lkeep <= 1.0:
+        raise DgvitError(f"layer_dropout_keep={lkeep} must be in (0, 1]")
+    if img.shape[0] == 0:
+        return _empty_maps(cfg, r, img, goal, params)
+    lib = _lib.load()
+    img, goal, params = _encoder_inputs(cfg, img, goal, params)
+    B = img.shape[0]
+    nws = lib.dgvit_got_workspace_floats(ctypes.byref(cfg), B, 0)     # (the no-grad workspace: it has the lse slot the maps read)
+    if nws < 0:
+        _lib.check(-1, "dgvit_got_workspace_floats")
+    ws = torch.empty(nws, dtype=torch.float32, device=img.device)
+    feat = torch.empty(B, cfg.dim, dtype=torch.float32, device=img.device)
+    maps = torch.empty(_maps_shape(cfg, B, r), dtype=torch.float32, device=img.device)
+    seed_val, seed_dev = _seed_args(dropout_seed)
+    with torch.cuda.device(img.device):
+        rc = lib.dgvit_got_forward_maps(ctypes.byref(cfg), _table(params), _ptr(img), _ptr(goal), _ptr(feat), _ptr(maps), r, _ptr(ws), nws, B,
+                                        float(dropout_keep), lkeep, seed_val, _ptr(seed_dev), _stream())
+    _lib.check(rc, "dgvit_got_forward_maps")
+    return feat, maps
+
+
+@torch.no_grad()
+def got_attention_maps_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, rows="goal", dropout_keep=1.0, dropout_seed=0):
+    """got_attention_maps in the bf16 configuration (dgvit_got_forward_maps_bf16): the probabilities come from the bf16 q / k the
+    attention kernel reads, with fp32 scores, softmax and output; feat is got_encoder_bf16's result under no_grad."""
+    r = maps_rows(rows)
+    cfg = dgvit_config(*cfg_tuple)
+    _refuse_no_projection_bf16(params)
+    if img.shape[0] == 0:
+        return _empty_maps(cfg, r, img, goal, params)
+    lib = _lib.load()
+    img, goal, params = _encoder_inputs(cfg, img, goal, params)
+    B = img.shape[0]
+    wpack = weights.get(cfg, params, with_transposes=False)
+    nws = lib.dgvit_got_bf16_workspace_bytes(ctypes.byref(cfg), B, 0)
+    if nws < 0:
+        _lib.check(-1, "dgvit_got_bf16_workspace_bytes")
+    ws = torch.empty(nws, dtype=torch.uint8, device=img.device)
+    feat = torch.empty(B, cfg.dim, dtype=torch.float32, device=img.device)
+    maps = torch.empty(_maps_shape(cfg, B, r), dtype=torch.float32, device=img.device)
+    seed_val, seed_dev = _seed_args(dropout_seed)
+    with torch.cuda.device(img.device):
+        rc = lib.dgvit_got_forward_maps_bf16(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(maps), r,
+                                             _ptr(ws), nws, B, float(dropout_keep), seed_val, _ptr(seed_dev), _stream())
+    _lib.check(rc, "dgvit_got_forward_maps_bf16")
+    return feat, maps
+
+
+def op_attention_probs(qkv, lse, heads, dim_head, rows="goal"):
+    """probabilities of the attention core from qkv (B, N, 3*H*dh) and its forward's lse (B, H, N): (B, H, N) or (B, H, N, N)"""
+    lib = _lib.load()
+    r = maps_rows(rows)
+    qkv, lse = _dev(qkv, "qkv"), _dev(lse, "lse")
+    B, N, _ = qkv.shape
+    probs = torch.empty((B, heads, N) + ((N,) if r == _lib.MAPS_ALL else ()), dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.dgvit_attention_probs(_ptr(qkv), _ptr(lse), _ptr(probs), B, N, heads, dim_head, r, _stream()), "dgvit_attention_probs")
+    return probs
+
+
+def op_attention_probs_bf16(qkv, lse, heads, dim_head=64, rows="goal"):
+    """op_attention_probs on bf16 qkv, with the lse of op_attention_bf16(..., want_lse=True)"""
+    lib = _lib.load()
+    r = maps_rows(rows)
+    qkv, lse = _dev_bf16(qkv, "qkv"), _dev(lse, "lse")
+    B, N, _ = qkv.shape
+    probs = torch.empty((B, heads, N) + ((N,) if r == _lib.MAPS_ALL else ()), dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.dgvit_attention_probs_bf16(_ptr(qkv), _ptr(lse), _ptr(probs), B, N, heads, dim_head, r, _stream()),
+               "dgvit_attention_probs_bf16")
+    return probs

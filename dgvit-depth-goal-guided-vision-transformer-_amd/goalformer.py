@@ -214,7 +214,8 @@ class GoT(nn.Module):
         base + rank draw different masks, a rank's sequence repeats) and needs no device sync."""
         return int(torch.randint(0, 2 ** 62, (1,)).item())
 
-    def forward(self, img, goal):
+    def _dropout_args(self, img):
+        """(emb-dropout keep, seed, transformer keep) of one call in the module's mode"""
         keep, seed = 1.0, 0
         lkeep = 1.0 - self.layer_dropout() if self.training else 1.0
         self._check_dropout_dtype(self.compute_dtype)
@@ -226,7 +227,25 @@ class GoT(nn.Module):
                 seed = torch.empty(1, dtype=torch.int64, device=img.device).random_()
             else:
                 seed = self.draw_dropout_seed()
+        return keep, seed, lkeep
+
+    def forward(self, img, goal):
+        keep, seed, lkeep = self._dropout_args(img)
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:
             return F_.got_encoder_bf16(img, goal, self._cfg, params, self._bf16_weights, keep, seed, grad_hook=self._grad_hook)
         return F_.got_encoder(img, goal, self._cfg, params, keep, seed, grad_hook=self._grad_hook, layer_dropout_keep=lkeep)
+
+    def attention_maps(self, img, goal, rows="goal"):
+        """(features, maps) without autograd; both detached.  ``maps`` is fp32: rows='goal' gives (B, depth, heads, N) with entry
+        [b, l, h, k] = softmax(q k^T * dim_head^-1/2)[query 0, key k] of head h in layer l -- the tensor GoalFormer.py:77 forms, before
+        the attention dropout -- for the goal token, the one token the networks read; rows='all' gives (B, depth, heads, N, N), every
+        query row.  ``features`` equals ``forward`` under torch.no_grad() for the same inputs, mode and dropout draw (the seed is drawn
+        as ``forward`` draws it).  The call always runs the GEMM schedule (never the small-batch block path) and, for rows='all', the
+        dense last block.  In the bf16 configuration the probabilities come from the bf16 q / k the attention reads (fp32 softmax)."""
+        r = F_.maps_rows(rows)     # (ValueError before anything is drawn)
+        keep, seed, lkeep = self._dropout_args(img)
+        params = self.param_table()
+        if self.compute_dtype == torch.bfloat16:
+            return F_.got_attention_maps_bf16(img, goal, self._cfg, params, self._bf16_weights, rows, keep, seed)
+        return F_.got_attention_maps(img, goal, self._cfg, params, rows, keep, seed, layer_dropout_keep=lkeep)

@@ -78,6 +78,13 @@ def _action_affine(action_space):
             torch.FloatTensor((action_space.high + action_space.low) / 2.))
 
 
+def _encoder_maps(module, inp, rows):
+    istate, pstate = inp
+    with torch.no_grad():
+        goal = _lin(module.fc_embed, pstate)                    # no activation (:226, :429)
+    return module.trans.attention_maps(istate, goal, rows)
+
+
 def _encoder(dim, depth, heads, image_size, patch_size):
     return GoT(image_size=image_size, patch_size=patch_size, num_classes=2, dim=dim, depth=depth, heads=heads, mlp_dim=2048,
                channels=1)
@@ -109,6 +116,14 @@ class GoTQNetwork(nn.Module):
         feat = self.trans(istate, goal)
         (q1,), (q2,) = _head([feat.view(feat.size(0), -1), a], [(self.fc1, self.fc2, [self.fc3]), (self.fc11, self.fc21, [self.fc31])])
         return q1, q2
+
+    def attention_maps(self, inp, rows="goal"):
+        """(features, maps) of the encoder (GoT.attention_maps) for the goal embedding forward computes; ``inp`` is [istate, pstate] or
+        forward's [istate, pstate, a] (the action is not used)."""
+        istate, pstate = inp[0], inp[1]
+        with torch.no_grad():
+            goal = _lin(self.fc_embed, pstate, relu=True)
+        return self.trans.attention_maps(istate, goal, rows)
 
 
 class GoTPolicy(nn.Module):
@@ -153,6 +168,10 @@ class GoTPolicy(nn.Module):
         mean, log_std_raw = self._head_outputs(inp)
         return mean, torch.clamp(log_std_raw, min=LOG_SIG_MIN, max=LOG_SIG_MAX)
 
+    def attention_maps(self, inp, rows="goal"):
+        """(features, maps) of the encoder (GoT.attention_maps) for the goal embedding forward computes from [istate, pstate]"""
+        return _encoder_maps(self, inp, rows)
+
     def sample(self, inp):
         """(action, log_prob, tanh(mean)) of got_sac_network.py:238-251: clamp, exp, rsample, tanh and the tanh-corrected Gaussian
         log-density as ONE HIP launch behind the head (no Normal object: its argument check alone is a host sync per call)."""
@@ -186,6 +205,10 @@ class DeterministicGoTPolicy(nn.Module):
         feat = self.trans(istate, goal)
         ((mean,),) = _head([feat.view(feat.size(0), -1)], [(self.fc1, self.fc2, [self.mean_linear])])
         return torch.tanh(mean) * self.action_scale + self.action_bias
+
+    def attention_maps(self, inp, rows="goal"):
+        """(features, maps) of the encoder (GoT.attention_maps) for the goal embedding forward computes from [istate, pstate]"""
+        return _encoder_maps(self, inp, rows)
 
     def sample(self, inp):
         mean = self.forward(inp)

@@ -189,6 +189,32 @@ int dgvit_got_backward_v3_ev(const dgvit_config* cfg, const float* const* params
                              const dgvit_grad_events* events);
 
 /* ----------------------------------------------------------------------------------------------
+ * Attention maps (GoalFormer.py:77): the softmax probabilities of every layer and head, taken before the attention-dropout site
+ *   P = softmax(q k^T * dim_head^-1/2)      (fp32 scores, softmax and output; in the bf16 configuration from the bf16 q / k that the
+ *                                            attention kernel reads -- not the bf16-rounded P that feeds P V)
+ * rows = DGVIT_MAPS_GOAL: query 0 only (the goal token, the one row the networks use)   maps (B, L, H, N)      [b][l][h][k]
+ * rows = DGVIT_MAPS_ALL:  every query row                                                maps (B, L, H, N, N)   [b][l][h][q][k]
+ * dgvit_got_forward_maps[_bf16] is the no-grad forward (save_for_backward = 0) with the same arguments otherwise, plus `maps` and
+ * `rows`: feat is what dgvit_got_forward_v2 / dgvit_got_forward_bf16 return for the same inputs, keeps and seed.  The call always
+ * takes the GEMM schedule (never the small-batch block path: feat then agrees with the block path to the usual 2e-5); under
+ * DGVIT_MAPS_ALL it runs the last block dense (as DGVIT_FLAG_DENSE_LAST_BLOCK).  After each layer's attention a maps kernel recomputes
+ * P from that layer's qkv buffer and the base-2 log-sum-exp the attention forward writes into the workspace.  Workspace: the no-grad
+ * sizes apply (dgvit_got_workspace_floats / dgvit_got_bf16_workspace_bytes with save_for_backward = 0); there is no size query of
+ * its own.  No allocation and no host sync: capturable like the forward.  A null `maps` or a bad `rows` returns DGVIT_ERR_ARG, and every
+ * refusal of the forward (shape, token limit, bf16 restrictions) applies unchanged.
+ * -------------------------------------------------------------------------------------------- */
+#define DGVIT_MAPS_GOAL 0
+#define DGVIT_MAPS_ALL 1
+int dgvit_got_forward_maps(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal, float* feat,
+                           float* maps, int rows, float* workspace, long long workspace_floats, int batch, float dropout_keep,
+                           float layer_dropout_keep, unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev,
+                           void* stream);
+/* kernel level: qkv (B, N, 3*H*dh) as the encoder's to_qkv output, lse (B, H, N) the base-2 log-sum-exp of dgvit_attention_forward /
+ * dgvit_attention_forward_tiled (rows = DGVIT_MAPS_GOAL reads lse[b][h][0] only)  ->  probs (B, H, N) or (B, H, N, N) fp32.
+ * dh 64 or 32. */
+int dgvit_attention_probs(const float* qkv, const float* lse, float* probs, int B, int N, int H, int dh, int rows, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Head Linears (got_sac_network.py:111,115-121,226,230-234,429,433-435):  y = act(x W^T + b)
  *   x (M, K), w (N, K), b (N) or NULL, y (M, N); act: 0 = identity, 1 = ReLU.
  * -------------------------------------------------------------------------------------------- */
@@ -420,6 +446,15 @@ int dgvit_attention_forward_bf16(const unsigned short* qkv, unsigned short* out,
  * of scratch (rowsum(dout o out), handed from the dQ kernel to the dK/dV kernel) */
 int dgvit_attention_backward_bf16(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout, const float* lse,
                                   unsigned short* dqkv, float* delta, int B, int N, int H, int dh, void* stream);
+/* attention maps in the bf16 configuration (see dgvit_got_forward_maps): the arguments of dgvit_got_forward_bf16 without
+ * save_for_backward, plus maps and rows */
+int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
+                                const float* goal, float* feat, float* maps, int rows, void* workspace, long long workspace_bytes,
+                                int batch, float dropout_keep, unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev,
+                                void* stream);
+/* probabilities from bf16 qkv (dh 64) and the lse of dgvit_attention_forward_bf16; layouts as dgvit_attention_probs */
+int dgvit_attention_probs_bf16(const unsigned short* qkv, const float* lse, float* probs, int B, int N, int H, int dh, int rows,
+                               void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Optional live kernel timing (HIP events on the launch stream around kernel launches).
