@@ -152,7 +152,8 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_kernel(const bf16_t* __
   // all of a thread's 16-byte loads are requested before the first LDS write (a load-store-load-store loop would serialise
   // one memory round trip per chunk)
   {
-    constexpr int CH = 4;   // chunks per thread, image and trip: NP * 8 <= CH * NTHR for every supported N when NTHR = 512
+    constexpr int CH = 4;   // chunks per thread, image and trip: one trip when NP * 8 <= CH * NTHR (N <= 256 at 8 waves, N <= 288 at 9);
+                            // the loop is correct for any NP, a second trip only costs one more memory round trip
     for (int f0 = tid; f0 < NP * 8; f0 += CH * NTHR) {
       u32x4_t kv[CH], vv[CH];
 #pragma unroll
@@ -321,6 +322,102 @@ __global__ void __launch_bounds__(512) attn_fwd_bf16_stream_kernel(const bf16_t*
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The persistent form for 225 <= N <= 288 (eight or nine query tiles).  Five 288-row images would be 180 KB, so there is no Q image:
+// K and V stay double-buffered as 288-row images (4 x 36 KB = 144 KB) and each compute wave reads the Q fragments of its NEXT item
+// from global memory into registers while it computes the current one.  Waves 0..8 own query tiles 0..8, wave 9 is the loader
+// (72 DMA instructions per item: 4 full 64-row passes plus half a pass for rows 256..287).  With no Q buffer to free, the loader
+// starts the next item at once and one barrier per item remains.  Ten waves put three on two of the SIMDs: VGPR budget 168.
+template <bool HAS_LSE>
+__global__ void __launch_bounds__(640) attn_fwd_bf16_stream288_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse,
+                                                                      int N, int H, float scale, int nq, int nitems) {
+  constexpr int DH = 64, IMG = 288 * 128, LOADER = 9;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  const int nkt = (N + 31) / 32;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, h = lane >> 5;
+  const int I = H * DH;
+  const long long ld = 3ll * I;
+  const unsigned ldb = 3u * (unsigned)I * 2u;
+  const float sc = scale * DGVIT_LOG2E;
+  // DMA lane geometry as in attn_fwd_bf16_stream_kernel: instruction j of share sw fills rows 64 j + 8 sw + (lane >> 3); the fifth
+  // pass (j = 4) only for shares 0..3 (rows 256..287: a share of 4..7 would write into the next image)
+  const unsigned cv = (unsigned)((lane & 7) ^ (((lane >> 4) & 1) << 2)), dstep = 64u * ldb;
+  auto issue_item = [&](int item, int buf, int sw) {
+    const int drow = 8 * sw + (lane >> 3);
+    const unsigned ck = (unsigned)((lane & 7) ^ ((4 * (sw & 1) + (lane >> 4)) & 7));
+    const unsigned offk = (unsigned)drow * ldb + ck * 16u, offv = (unsigned)drow * ldb + cv * 16u;
+    const bool live = item < nitems;
+    const int b = live ? item / H : 0, hd = live ? item % H : 0;
+    const bf16_t* base = qkv + (long long)b * N * (3ll * I) + hd * DH;
+    const int bytes = live ? (int)((unsigned)(N - 1) * ldb + 128u) : 0;
+    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base + I), 0, bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base + 2 * I), 0, bytes, 0x00020000);
+    unsigned char* kd = smem + buf * IMG + sw * 1024, *vd = smem + (2 + buf) * IMG + sw * 1024;
+    const int passes = sw < 4 ? 5 : 4;   // wave-uniform
+    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (attn_lds_ptr_t)(kd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
+    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (attn_lds_ptr_t)(vd + j * 8192), 16, offv + j * dstep, 0, 0, 0);
+  };
+  const unsigned fsw = (unsigned)((li >> 1) & 7);
+  const int nqt = (nq + 31) / 32;
+  const bool computes = wave < nqt;
+  // Q fragments of `item` for this wave's tile (rows >= N read row 0: harmless, never stored)
+  auto load_q = [&](bf16x8 (&f)[4], int item) {
+    const int q = wave * 32 + li;
+    const bf16_t* qrow = qkv + ((long long)(item / H) * N + (q < N ? q : 0)) * ld + (item % H) * DH;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) f[s] = *reinterpret_cast<const bf16x8*>(qrow + 16 * s + 8 * h);
+  };
+  if (wave < 8) issue_item(blockIdx.x, 0, wave);
+  bf16x8 qn[4];
+  if (computes) load_q(qn, blockIdx.x);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  int buf = 0;
+  for (int item = blockIdx.x; item < nitems; item += gridDim.x, buf ^= 1) {
+    const unsigned char* Ks = smem + buf * IMG, *Vs = smem + (2 + buf) * IMG;
+    if (wave == LOADER) {
+#pragma unroll 1
+      for (int sw = 0; sw < 8; ++sw) issue_item(item + (int)gridDim.x, buf ^ 1, sw);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if (computes) {
+      const int b = item / H, hd = item % H;
+      bf16x8 qf[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qf[s] = qn[s];
+      if (item + (int)gridDim.x < nitems) load_q(qn, item + (int)gridDim.x);   // lands while this item is computed
+      const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out + (long long)b * N * I + hd * DH, 0, (int)((unsigned)(nq - 1) * (unsigned)I * 2u + 128u), 0x00020000);
+      const int q = wave * 32 + li;
+      float m = -INFINITY, l = 0.f;
+      f32x16 o[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        o[0][r] = 0.f;
+        o[1][r] = 0.f;
+      }
+      int kt = 0;
+      for (; kt + 2 <= nkt; kt += 2) attn_key_tiles<2>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw);
+      if (kt < nkt) attn_key_tiles<1>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw);
+      const float inv = 1.f / l;
+      const unsigned orow = (unsigned)q * (unsigned)I * 2u;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          fx4 v = {o[dt][4 * c] * inv, o[dt][4 * c + 1] * inv, o[dt][4 * c + 2] * inv, o[dt][4 * c + 3] * inv};
+          typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, __builtin_convertvector(v, bf16x4)), ro, orow + (unsigned)(dt * 32 + 8 * c + 4 * h) * 2u, 0, 0);
+        }
+      if constexpr (HAS_LSE) {
+        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(lse + ((long long)b * H + hd) * N, 0, nq * 4, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, m + __builtin_amdgcn_logf(l)), rl, h == 0 ? (unsigned)q * 4u : 0x80000000u, 0, 0);
+      }
+    }
+    __builtin_amdgcn_s_barrier();   // the next item is complete in LDS (the loader waited for it); this item's K / V buffers are free
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // ------------------------------------------------------------------------------------------------ backward
 // Two kernels, each one workgroup of 8 waves per (frame, head), probabilities recomputed from the saved base-2
 // log-sum-exp (nothing of size N x N is stored):
@@ -424,11 +521,13 @@ __device__ __forceinline__ void store_T_bf16(const f32x16 (&o)[2], bf16_t* rowpt
     }
 }
 
-__global__ void __launch_bounds__(512) attn_bwd_dq_bf16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o_fwd,
-                                                               const bf16_t* __restrict__ d_out, const float* __restrict__ lse,
-                                                               bf16_t* __restrict__ dqkv, float* __restrict__ delta, int N, int H,
-                                                               float scale) {
-  constexpr int DH = 64, NTHR = 512, NW = 8;
+// NW = 8; NW = 9 for nine query tiles (257 <= N <= 288: one tile per wave instead of a second round for one wave)
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_bwd_dq_bf16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o_fwd,
+                                                                   const bf16_t* __restrict__ d_out, const float* __restrict__ lse,
+                                                                   bf16_t* __restrict__ dqkv, float* __restrict__ delta, int N, int H,
+                                                                   float scale) {
+  constexpr int DH = 64, NTHR = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nkt = (N + 31) / 32, NP = nkt * 32, VS = NP + 8;
   unsigned char* Ks = smem;
@@ -561,10 +660,17 @@ __global__ void __launch_bounds__(512) attn_bwd_dkv_bf16_kernel(const bf16_t* __
 
 }  // namespace
 
+// raise the dynamic-LDS limit of each kernel (once per device, by the callers' DeviceOnce)
+static bool raise_lds(const void* const* kerns, int n, int bytes) {
+  for (int i = 0; i < n; ++i)
+    if (hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  return true;
+}
+
 int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
   DGVIT_CHECK_ARG(qkv && out && B > 0 && H > 0, "attention_bf16: bad arguments");
   DGVIT_CHECK_ARG(dh == 64, "attention_bf16: dim_head=%d unsupported (64)", dh);
-  DGVIT_CHECK_ARG(N >= 1 && N <= 224, "attention_bf16: tokens N=%d outside [1, 224]", N);
+  DGVIT_CHECK_ARG(N >= 1 && N <= 288, "attention_bf16: tokens N=%d outside [1, 288]", N);
   DGVIT_CHECK_ARG(nq >= 1 && nq <= N, "attention_bf16: bad query limit");
   const int NP = (N + 31) / 32 * 32;
   const size_t lds = (size_t)2 * NP * 128;
@@ -573,12 +679,14 @@ int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N,
   const int slot = profile_begin(PROF_ATTN_FWD, flops, st);
   // many items of more than four query tiles (BASELINE config 5: N = 197, 5280 items): the persistent kernel with LDS-DMA prefetch
   const long long items = (long long)B * H;
-  if ((N + 31) / 32 > 4 && items >= 512 && 3ll * H * dh * 2 * 256 < (1ll << 31)) {
-    int dev = 0, cus = 256;
+  static int cached_cus = 0;
+  if (!cached_cus) {
+    int dev = 0;
     hipDeviceProp_t prop;
-    static int cached_cus = 0;
-    if (!cached_cus) cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    cus = cached_cus;
+    cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }
+  const int cus = cached_cus;
+  if (N <= 224 && (N + 31) / 32 > 4 && items >= 512 && 3ll * H * dh * 2 * 256 < (1ll << 31)) {
     static DeviceOnce once;
     if (const unsigned long long bit = once.pending()) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_bf16_stream_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
@@ -589,10 +697,35 @@ int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N,
     const unsigned grid = (unsigned)(items < cus ? items : cus);
     if (lse) hipLaunchKernelGGL((attn_fwd_bf16_stream_kernel<true>), dim3(grid), dim3(512), 160 * 1024, st, qkv, out, lse, N, H, scale, nq, (int)items);
     else hipLaunchKernelGGL((attn_fwd_bf16_stream_kernel<false>), dim3(grid), dim3(512), 160 * 1024, st, qkv, out, lse, N, H, scale, nq, (int)items);
-  } else if ((nq + 31) / 32 > 4)
-    hipLaunchKernelGGL((attn_fwd_bf16_kernel<8>), dim3((unsigned)((long long)B * H)), dim3(512), lds, st, qkv, out, lse, N, H, scale, nq);
-  else
-    hipLaunchKernelGGL((attn_fwd_bf16_kernel<4>), dim3((unsigned)((long long)B * H)), dim3(256), lds, st, qkv, out, lse, N, H, scale, nq);
+  } else if (N > 224 && (g_attn_bf16_long & 1) && items >= 512 && 3ll * H * dh * 2 * 288 < (1ll << 31)) {
+    constexpr int LDS288 = 4 * 288 * 128;   // K, V double-buffered: 144 KB
+    static DeviceOnce once;
+    if (const unsigned long long bit = once.pending()) {
+      const void* k[2] = {reinterpret_cast<const void*>(&attn_fwd_bf16_stream288_kernel<true>), reinterpret_cast<const void*>(&attn_fwd_bf16_stream288_kernel<false>)};
+      if (!raise_lds(k, 2, LDS288)) return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd_bf16: cannot raise the dynamic LDS limit");
+      once.mark(bit);
+    }
+    const unsigned grid = (unsigned)(items < cus ? items : cus);
+    if (lse) hipLaunchKernelGGL((attn_fwd_bf16_stream288_kernel<true>), dim3(grid), dim3(640), LDS288, st, qkv, out, lse, N, H, scale, nq, (int)items);
+    else hipLaunchKernelGGL((attn_fwd_bf16_stream288_kernel<false>), dim3(grid), dim3(640), LDS288, st, qkv, out, lse, N, H, scale, nq, (int)items);
+  } else {
+    if (lds > 64 * 1024) {   // N > 256: K + V images above the default 64 KB
+      static DeviceOnce once;
+      if (const unsigned long long bit = once.pending()) {
+        const void* k[3] = {reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<4>), reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<8>),
+                            reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<9>)};
+        if (!raise_lds(k, 3, 2 * 288 * 128)) return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd_bf16: cannot raise the dynamic LDS limit");
+        once.mark(bit);
+      }
+    }
+    const int nqt = (nq + 31) / 32;
+    if (nqt > 8 && (g_attn_bf16_long & 2))
+      hipLaunchKernelGGL((attn_fwd_bf16_kernel<9>), dim3((unsigned)((long long)B * H)), dim3(576), lds, st, qkv, out, lse, N, H, scale, nq);
+    else if (nqt > 4)
+      hipLaunchKernelGGL((attn_fwd_bf16_kernel<8>), dim3((unsigned)((long long)B * H)), dim3(512), lds, st, qkv, out, lse, N, H, scale, nq);
+    else
+      hipLaunchKernelGGL((attn_fwd_bf16_kernel<4>), dim3((unsigned)((long long)B * H)), dim3(256), lds, st, qkv, out, lse, N, H, scale, nq);
+  }
   profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("attn_fwd_bf16_kernel");
   return DGVIT_OK;
@@ -603,24 +736,27 @@ int attention_bwd_bf16(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout,
                        int N, int H, int dh, hipStream_t st) {
   DGVIT_CHECK_ARG(qkv && out && dout && lse && dqkv && delta && B > 0 && H > 0, "attention_bwd_bf16: bad arguments");
   DGVIT_CHECK_ARG(dh == 64, "attention_bwd_bf16: dim_head=%d unsupported (64)", dh);
-  DGVIT_CHECK_ARG(N >= 1 && N <= 224, "attention_bwd_bf16: tokens N=%d outside [1, 224]", N);
+  DGVIT_CHECK_ARG(N >= 1 && N <= 288, "attention_bwd_bf16: tokens N=%d outside [1, 288]", N);
   const int NP = (N + 31) / 32 * 32;
-  const size_t lds_q = (size_t)2 * NP * 128 + (size_t)64 * (NP + 8) * 2;
-  const size_t lds_kv = (size_t)2 * NP * 128 + (size_t)2 * 64 * (NP + 8) * 2 + (size_t)2 * NP * 4;
+  const size_t lds_q = (size_t)2 * NP * 128 + (size_t)64 * (NP + 8) * 2;                            // 109 KB at NP = 288
+  const size_t lds_kv = (size_t)2 * NP * 128 + (size_t)2 * 64 * (NP + 8) * 2 + (size_t)2 * NP * 4;  // 148 KB at NP = 288
   static DeviceOnce once;
   if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) !=
-            hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
+    const void* kq[2] = {reinterpret_cast<const void*>(&attn_bwd_dq_bf16_kernel<8>), reinterpret_cast<const void*>(&attn_bwd_dq_bf16_kernel<9>)};
+    const void* kkv[1] = {reinterpret_cast<const void*>(&attn_bwd_dkv_bf16_kernel)};
+    if (!raise_lds(kq, 2, 120 * 1024) || !raise_lds(kkv, 1, 160 * 1024))
       return dgvit_set_error(DGVIT_ERR_HIP, "attention_bwd_bf16: cannot raise the dynamic LDS limit");
     once.mark(bit);
   }
   const float scale = 1.0f / sqrtf((float)dh);
   const double flops = 10.0 * (double)N * N * dh * H * B;   // 2.5 x forward
   const int slot = profile_begin(PROF_ATTN_BWD, flops, st);
-  hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel, dim3((unsigned)((long long)B * H)), dim3(512), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
-                     H, scale);
+  if (NP > 256 && (g_attn_bf16_long & 2))
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<9>), dim3((unsigned)((long long)B * H)), dim3(576), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
+                       H, scale);
+  else
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<8>), dim3((unsigned)((long long)B * H)), dim3(512), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
+                       H, scale);
   hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, dim3((unsigned)((long long)B * H)), dim3(512), lds_kv, st, qkv, dout, lse, delta, dqkv, N, H,
                      scale);
   profile_end(slot, st);

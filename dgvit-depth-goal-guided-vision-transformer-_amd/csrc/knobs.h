@@ -54,6 +54,7 @@ DGVIT_KNOB(long long*, g_gemm_bf16_stamps, nullptr)
 DGVIT_KNOB(int, g_attn_bwd64, 1)                // single-pass fp32 attention backward for 32 < N <= 64
 DGVIT_KNOB(int, g_gemm_zfold, 1)                // weight-gradient GEMMs: k-slices folded into blockIdx.x, k-slice major per XCD (0: grid z)
 DGVIT_KNOB(int, g_attn_q1, 1)                   // one-query (token 0) fp32 attention forward / backward on plain FMAs for N <= 64
+DGVIT_KNOB(int, g_attn_bf16_long, 3)           // bf16 attention at 225..288 tokens: bit 0 the persistent forward (>= 512 items), bit 1 nine-wave workgroups for nine tiles
 #ifdef DGVIT_DIAG
 extern long long g_gemm_persist_launches;       // launches that took the pipelined kernel
 #endif

@@ -159,7 +159,8 @@ class GoT(nn.Module):
         ``wgrad_overlap``: the backward runs the weight-gradient GEMMs on a helper stream beside the data-gradient chain
         (+3..5 % frames/s at BASELINE config 3; per-kernel timings stop being interpretable).
         ``long_sequence``: lift the fp32 encoder's 288-token limit -- for N > 288 the attention runs on K / V-tiled kernels (N <= 288 is
-        unchanged, bit for bit); the backward needs B*H*N floats more scratch.  fp32 only (the bf16 configuration stops at 256 tokens)."""
+        unchanged, bit for bit); the backward needs B*H*N floats more scratch.  fp32 only: the bf16 configuration runs up to 288 tokens,
+        the limit both configurations share without this option."""
         from ._lib import FLAG_DENSE_LAST_BLOCK, FLAG_LONG_SEQUENCE, FLAG_WGRAD_OVERLAP
         if long_sequence:
             self._check_long_sequence_dtype(self.compute_dtype, True)
@@ -177,7 +178,7 @@ class GoT(nn.Module):
     def _check_long_sequence_dtype(dtype, long_sequence):
         if dtype == torch.bfloat16 and long_sequence:
             raise NotImplementedError("long_sequence (the K/V-tiled attention for more than 288 tokens) is implemented on the fp32 path "
-                                      "only; the bf16 configuration keeps its 256-token limit")
+                                      "only; the bf16 configuration runs up to 288 tokens (e.g. 256x256 frames with 16x16 patches)")
 
     def layer_dropout(self) -> float:
         """The transformer ``dropout`` p (the reference's nn.Dropout modules inside the blocks; they all share it)."""

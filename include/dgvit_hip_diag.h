@@ -88,6 +88,10 @@ void dgvit_set_gemm_bf16_l2_budget_kb(int kb);
 void dgvit_set_attention_bwd_single_pass(int on);
 /* 0: a one-query attention (the last block's token 0) runs on the MFMA tile kernels as before round 4; 1 (default): attn_q1_*_kernel */
 void dgvit_set_attention_single_query(int on);
+/* A/B knob, bf16 attention at 225 <= N <= 288 tokens: bit 0 the persistent forward (attn_fwd_bf16_stream288_kernel) for >= 512 items,
+ * else the per-item kernel; bit 1 nine-wave workgroups (per-item forward, dq backward) for nine 32-token tiles, else eight waves with a second
+ * round for one of them.  Default 3; -1 restores it.  Same results whatever the bits. */
+void dgvit_set_attention_bf16_long(int bits);
 /* A/B knob: 1 (default) the weight-gradient GEMMs deal (tile, k-slice) pairs to the XCDs k-slice major (an XCD reads its slices of dY and X
  * once); 0 the round 1-3 grid (tiles, 1, slices): an XCD owns a few tiles and all their slices.  Bit-identical results. */
 void dgvit_set_gemm_wgrad_slice_major(int on);
