@@ -94,11 +94,11 @@ SplitPlan wgrad_bf16_plan(int Mo, int Ko, int Tp) {
   const long long tiles = (long long)((Mo + 255) / 256) * ((Ko + 255) / 256);
   long long s = 256 / tiles;
   if (s < 1) s = 1;
-  const long long maxs = (Tp + 511) / 512;   // at least 16 k-tiles per slice
+  const long long maxs = ((long long)Tp + 511) / 512;   // at least 16 k-tiles per slice (64-bit: Tp + 511 wraps for Tp near 2^31)
   if (s > maxs) s = maxs;
   SplitPlan pl;
   pl.kchunk = (int)((((Tp + s - 1) / s) + 31) / 32 * 32);
-  pl.splits = (Tp + pl.kchunk - 1) / pl.kchunk;
+  pl.splits = (int)(((long long)Tp + pl.kchunk - 1) / pl.kchunk);
   pl.slab = al4((long long)Mo * Ko);
   return pl;
 }

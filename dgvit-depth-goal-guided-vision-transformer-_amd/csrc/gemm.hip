@@ -1387,9 +1387,13 @@ int launch_persistent(const GemmParams& p, hipStream_t stream, bool* taken) {
 
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// the tallest / widest tile of DGVIT_TILES: gemm_f32's leading-dimension checks bound a tile's 32-bit row offsets with it
+#define DGVIT_MAX_TILE_ROWS 128
+
 template <class T, int LAYOUT, int VEC, int EPI, bool GATHER = false>
 int launch(const GemmParams& p0, int nsplit, hipStream_t stream) {
   constexpr int BM = T::BM, BN = T::BN, BK = T::BK;
+  static_assert(BM <= DGVIT_MAX_TILE_ROWS && BN <= DGVIT_MAX_TILE_ROWS, "raise DGVIT_MAX_TILE_ROWS: gemm_f32's leading-dimension checks depend on it");
   constexpr bool AKC = LAYOUT != GEMM_TN;
   constexpr bool BKC = LAYOUT == GEMM_NT;
   constexpr int A_TILE = AKC ? BM * (BK + 4) : BK * (BM + 4);
@@ -1526,7 +1530,14 @@ int gemm_f32(int layout, int epi, const GemmParams& p, int nsplit, hipStream_t s
   if (layout == GEMM_NN) vec4 = vec4 && p.K % 4 == 0 && p.N % 4 == 0;
   if (layout == GEMM_TN) vec4 = vec4 && p.M % 4 == 0 && p.N % 4 == 0;
   DGVIT_CHECK_ARG(p.a_kgrp == 0, "gemm: a_kgrp is no longer supported (gather the rows first)");
-  DGVIT_CHECK_ARG((long long)p.lda * 512 < 0x7FFFFFFFll && (long long)p.ldb * 512 < 0x7FFFFFFFll, "gemm: leading dimension too large");
+  // 32-bit byte offsets inside a descriptor window of at most 2 GiB: a tile's DGVIT_MAX_TILE_ROWS rows of an operand must fit
+  constexpr long long ROW_BYTES = 4ll * DGVIT_MAX_TILE_ROWS;
+  DGVIT_CHECK_ARG(p.lda * ROW_BYTES < 0x7FFFFFFFll && p.ldb * ROW_BYTES < 0x7FFFFFFFll, "gemm: leading dimension too large");
+  // ... and so must the rows of C / residual / C2 / aux that the direct epilogue addresses the same way.  Conservative: strides this
+  // large are refused whatever M is and also where the LDS-image or element-wise epilogue (64-bit addresses) would run.
+  DGVIT_CHECK_ARG(p.ldc * ROW_BYTES < 0x7FFFFFFFll && (!p.res || p.ldr * ROW_BYTES < 0x7FFFFFFFll) &&
+                      (!p.C2 || p.ldc2 * ROW_BYTES < 0x7FFFFFFFll) && (!p.aux || p.ldaux * ROW_BYTES < 0x7FFFFFFFll),
+                  "gemm: output leading dimension too large");
   DGVIT_CHECK_ARG(layout == GEMM_NT || (long long)p.kchunk * p.ldb * 4 < 0x7FFFFFFFll, "gemm: k-chunk x ldb exceeds the 2 GiB descriptor window");
   DGVIT_CHECK_ARG(layout != GEMM_TN || (long long)p.kchunk * p.lda * 4 < 0x7FFFFFFFll, "gemm: k-chunk x lda exceeds the 2 GiB descriptor window");
   GemmParams q = p;

@@ -41,7 +41,7 @@ inline int wgrad_splits(int M, int N, int K) {
   const int bt = (M >= 128 && N >= 128) ? 128 : 64;  // must mirror pick_tile's automatic TN choice
   const long long tiles = (long long)((M + bt - 1) / bt) * ((N + bt - 1) / bt);
   long long s = 512 / tiles;
-  const long long maxs = (K + 255) / 256;  // at least 8 k-tiles per split
+  const long long maxs = ((long long)K + 255) / 256;  // at least 8 k-tiles per split (64-bit: K + 255 wraps for K near 2^31)
   if (s > maxs) s = maxs;
   if (s > 256) s = 256;
   if (s < 1) s = 1;

@@ -152,3 +152,33 @@ def gemm_ref_rows(a, b64, rows, bias=None):
     ar = a[rows.to(a.device), :K].double().cpu()
     h = ar @ b64.T
     return h if bias is None else h + bias.double().cpu()
+
+
+# ------------------------------------------------------------------------------------------------ operands past 2 GiB / 4 GiB / 2^31 elements
+GIB = 1 << 30
+
+
+def boundary_rows(n_rows, row_elems, itemsize=4):
+    """Rows on each side of every 2^31-byte, 2^32-byte and 2^31-element offset of an (n_rows, row_elems) operand whose rows are
+    row_elems elements apart (the leading dimension): for a boundary at element e, the row that holds element e - 1 and the row that
+    holds element e, plus one neighbour on each side.  Boundaries the operand does not reach give nothing."""
+    rows = set()
+    for e in ((1 << 31) // itemsize, (1 << 32) // itemsize, 1 << 31):
+        r = e // row_elems
+        rows |= {q for q in (r - 2, r - 1, r, r + 1) if 0 <= q < n_rows and r < n_rows}
+    return sorted(rows)
+
+
+def large_rows(n_rows, row_elems, itemsize=4, extra=64, seed=0):
+    """sampled_rows for a large operand: first and last panel, the rows around every byte / element boundary, a seeded sample."""
+    return sampled_rows(n_rows, extra=extra, seed=seed, more=boundary_rows(n_rows, row_elems, itemsize))
+
+
+def need_device_memory(nbytes):
+    """Skip (with the numbers) when the device has less than ``nbytes`` free; the large-operand tests stay under 48 GiB each."""
+    import pytest
+    assert nbytes <= 48 * GIB, f"a large-operand test may use at most 48 GiB, this one asks for {nbytes / GIB:.1f}"
+    torch.cuda.empty_cache()
+    free, total = torch.cuda.mem_get_info()
+    if free < nbytes + GIB:
+        pytest.skip(f"needs {nbytes / GIB:.1f} GiB (+1 GiB slack) of device memory, {free / GIB:.1f} of {total / GIB:.1f} GiB free")

@@ -300,7 +300,9 @@ def test_soft_update_flat(amd):
 
 
 def test_large_batch_indexing(amd):
-    """B = 2048 frames (T = 102400 token rows, > 2^31 bytes of hidden activations): 64-bit indexing everywhere.
+    """B = 2048 frames (T = 102 400 token rows).  The largest single operand is the fc1 output, 102 400 x 2048 floats = 838 860 800
+    bytes: no one buffer reaches 2^31 bytes here (the two layers' activations together do), so this test does not cross any of
+    the size boundaries of DESIGN 3.21.
     Frame independence: rows of the big batch equal the same frames run as a small batch."""
     cfg = O.GoTConfig(image=(84, 84), patch=(12, 12), dim=256, depth=2, heads=8)
     torch.manual_seed(3)
