@@ -80,7 +80,10 @@ struct CastBatch {
 void cast_batch_init(CastBatch& b);
 int cast_batch_add(CastBatch& b, const float* src, bf16_t* dst, long long n, hipStream_t st);
 int cast_batch_flush(CastBatch& b, hipStream_t st);
-int patchify_bf16(const float* img, bf16_t* patches, int B, int ih, int iw, int ph, int pw, hipStream_t st);
+// fp32 (rows, cols) -> bf16 (rows, ldd >= cols) with columns cols .. ldd-1 zeroed; cols may be odd (the padded patch weight)
+int cast_f32_bf16_rows(const float* src, bf16_t* dst, long long rows, int cols, int ldd, hipStream_t st);
+// patches: (B * P) rows of ldp elements, ldp = ph * pw or ph * pw rounded up to 8; columns ph * pw .. ldp-1 are written as zeros
+int patchify_bf16(const float* img, bf16_t* patches, int ldp, int B, int ih, int iw, int ph, int pw, hipStream_t st);
 int layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd, int T, int D,
                        float eps, int rs, hipStream_t st);
 int add_layernorm_fwd_bf16(const float* x, const bf16_t* delta, float* xout, const float* gamma, const float* beta, bf16_t* y,

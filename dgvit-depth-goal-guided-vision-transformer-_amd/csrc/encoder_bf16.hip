@@ -14,7 +14,11 @@ namespace {
 inline long long al128(long long bytes) { return (bytes + 255) & ~255ll; }
 inline int up8(long long n) { return (int)((n + 7) & ~7ll); }
 
-// bf16 weight arena (elements): patch weight, then per layer to_qkv, to_out, fc1, fc2 in the reference's (out, in)
+// The patch GEMM needs K and both row strides % 8 == 0 (gemm_bf16): patch rows and patch-weight rows have ldp = up8(pd) elements with a
+// zero tail.  ldp == pd for every patch area that is a multiple of 8: nothing differs from the unpadded layout there.
+inline int patch_ld(const Dims& d) { return up8(d.pd); }
+
+// bf16 weight arena (elements): patch weight (D rows of ldp), then per layer to_qkv, to_out, fc1, fc2 in the reference's (out, in)
 // layouts, followed by their transposes (in, out) -- the B operands of the data-gradient GEMMs dX = dY W
 struct Wp {
   long long patch, layer0, qkv, out, fc1, fc2, qkvT, outT, fc1T, fc2T, layer_elems, total;
@@ -22,7 +26,7 @@ struct Wp {
 Wp make_wp(const Dims& d) {
   Wp w;
   long long o = 0;
-  w.patch = o; o += al4((long long)d.D * d.pd);
+  w.patch = o; o += al4((long long)d.D * patch_ld(d));
   long long l = 0;
   w.qkv = l; l += (long long)3 * d.I * d.D;
   w.out = l; l += (long long)d.D * d.I;
@@ -46,7 +50,7 @@ struct Wsb {
 Wsb make_wsb(const Dims& d, int save) {
   Wsb w;
   long long o = 0;
-  w.patches = o; o += al128((long long)d.B * d.P * d.pd * 2);
+  w.patches = o; o += al128((long long)d.B * d.P * patch_ld(d) * 2);
   w.xa = o; o += al128(d.T * d.D * 4);
   w.xb = o; o += al128(d.T * d.D * 4);
   w.pooled = o; o += al128((long long)d.B * d.D * 4);
@@ -78,7 +82,7 @@ Wsb make_wsb(const Dims& d, int save) {
 int check_bf16_dims(const Dims& d) {
   DGVIT_CHECK_ARG(d.dh == 64, "bf16 path: dim_head=%d unsupported (64)", d.dh);
   DGVIT_CHECK_ARG(d.proj, "bf16 path: heads == 1 with dim_head == dim (attention without output projection) runs on the fp32 path only");
-  DGVIT_CHECK_ARG(d.D % 8 == 0 && d.M % 8 == 0 && d.pd % 8 == 0, "bf16 path: dim, mlp_dim and patch pixels must be multiples of 8");
+  DGVIT_CHECK_ARG(d.D % 8 == 0 && d.M % 8 == 0, "bf16 path: dim and mlp_dim must be multiples of 8");
   return DGVIT_OK;
 }
 
@@ -188,7 +192,9 @@ extern "C" int dgvit_got_pack_weights_bf16(const dgvit_config* cfg, const float*
   if (wpack_elems < w.total) return dgvit_set_error(DGVIT_ERR_WORKSPACE, "bf16 weight arena %lld < %lld elements", wpack_elems, w.total);
   CastBatch cb;     // the straight copies of all layers go out as one launch (49 segments at depth 12)
   cast_batch_init(cb);
-  TRY(cast_batch_add(cb, params[P_PW], wpack + w.patch, (long long)d.D * d.pd, st));
+  const int ldp = patch_ld(d);
+  if (ldp == d.pd) TRY(cast_batch_add(cb, params[P_PW], wpack + w.patch, (long long)d.D * d.pd, st));
+  else TRY(cast_f32_bf16_rows(params[P_PW], wpack + w.patch, d.D, d.pd, ldp, st));   // rows padded to ldp, tail zeroed
   for (int i = 0; i < d.L; ++i) {
     const float* const* lp = params + P_L0 + DGVIT_PARAMS_PER_LAYER * i;
     bf16_t* lw = wpack + w.layer0 + w.layer_elems * i;
@@ -236,9 +242,10 @@ int token_assembly_bf16(const FwdB& f, const float* img, const float* goal, floa
   const dgvit_config* cfg = f.cfg;
   hipStream_t st = f.st;
   bf16_t* patches = (bf16_t*)(f.ws + f.w.patches);
-  TRY(patchify_bf16(img, patches, d.B, cfg->image_h, cfg->image_w, cfg->patch_h, cfg->patch_w, st));
+  const int ldp = patch_ld(d);
+  TRY(patchify_bf16(img, patches, ldp, d.B, cfg->image_h, cfg->image_w, cfg->patch_h, cfg->patch_w, st));
   {
-    GemmBf16Params p = gpb(patches, d.pd, f.wpack + f.wp.patch, d.pd, x, d.D, d.B * d.P, d.D, d.pd);
+    GemmBf16Params p = gpb(patches, ldp, f.wpack + f.wp.patch, ldp, x, d.D, d.B * d.P, d.D, ldp);
     p.bias = f.params[P_PB];
     p.res = f.params[P_POS]; p.ldr = d.D; p.res_mod = d.P;
     p.c_rgrp = d.P;

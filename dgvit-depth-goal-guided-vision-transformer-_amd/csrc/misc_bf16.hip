@@ -66,6 +66,59 @@ __global__ void __launch_bounds__(256) patchify_bf16_kernel(const float* __restr
   out[idx] = __builtin_bit_cast(bf16_t, v);
 }
 
+// Patch areas that are no multiple of 8 (14 x 14, 7 x 7, 3 x 5): the patch GEMM needs K and both row strides % 8 == 0, so the rows
+// of `out` have ldo = pd rounded up to 8 elements and columns pd .. ldo-1 are written as zeros on EVERY call (the workspace is the
+// caller's memory: whatever it held would meet the weight's zero tail, and NaN x 0 is NaN).  idx walks the padded output.
+__global__ void __launch_bounds__(256) patchify_bf16_pad_kernel(const float* __restrict__ img, bf16_t* __restrict__ out, int B, int Hi,
+                                                                int Wi, int ph, int pw, int ldo) {
+  const int gw = Wi / pw, gh = Hi / ph, pd = ph * pw;
+  const long long total = (long long)B * gh * gw * ldo;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int e = (int)(idx % ldo);
+  const long long bp = idx / ldo;
+  const int p = (int)(bp % (gh * gw));
+  const long long b = bp / (gh * gw);
+  float f = 0.f;
+  if (e < pd) {
+    const int p1 = e / pw, p2 = e % pw, hy = p / gw, wx = p % gw;
+    f = img[(b * Hi + hy * ph + p1) * Wi + wx * pw + p2];
+  }
+  out[idx] = __builtin_bit_cast(bf16_t, (__bf16)f);
+}
+
+// the same for patch widths that are multiples of 4 (3 x 4: pd = 12, ldo = 16): pd and ldo are multiples of 4, a group of four output
+// elements is either four pixels of one patch row or four pad columns.  idx4 walks the padded output in units of four elements.
+__global__ void __launch_bounds__(256) patchify_bf16_x4_pad_kernel(const float* __restrict__ img, bf16_t* __restrict__ out, int B, int Hi,
+                                                                   int Wi, int ph, int pw, int ldo) {
+  const int gw = Wi / pw, gh = Hi / ph, pd4 = ph * pw / 4, pw4 = pw / 4, ld4 = ldo / 4;
+  const long long total4 = (long long)B * gh * gw * ld4;
+  const long long idx4 = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx4 >= total4) return;
+  const int e4 = (int)(idx4 % ld4);
+  const long long bp = idx4 / ld4;
+  const int p = (int)(bp % (gh * gw));
+  const long long b = bp / (gh * gw);
+  fx4 v = {0.f, 0.f, 0.f, 0.f};
+  if (e4 < pd4) {
+    const int p1 = e4 / pw4, q = e4 % pw4, hy = p / gw, wx = p % gw;
+    v = *reinterpret_cast<const fx4*>(img + (b * Hi + hy * ph + p1) * Wi + wx * pw + 4 * q);
+  }
+  reinterpret_cast<bf16x4*>(out)[idx4] = __builtin_convertvector(v, bf16x4);
+}
+
+// fp32 (rows, cols) -> bf16 (rows, ldd), columns cols .. ldd-1 zeroed (the padded patch weight of the arena).  cols may be odd, so
+// the source rows have no alignment beyond 4 bytes: scalar loads.  A weight of D x pd elements: a few hundred KB at most.
+__global__ void __launch_bounds__(256) cast_f32_bf16_rows_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long long rows,
+                                                                 int cols, int ldd) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * ldd) return;
+  const long long r = idx / ldd;
+  const int c = (int)(idx % ldd);
+  const float f = c < cols ? src[r * cols + c] : 0.f;
+  dst[idx] = __builtin_bit_cast(bf16_t, (__bf16)f);
+}
+
 // nn.LayerNorm(D), eps 1e-5 (GoalFormer.py:34,37): fp32 row in, bf16 row out; one wave per row, row kept in registers.
 // ADD: the row is first completed with the bf16 branch output of the previous sub-block (GoalFormer.py:103-104:
 // x = attn(..) + x / x = ff(..) + x): v = x + delta, written back to the fp32 residual stream `xout` (unless NULL).  With `delta2`
@@ -193,11 +246,33 @@ int cast_batch_flush(CastBatch& b, hipStream_t st) {
   return DGVIT_OK;
 }
 
-int patchify_bf16(const float* img, bf16_t* out, int B, int Hi, int Wi, int ph, int pw, hipStream_t st) {
+int cast_f32_bf16_rows(const float* src, bf16_t* dst, long long rows, int cols, int ldd, hipStream_t st) {
+  DGVIT_CHECK_ARG(src && dst && rows > 0 && cols > 0 && ldd >= cols, "cast_f32_bf16_rows: bad arguments");
+  const long long total = rows * ldd;
+  DGVIT_CHECK_ARG((total + 255) / 256 < (1ll << 31), "cast_f32_bf16_rows: too many elements");
+  hipLaunchKernelGGL(cast_f32_bf16_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, dst, rows, cols, ldd);
+  DGVIT_CHECK_LAUNCH("cast_f32_bf16_rows");
+  return DGVIT_OK;
+}
+
+// ldo: row stride of `out` in elements, ph * pw or ph * pw rounded up to a multiple of 8 (tail columns zeroed)
+int patchify_bf16(const float* img, bf16_t* out, int ldo, int B, int Hi, int Wi, int ph, int pw, hipStream_t st) {
   DGVIT_CHECK_ARG(img && out && B > 0, "patchify_bf16: bad arguments");
   DGVIT_CHECK_ARG(ph > 0 && pw > 0 && Hi % ph == 0 && Wi % pw == 0, "Image dimensions must be divisible by the patch size.");
+  const int pd = ph * pw;
+  DGVIT_CHECK_ARG(ldo == pd || (ldo == ((pd + 7) & ~7)), "patchify_bf16: row stride %d for a patch of %d pixels", ldo, pd);
+  const bool x4 = pw % 4 == 0 && Wi % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 7) == 0;   // four pixels of a patch row per thread
+  if (ldo != pd) {
+    const long long total = (long long)B * (Hi / ph) * (Wi / pw) * ldo;
+    if (x4)
+      hipLaunchKernelGGL(patchify_bf16_x4_pad_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, img, out, B, Hi, Wi, ph, pw, ldo);
+    else
+      hipLaunchKernelGGL(patchify_bf16_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, img, out, B, Hi, Wi, ph, pw, ldo);
+    DGVIT_CHECK_LAUNCH("patchify_bf16");
+    return DGVIT_OK;
+  }
   const long long total = (long long)B * Hi * Wi;
-  if (pw % 4 == 0 && Wi % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 7) == 0) {   // four pixels of a patch row per thread
+  if (x4) {
     hipLaunchKernelGGL(patchify_bf16_x4_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, img, out, B, Hi, Wi, ph, pw);
     DGVIT_CHECK_LAUNCH("patchify_bf16");
     return DGVIT_OK;

@@ -378,9 +378,11 @@ int dgvit_soft_update(float* target, const float* source, long long n, float tau
  * Same GoT.forward (GoalFormer.py:156-171) with bf16 STORAGE for every GEMM operand (LayerNorm outputs, qkv, attention
  * output, MLP hidden, the four weight matrices of each block and the patch weight) and fp32 everywhere else (residual
  * stream, LayerNorm statistics, biases, softmax, accumulation on v_mfma_f32_32x32x16_bf16, RMSNorm, output).
- * bf16 values are raw 16-bit patterns (unsigned short).  Needs dim_head 64 and dim, mlp_dim, patch pixels % 8 == 0.
+ * bf16 values are raw 16-bit patterns (unsigned short).  Needs dim_head 64 and dim, mlp_dim % 8 == 0; any patch size (a patch area
+ * that is no multiple of 8 -- 14x14, 7x7, 3x5 -- is padded with zero columns to the next one inside the arena and the workspace, which
+ * the size queries account for; parameters and gradients keep their (dim, patch pixels) shapes).
  *   wpack: bf16 copies of the GEMM weights in one arena of dgvit_got_bf16_weight_elems elements
- *          [patch weight | per layer: to_qkv, to_out, fc1, fc2 and their transposes], refreshed with dgvit_got_pack_weights_bf16 whenever the
+ *          [patch weight, rows padded to a multiple of 8 | per layer: to_qkv, to_out, fc1, fc2 and their transposes], refreshed with dgvit_got_pack_weights_bf16 whenever the
  *          fp32 master parameters change; `params` is the fp32 table of dgvit_got_forward (biases, norms, pos_embedding).
  *   workspace: dgvit_got_bf16_workspace_bytes BYTES, 256-byte aligned.
  * -------------------------------------------------------------------------------------------- */

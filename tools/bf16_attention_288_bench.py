@@ -8,8 +8,8 @@
         stats table gives each form's per-launch time.  Device-event times are printed too (profiler on: indicative only).
     python tools/bf16_attention_288_bench.py encoder [--image 256 --patch 16 --batch 440]
         the ViT-B encoder (depth 12, dim 768, 12 heads, MLP 3072) in the bf16 configuration: forward (no grad) and forward + backward
-        in frames/s from device events, profiler off.  Prints one JSON line.  (ViT-B/14 has the same 257 tokens as 256 @ 16, but the
-        bf16 patch embedding takes patch areas that are multiples of 8 only.)
+        in frames/s from device events, profiler off.  Prints one JSON line.  (ViT-B/14, the same 257 tokens as 256 @ 16:
+        tools/bf16_patch14_bench.py.)
 """
 import argparse
 import json
