@@ -22,11 +22,11 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libdgvit_hip.so")
 LIB_DIAG = os.path.join(HERE, "libdgvit_hip_diag.so")   # the same sources with -DDGVIT_DIAG: knobs, stamps, experiments (tools/, A/B tests)
-SOURCES = ["gemm.hip", "norm.hip", "attention.hip", "attention_long.hip", "embed.hip", "conv.hip", "optim.hip", "profile.hip", "preprocess.hip", "gemm_bf16.hip",
+SOURCES = ["gemm.hip", "gemm_reduce.hip", "norm.hip", "attention.hip", "attention_long.hip", "embed.hip", "conv.hip", "optim.hip", "profile.hip", "preprocess.hip", "gemm_bf16.hip",
            "gemm_bf16_stream.hip", "attention_bf16.hip", "attention_maps.hip", "misc_bf16.hip", "heads.hip", "block.hip", "api.hip", "encoder.hip", "encoder_bf16.hip", "cnn_api.hip"]
 DIAG_ONLY_SOURCES = ["frame.hip", "diag_api.hip"]    # experiments and the knob entry points: not part of the product library
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_tiles.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "bf16.h"), os.path.join(CSRC, "small_mma.h"),
-           os.path.join(CSRC, "knobs.h"), os.path.join(CSRC, "schedule.h"), os.path.join(INCLUDE, "dgvit_hip.h"), os.path.join(INCLUDE, "dgvit_hip_diag.h")]
+           os.path.join(CSRC, "knobs.h"), os.path.join(CSRC, "schedule.h"), os.path.join(CSRC, "gemm_tile.h"), os.path.join(CSRC, "gemm_pipe.h"), os.path.join(INCLUDE, "dgvit_hip.h"), os.path.join(INCLUDE, "dgvit_hip_diag.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-fvisibility=hidden", "-I", INCLUDE, "-Rpass-analysis=kernel-resource-usage"]
 
@@ -72,8 +72,10 @@ def _compile(job):
     os.makedirs(os.path.dirname(obj), exist_ok=True)
     path = os.path.join(CSRC, src)
     r = subprocess.run(["hipcc", *FLAGS, *(["-DDGVIT_DIAG"] if diag else []), "-c", path, "-o", obj], capture_output=True, text=True)
-    other = "\n".join(l for l in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l and not re.match(r"^\s+\d* *\|", l)
-                      and "remarks generated" not in l and "remark generated" not in l)
+    mark, lines = "-Rpass-analysis=kernel-resource-usage", r.stderr.splitlines()
+    other = "\n".join(l for i, l in enumerate(lines) if mark not in l and not re.match(r"^\s+\d* *\|", l)
+                      and "remarks generated" not in l and "remark generated" not in l
+                      and not (l.startswith("In file included from") and mark in "".join(lines[i + 1:i + 2])))   # a remark on a kernel in a header
     if r.returncode != 0:
         sys.stderr.write(r.stderr)
         raise RuntimeError(f"hipcc failed on {src}")

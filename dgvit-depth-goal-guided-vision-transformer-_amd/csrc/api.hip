@@ -127,9 +127,10 @@ extern "C" int dgvit_gemm(int layout, int epilogue, const float* A, int lda, con
     return wgrad(A, lda, B, ldb, C, nullptr, M, N, K, scratch, scratch_floats, st);
   }
   DGVIT_CHECK_ARG(layout == GEMM_NT || layout == GEMM_NN, "gemm: bad layout %d", layout);
-  DGVIT_CHECK_ARG(epilogue >= EPI_STORE && epilogue <= EPI_DRELU, "gemm: bad epilogue %d", epilogue);
-  DGVIT_CHECK_ARG(epilogue != EPI_GELU2 || C2, "gemm: epilogue 1 needs C2");
-  DGVIT_CHECK_ARG((epilogue != EPI_DGELU && epilogue != EPI_DRELU) || aux, "gemm: epilogue needs aux");
+  DGVIT_CHECK_ARG((epilogue >= EPI_STORE && epilogue <= EPI_DRELU) || epilogue == EPI_GELU2D || epilogue == EPI_DMUL || epilogue == EPI_GELU,
+                  "gemm: bad epilogue %d", epilogue);
+  DGVIT_CHECK_ARG((epilogue != EPI_GELU2 && epilogue != EPI_GELU2D) || C2, "gemm: epilogue %d needs C2", epilogue);
+  DGVIT_CHECK_ARG((epilogue != EPI_DGELU && epilogue != EPI_DRELU && epilogue != EPI_DMUL) || aux, "gemm: epilogue needs aux");
   GemmParams p = gp(A, lda, B, ldb, C, ldc, M, N, K);
   p.bias = bias; p.res = res; p.ldr = ldr; p.C2 = C2; p.ldc2 = ldc2; p.aux = aux; p.ldaux = ldaux;
   const GemmSplitPlan pl = gemm_split_plan(layout, M, N, K);

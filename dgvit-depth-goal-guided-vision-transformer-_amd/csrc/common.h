@@ -25,6 +25,8 @@ int dgvit_set_error(int code, const char* fmt, ...);
     if (e_ != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "%s: %s", name, hipGetErrorString(e_)); \
   } while (0)
 
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }   // float4 accesses need it
+
 // Kernel attributes (the dynamic-LDS limit above 64 KB) are per DEVICE: a flag per device ordinal, set on the first launch on
 // that device (a process-wide `static bool` would leave a second GPU of a single-process host without the attribute).
 // Racing threads may both set the attribute: harmless, it is idempotent.

@@ -22,248 +22,14 @@
 // staging LDS so that every global access of the epilogue -- C, residual, GELU input/output -- is a
 // 16-byte-per-lane, 512-byte-per-row coalesced float4; bias / residual / GELU / GELU' / ReLU are applied
 // on the way out.  The weight-gradient form also sums its A tiles over k (= the bias gradient) for free.
+// In other files: the tile primitives (TileCfg, Fetch, frag / frag_mc, sched_pattern) in gemm_tile.h, the diagnostic-only pipelined
+// persistent kernel in gemm_pipe.h, the slab reductions that follow the split-K weight gradients in gemm_reduce.hip.
 #include <algorithm>
 
 #include "common.h"
-
-#define TRY_RG(expr)      \
-  do {                    \
-    int rc_ = (expr);     \
-    if (rc_) return rc_;  \
-  } while (0)
-
+#include "gemm_tile.h"
 
 namespace {
-
-// BM x BN output tile, BK-deep k-tiles, WVM x WVN waves (each owning a (BM/WVM) x (BN/WVN) block of 32x32 accumulators).
-// 2x2 waves everywhere: two-wave workgroups (1x2 / 2x1) measured 10-45 % slower and eight-wave ones (128x128 as 2x4,
-// 256x128x16 as 4x2) hit the same 83 % in-CU ceiling as 2x2 (tools/gemm_fill_probe.py, round 1)
-template <int BM_, int BN_, int BK_, int WVM_ = 2, int WVN_ = 2>
-struct TileCfg {
-  static constexpr int BM = BM_, BN = BN_, BK = BK_, WVM = WVM_, WVN = WVN_, NT = 64 * WVM_ * WVN_;
-  // workgroups per CU the two LDS stages allow (<= 32 KB each: 5, the occupancy the K = 256 shapes are tuned at); the register
-  // allocator is held to it, so an epilogue variant cannot silently cost a resident workgroup
-  static constexpr int LDS_BYTES = 2 * (BM_ + BN_) * (BK_ + 4) * 4;
-  static constexpr int MINB = LDS_BYTES * 5 <= 160 * 1024 ? 5 : 2;
-};
-
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  // Blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous chunk of the tile grid so
-  // that the column tiles sharing an A row-panel hit the same L2 (speed only, bijective for any n).
-  const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// ---- global -> register tile fetch ---------------------------------------------------------------
-// KC: tile is R rows x BK k (k contiguous in memory).  MC: tile is BK k-rows x R (row index contiguous).
-// VEC == 4: 16-byte buffer loads through a per-workgroup resource descriptor; rows/columns/k outside the
-// matrix are dropped by the hardware range check (offset >= num_records reads 0), so the fetch is
-// branch-free and can be scheduled among the MFMAs.  VEC == 1: scalar loads with explicit predicates
-// (odd leading dimensions / unaligned bases; small head and odd-patch GEMMs only).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#define DGVIT_OOB 0xFFFFFFF0u
-
-template <int R, int BK, bool KC, int VEC, int NT, bool GATHER = false>
-struct Fetch {
-  static_assert(!GATHER || (KC && VEC == 4), "the patch gather is a k-contiguous float4 fetch");
-  static_assert(R * BK / 4 % NT == 0, "tile must split evenly over the workgroup's threads");
-  static constexpr int NV = R * BK / 4 / NT;  // float4 slots per thread
-  static constexpr int PER_ROW = KC ? BK / 4 : R / 4;
-
-  // --- VEC == 4 ---------------------------------------------------------------------------------
-  struct Plan {
-    __amdgpu_buffer_rsrc_t rsrc;
-    unsigned off[NV];   // byte offset of slot i at the block's first k-tile
-    int kc[NV];         // KC: k offset of the slot inside a tile; MC: k row of the slot inside a tile
-    unsigned bad[NV];   // MC: all ones when the slot's columns lie outside the matrix (OR-ed into the offset: no branch), else 0
-    unsigned kstep;     // bytes to advance per k-tile
-    int g_wi, g_pw, g_inv, g_shift;   // GATHER: image row pitch, window-row floats, 2^shift / pw + 1, shift
-    int g_k0;                         // GATHER: first k of this workgroup's k-range (a k-slice of a split tile starts past 0)
-  };
-
-  // GATHER: A is never materialised.  Row m of the patch matrix starts at pixel (b, hy * ph, wx * xs) of the image; element k of
-  // the row is p1 = k / pw image rows further down and p2 = k % pw floats to the right (k / pw by multiply-shift; dgvit_api checks
-  // that it is exact for every k < K).  Non-overlapping patches (xs = pw) and the strided 5x5 windows of the NHWC convolutions
-  // (xs = stride * C, pw = KW * C) are the same arithmetic.  The descriptor covers the whole image buffer.
-  __device__ static __forceinline__ void plan_gather(Plan& pl, const GemmParams& p, int r0, int kbeg, int tid) {
-    pl.g_k0 = kbeg;
-    long long bytes = p.g_img_floats * 4;
-    if (bytes > 0x7FFFFFFFll) bytes = 0x7FFFFFFFll;
-    pl.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.g_img), 0, (int)bytes, 0x00020000);
-    pl.kstep = 0;
-    pl.g_wi = p.g_wi; pl.g_pw = p.g_pw; pl.g_inv = p.g_inv; pl.g_shift = p.g_shift ? p.g_shift : 16;
-    const int xs = p.g_xs ? p.g_xs : p.g_pw;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int f = tid + i * NT;
-      const int a = f / PER_ROW, c = (f % PER_ROW) * 4;
-      const int m = r0 + a;
-      const int b = m / p.g_P, pi = m - b * p.g_P, hy = pi / p.g_gw, wx = pi - hy * p.g_gw;
-      pl.off[i] = ((unsigned)b * (unsigned)p.g_hw + (unsigned)(hy * p.g_ph) * (unsigned)p.g_wi + (unsigned)(wx * xs)) * 4u;
-      pl.kc[i] = c;
-      pl.bad[i] = m < p.M ? 0u : 0xFFFFFFFFu;
-    }
-  }
-
-  __device__ static __forceinline__ void plan(Plan& pl, const float* base, int ld, int r0, int rmax, int kbeg, int ktotal,
-                                              int tid) {
-    // resource base = first element this workgroup can touch; num_records = bytes from there to the end of the matrix
-    long long first, last;
-    if (KC) {
-      first = (long long)r0 * ld + kbeg;
-      last = (long long)(rmax - 1) * ld + ktotal;       // one past the last valid element
-    } else {
-      first = (long long)kbeg * ld + r0;
-      last = (long long)(ktotal - 1) * ld + rmax;
-    }
-    long long bytes = (last - first) * 4;
-    if (bytes > 0x7FFFFFFFll) bytes = 0x7FFFFFFFll;
-    if (bytes < 0) bytes = 0;
-    pl.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + first), 0, (int)bytes, 0x00020000);
-    pl.kstep = KC ? BK * 4u : (unsigned)BK * (unsigned)ld * 4u;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int f = tid + i * NT;
-      const int a = f / PER_ROW, c = (f % PER_ROW) * 4;
-      if (KC) {
-        pl.off[i] = ((unsigned)a * (unsigned)ld + (unsigned)c) * 4u;
-        pl.kc[i] = c;
-        pl.bad[i] = 0u;  // rows past rmax fall outside num_records
-      } else {
-        pl.off[i] = ((unsigned)a * (unsigned)ld + (unsigned)c) * 4u;
-        pl.kc[i] = a;
-        pl.bad[i] = r0 + c < rmax ? 0u : 0xFFFFFFFFu;
-      }
-    }
-  }
-
-  // fetch k-tile number `t` (k0 = kbeg + t*BK); klim = kend - kbeg
-  __device__ static __forceinline__ void run4(float4 (&reg)[NV], const Plan& pl, int t, int klim) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      unsigned at;
-      if constexpr (GATHER) {
-        const unsigned k = (unsigned)(pl.g_k0 + t * BK + pl.kc[i]), p1 = (k * (unsigned)pl.g_inv) >> pl.g_shift, p2 = k - p1 * (unsigned)pl.g_pw;
-        at = (pl.off[i] + (p1 * (unsigned)pl.g_wi + p2) * 4u) | pl.bad[i];
-      } else {
-        at = (pl.off[i] + (unsigned)t * pl.kstep) | pl.bad[i];   // num_records <= 0x7FFFFFFF: all ones is out of range
-      }
-      const unsigned o = t * BK + pl.kc[i] < klim ? at : DGVIT_OOB;
-      reg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(pl.rsrc, o, 0, 0));
-    }
-  }
-
-  // --- VEC == 1 ---------------------------------------------------------------------------------
-  __device__ static __forceinline__ void run(float4 (&reg)[NV], const float* __restrict__ base, int ld, int r0,
-                                             int rmax, int k0, int kend, int tid) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int f = tid + i * NT;
-      const int a = f / PER_ROW, c = (f % PER_ROW) * 4;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (KC) {
-        const int row = r0 + a, k = k0 + c;
-        if (row < rmax) {
-          const float* src = base + (long long)row * ld + k;
-          if (k + 0 < kend) v.x = src[0];
-          if (k + 1 < kend) v.y = src[1];
-          if (k + 2 < kend) v.z = src[2];
-          if (k + 3 < kend) v.w = src[3];
-        }
-      } else {
-        const int k = k0 + a, col = r0 + c;
-        if (k < kend) {
-          const float* src = base + (long long)k * ld + col;
-          if (col + 0 < rmax) v.x = src[0];
-          if (col + 1 < rmax) v.y = src[1];
-          if (col + 2 < rmax) v.z = src[2];
-          if (col + 3 < rmax) v.w = src[3];
-        }
-      }
-      reg[i] = v;
-    }
-  }
-
-  __device__ static __forceinline__ void stash(const float4 (&reg)[NV], float* lds, int tid) {
-    constexpr int STRIDE = KC ? BK + 4 : R + 4;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int f = tid + i * NT;
-      const int a = f / PER_ROW, c = (f % PER_ROW) * 4;
-      *reinterpret_cast<float4*>(lds + a * STRIDE + c) = reg[i];
-    }
-  }
-};
-
-// ---- LDS -> MFMA operand fragments for one 8-deep k-group -----------------------------------------
-template <int R, int BK, bool KC>
-__device__ __forceinline__ void frag(float (&out)[4], const float* lds, int row, int g, int h) {
-  if (KC) {
-    const float4 v = *reinterpret_cast<const float4*>(lds + row * (BK + 4) + 8 * g + 4 * h);
-    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-  } else {
-    const float* p = lds + (8 * g + 4 * h) * (R + 4) + row;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) out[s] = p[s * (R + 4)];
-  }
-}
-
-// m/n-contiguous operand, the wave's NTILE 32-row MFMA tiles INTERLEAVED: lane i of tile t owns row base + NTILE * i + t, so the
-// NTILE values a lane needs from one k-row are adjacent in LDS and come in with one ds_read_b64 / b128 (256 B/clk) instead of NTILE
-// ds_read_b32 (128 B/clk).  The permutation of the tile's rows is undone where the accumulators are written out.
-template <int R, int NTILE>
-__device__ __forceinline__ void frag_mc(float (&out)[NTILE][4], const float* lds, int base, int li, int g, int h) {
-  typedef float vec_t __attribute__((ext_vector_type(NTILE == 1 ? 1 : NTILE == 2 ? 2 : 4)));
-  static_assert(NTILE == 1 || NTILE == 2 || NTILE == 4, "frag_mc: tiles per wave");
-  const float* p = lds + (8 * g + 4 * h) * (R + 4) + base + NTILE * li;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    if constexpr (NTILE == 1) {
-      out[0][s] = p[s * (R + 4)];
-    } else {
-      // volatile: keeps LLVM from pairing two of these into one ds_read2_b64, which runs at half the rate of two ds_read_b64
-      typedef __attribute__((address_space(3))) const volatile vec_t lds_vec_t;
-      const vec_t v = *(lds_vec_t*)(p + s * (R + 4));
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) out[t][s] = v[t];
-    }
-  }
-}
-
-// ---- instruction-order hints for the pipelined main loop -----------------------------------------------
-// One k-tile = NG k-groups of MF MFMAs.  The LDS writes of the next tile (NW ds_write_b128) and the fetch of
-// the tile after it (NW buffer loads) are spread one per MFMA over the first k-group; the fragments of
-// k-group g+1 are read while k-group g's MFMAs run.  (LLVM SchedGroupMask: MFMA 0x8, VMEM read 0x20,
-// DS read 0x100, DS write 0x200.)
-#define SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-constexpr int cdiv_c(int a, int b) { return (a + b - 1) / b; }
-// m-th of H MFMAs, each followed by its share of NI instructions of kind MASK
-template <int m, int H, int NI, int MASK>
-__device__ __forceinline__ void spread() {
-  if constexpr (m < H) {
-    SGB(0x8, 1);
-    constexpr int c = cdiv_c((m + 1) * NI, H) - cdiv_c(m * NI, H);
-    if constexpr (c > 0) SGB(MASK, c);
-    spread<m + 1, H, NI, MASK>();
-  }
-}
-template <int MF, int NW, int RPG, int NG>
-__device__ __forceinline__ void sched_pattern() {
-  static_assert(MF >= 2 && MF % 2 == 0, "sched_pattern: MFMAs per k-group");
-  SGB(0x100, RPG);                       // fragments of k-group 0
-  spread<0, MF / 2, NW, 0x200>();        // first half of k-group 0: LDS writes of the next tile
-  if constexpr (NG > 1) SGB(0x100, RPG); // fragments of k-group 1
-  spread<0, MF / 2, NW, 0x20>();         // second half: global fetch of the tile after next
-  if constexpr (NG > 1) { if constexpr (NG > 2) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 2) { if constexpr (NG > 3) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 3) { if constexpr (NG > 4) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 4) { if constexpr (NG > 5) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 5) { if constexpr (NG > 6) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 6) { if constexpr (NG > 7) SGB(0x100, RPG); SGB(0x8, MF); }
-  if constexpr (NG > 7) { SGB(0x8, MF); }
-}
-#undef SGB
 
 // diagnostic stamps (dgvit_set_gemm_stamps): wave 0 of every workgroup records the shader clock at four points and where it ran
 __device__ __forceinline__ void stamp(const GemmParams& p, int slot, int tid) {
@@ -950,357 +716,6 @@ __global__ void __launch_bounds__(T::NT, T::MINB) gemm_f32_kernel(const GemmPara
   }
 }
 
-// out1[0..n1) , out2[0..n-n1)  <-  sum over slabs of slab[z][0..n), for up to DGVIT_REDUCE_JOBS independent jobs in ONE launch
-// (a transformer layer's four split-K weight gradients + its two LayerNorm parameter-gradient partials).
-// 256 threads = CW float4 columns x GS slab groups (CW * GS = 256; jobs with few columns and many slabs -- LayerNorm partials --
-// take CW = 16, GS = 16): group y sums slabs y, y+GS, y+2GS, ... with 4 loads in flight, then the GS partial sums are combined
-// through LDS in a fixed (tree) order: deterministic for a given (nslab, GS).
-__global__ void __launch_bounds__(256) reduce_group_kernel(const ReduceGroup g) {
-  __shared__ float4 part[256];
-  int j = 0;
-#pragma unroll
-  for (int t = 1; t < DGVIT_REDUCE_JOBS; ++t)
-    if (t < g.njobs && (int)blockIdx.x >= g.first_block[t]) j = t;
-  const ReduceJob job = g.job[j];
-  const int cwl = job.cw_log, CW = 1 << cwl, GS = 256 >> cwl;
-  const int tx = threadIdx.x & (CW - 1), ty = threadIdx.x >> cwl;
-  const long long i = (long long)((int)blockIdx.x - g.first_block[j]) * CW + tx;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (i < job.n4) {
-    const float4* src = reinterpret_cast<const float4*>(job.slabs) + i;
-    const long long st4 = job.stride4;
-    int z = ty;
-    for (; z + 3 * GS < job.nslab; z += 4 * GS) {
-      const float4 a = src[(z + 0 * GS) * st4], b = src[(z + 1 * GS) * st4], c = src[(z + 2 * GS) * st4], d = src[(z + 3 * GS) * st4];
-      s.x += (a.x + b.x) + (c.x + d.x);
-      s.y += (a.y + b.y) + (c.y + d.y);
-      s.z += (a.z + b.z) + (c.z + d.z);
-      s.w += (a.w + b.w) + (c.w + d.w);
-    }
-    for (; z < job.nslab; z += GS) {
-      const float4 a = src[z * st4];
-      s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
-    }
-  }
-  part[ty * CW + tx] = s;
-  __syncthreads();
-  for (int half = GS >> 1; half >= 1; half >>= 1) {   // fixed pairing: (y, y + half)
-    if (ty < half) {
-      const float4 a = part[ty * CW + tx], b = part[(ty + half) * CW + tx];
-      part[ty * CW + tx] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-    __syncthreads();
-  }
-  if (ty == 0 && i < job.n4) {
-    const float4 r = part[tx];
-    if (i < job.n14) reinterpret_cast<float4*>(job.out1)[i] = r;
-    else reinterpret_cast<float4*>(job.out2)[i - job.n14] = r;
-  }
-}
-
-__global__ void __launch_bounds__(256) reduce_slabs_scalar_kernel(const float* __restrict__ slabs, float* __restrict__ out1,
-                                                                  float* __restrict__ out2, long long n, long long n1, int nslab,
-                                                                  long long stride) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int z = 0; z < nslab; ++z) s += slabs[z * stride + i];
-  if (i < n1) out1[i] = s;
-  else out2[i - n1] = s;
-}
-
-#ifdef DGVIT_DIAG   // measured 4-15 % slower than the per-tile kernel: kept for tools/ and its equality tests only
-// ---- pipelined persistent variant: one continuous k-tile stream per workgroup, a tile's stores under the next tile's MFMAs -----
-// What the per-tile kernel loses at the K = 256 shapes (45 % of the step's GEMM time) is its epilogue: with the stores skipped
-// (diagnostic bit of dgvit_set_gemm_diagnostics) QKV / fc1 / fc2-dgrad run at 133-135 TFLOP/s instead of 101-107
-// (profiles/r02_c_gemm_no_epilogue_bound.txt).  Shortening the epilogue did not help (the time reappears as waiting elsewhere), and
-// a persistent tile loop that keeps epilogue and main loop as separate phases is slower still: all workgroups of the chip fall into
-// step and store at the same moment (profiles/r02_c_gemm_persistent_kernel_negative_result.txt).  So here there are no phases:
-//   * the workgroup walks over its tiles (tile id += gridDim.x, same XCD-contiguous order) with ONE k-tile pipeline: iteration kt
-//     of a tile fetches k-tile kt + 2 - of the NEXT tile for the last two iterations - so there is no prologue after the first;
-//   * the finished tile's accumulators are copied to a second register set and leave during the next tile's main loop, one
-//     accumulator row piece (TN values per lane and MFMA row tile) per iteration: buffer stores straight from registers (a lane's
-//     32-bit (NT) or 64-bit (NN) pieces, 128 / 256 contiguous bytes per half-wave; rows past M dropped by the descriptor's range
-//     check, columns past N and the not-yet-existing previous tile of the first round by an out-of-range offset - no branch);
-//   * side inputs (residual / activation-gradient operand) of piece r are requested two iterations before they are used, the
-//     first two pieces during the tile's own last two iterations.
-// The k-tile count is a compile-time constant (NK = 16: K = 256 with 16-deep and K = 512 with 32-deep k-tiles) and the main loop is
-// fully unrolled, which is what gives every iteration ITS accumulator registers to drain.  Memory operations of one iteration, in
-// program order: operand fetch, side-input request, stores - vmcnt retires in order on gfx9, so every wait the compiler needs is for
-// something older than the stores around it.  64 accumulator registers: 4 workgroups per CU instead of 5.
-template <class T, int LAYOUT, int EPI, int NK>
-__global__ void __launch_bounds__(T::NT, T::LDS_BYTES * 4 <= 160 * 1024 ? 4 : 2) gemm_f32_pipe_kernel(const GemmParams p) {
-  constexpr int BM = T::BM, BN = T::BN, BK = T::BK, NT = T::NT;
-  static_assert(LAYOUT == GEMM_NT || LAYOUT == GEMM_NN, "pipelined GEMM: forward / data-gradient forms");
-  static_assert(EPI != EPI_SPLITK && NK % 2 == 0 && NK >= 4, "pipelined GEMM: complete-K tiles, even k-tile count");
-  constexpr bool BKC = LAYOUT == GEMM_NT;
-  constexpr int WM = BM / T::WVM, WN = BN / T::WVN, TM = WM / 32, TN = WN / 32;
-  static_assert(16 % NK == 0 || NK % 16 == 0, "pipelined GEMM: accumulator rows per iteration");
-  constexpr int RPI = NK >= 16 ? 1 : 16 / NK;     // accumulator rows (r) drained per iteration
-  constexpr int DRAIN_EVERY = NK >= 16 ? NK / 16 : 1;
-  constexpr int A_TILE = BM * (BK + 4);
-  constexpr int B_TILE = BKC ? BN * (BK + 4) : BK * (BN + 4);
-  constexpr int STAGE = A_TILE + B_TILE;
-  constexpr int CW = BKC ? 1 : TN;            // floats per store: NT one column per MFMA tile, NN the lane's TN adjacent columns
-  static_assert(CW == 1 || CW == 2, "pipelined GEMM: one or two adjacent columns per lane");
-  constexpr bool HAS_SIDE = EPI == EPI_STORE || EPI == EPI_DGELU || EPI == EPI_DRELU;
-  using FA = Fetch<BM, BK, true, 4, NT>;
-  using FB = Fetch<BN, BK, BKC, 4, NT>;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int wm = wave / T::WVN, wn = wave % T::WVN;
-  const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM, ntiles = tiles_m * tiles_n;
-  constexpr int klim = NK * BK;               // == p.K (checked at launch)
-
-  auto load_frags = [&](float (&fa)[TM][4], float (&fb)[TN][4], const float* la, const float* lb, int g) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) frag<BM, BK, true>(fa[i], la, wm * WM + i * 32 + li, g, h);
-    if constexpr (BKC) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) frag<BN, BK, true>(fb[j], lb, wn * WN + j * 32 + li, g, h);
-    } else {
-      frag_mc<BN, TN>(fb, lb, wn * WN, li, g, h);
-    }
-  };
-  int coln[TN];   // this lane's column(s) inside a tile
-#pragma unroll
-  for (int j = 0; j < TN; ++j) coln[j] = wn * WN + (BKC ? j * 32 + li : li * TN + j);
-  const bool use_side = HAS_SIDE && (EPI == EPI_STORE ? p.res != nullptr : true);
-  const float* side_base = EPI == EPI_STORE ? p.res : p.aux;
-  const int sld = EPI == EPI_STORE ? p.ldr : p.ldaux;
-
-  // window of one tile in a row-major matrix: tile origin .. end of the matrix (rows past M fall outside, columns are predicated)
-  auto tile_rsrc = [&](const float* base, int ld, int m0, int n0) {
-    long long bytes = ((long long)(p.M - 1 - m0) * ld + (p.N - n0)) * 4;
-    if (bytes > 0x7FFFFFFFll) bytes = 0x7FFFFFFFll;
-    if (bytes < 0) bytes = 0;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (long long)m0 * ld + n0), 0, (int)bytes, 0x00020000);
-  };
-  // byte offset of accumulator element r of MFMA tile (i, j) inside that window (all of it in the VGPR operand: the scalar offset of
-  // a buffer instruction is not range-checked); `lanepart` is DGVIT_OOB for a lane that must not touch memory
-  auto elem_off = [&](unsigned lanepart, int i, int r, int ld) -> unsigned {
-    const unsigned rowpart = (unsigned)((wm * WM + i * 32 + (r & 3) + 8 * (r >> 2)) * ld * 4);   // uniform
-    return lanepart == DGVIT_OOB ? DGVIT_OOB : rowpart + lanepart;
-  };
-
-  int id = blockIdx.x;
-  int tile = xcd_remap(id, ntiles);
-  int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
-  typename FA::Plan pa, pan;
-  typename FB::Plan pb, pbn;
-  float4 ra[FA::NV], rb[FB::NV];
-  FA::plan(pa, p.A, p.lda, m0, p.M, 0, p.K, tid);
-  FB::plan(pb, p.B, p.ldb, n0, p.N, 0, p.K, tid);
-  {   // the only prologue: k-tiles 0 and 1 of the first tile
-    float4 ra0[FA::NV], rb0[FB::NV];
-    FA::run4(ra0, pa, 0, klim);
-    FB::run4(rb0, pb, 0, klim);
-    FA::run4(ra, pa, 1, klim);
-    FB::run4(rb, pb, 1, klim);
-    FA::stash(ra0, smem, tid);
-    FB::stash(rb0, smem + A_TILE, tid);
-  }
-  __syncthreads();
-  stamp(p, 0, tid);
-
-  // the tile that is leaving: accumulators, bias, lane offsets (DGVIT_OOB until a first tile has finished), descriptors
-  f32x16 prev[TM][TN];
-  float bias_p[TN];
-  unsigned lane_c[TN], lane_s[TN];   // lane part of the offsets into C (and C2) / the side input, or DGVIT_OOB
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    bias_p[j] = 0.f;
-    lane_c[j] = DGVIT_OOB;
-    lane_s[j] = DGVIT_OOB;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) prev[i][j][r] = 0.f;
-  }
-  __amdgpu_buffer_rsrc_t c_rs = tile_rsrc(p.C, p.ldc, m0, n0), c2_rs = c_rs, s_rs = c_rs;
-  float sd[16][TM][TN];   // side inputs of the leaving tile, by accumulator row (live from request to use only)
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) sd[r][i][j] = 0.f;
-
-  // request the side inputs of accumulator row r of the tile at (sm0, sn0): descriptor `rs`, lane parts `ls`
-  auto side_request = [&](int r, const __amdgpu_buffer_rsrc_t& rs, const unsigned (&ls)[TN]) {
-    if constexpr (HAS_SIDE) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          sd[r][i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, elem_off(ls[j], i, r, sld), 0, 0));
-    }
-  };
-  // store accumulator row r of the leaving tile
-  auto drain_row = [&](int r) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      float v[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        v[j] = prev[i][j][r];
-        if (EPI == EPI_STORE) {
-          if (use_side) v[j] += sd[r][i][j];          // residual first, then bias: the order of gemm_f32_kernel
-          v[j] += bias_p[j];
-        } else if (EPI == EPI_GELU2) {
-          v[j] += bias_p[j];
-        } else if (EPI == EPI_RELU) {
-          v[j] = fmaxf(v[j] + bias_p[j], 0.f);
-        } else if (EPI == EPI_DGELU) {
-          v[j] *= gelu_erf_grad(sd[r][i][j]);
-        } else if (EPI == EPI_DRELU) {
-          v[j] = sd[r][i][j] > 0.f ? v[j] : 0.f;
-        }
-      }
-      if constexpr (CW == 1) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), c_rs, elem_off(lane_c[j], i, r, p.ldc), 0, 0);
-          if (EPI == EPI_GELU2)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gelu_erf(v[j])), c2_rs, elem_off(lane_c[j], i, r, p.ldc), 0, 0);
-        }
-      } else {
-        u32x2 w;
-        w[0] = __builtin_bit_cast(unsigned, v[0]);
-        w[1] = __builtin_bit_cast(unsigned, v[1]);
-        __builtin_amdgcn_raw_buffer_store_b64(w, c_rs, elem_off(lane_c[0], i, r, p.ldc), 0, 0);
-        if (EPI == EPI_GELU2) {
-          w[0] = __builtin_bit_cast(unsigned, gelu_erf(v[0]));
-          w[1] = __builtin_bit_cast(unsigned, gelu_erf(v[1]));
-          __builtin_amdgcn_raw_buffer_store_b64(w, c2_rs, elem_off(lane_c[0], i, r, p.ldc), 0, 0);
-        }
-      }
-    }
-  };
-
-  while (true) {
-    // ---- tile (m0, n0): its plans are pa / pb and its first two k-tiles are on their way (stage 0 in LDS, k-tile 1 in ra / rb)
-    const int nid = id + (int)gridDim.x;
-    const bool more = nid < ntiles;
-    const int ntile = more ? xcd_remap(nid, ntiles) : 0;
-    const int nm0 = (ntile / tiles_n) * BM, nn0 = (ntile % tiles_n) * BN;
-    FA::plan(pan, p.A, p.lda, nm0, more ? p.M : 0, 0, p.K, tid);      // no next tile: an empty window, the fetches read 0
-    FB::plan(pbn, p.B, p.ldb, nn0, more ? p.N : 0, 0, p.K, tid);
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    float bias_c[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bias_c[j] = 0.f;
-    if ((EPI == EPI_STORE || EPI == EPI_GELU2 || EPI == EPI_RELU) && p.bias) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bias_c[j] = p.bias[min(n0 + coln[j], p.N - 1)];
-    }
-    // this tile's own output window and lane offsets (used for its first side requests now, for its stores during the next tile)
-    const __amdgpu_buffer_rsrc_t cur_c = tile_rsrc(p.C, p.ldc, m0, n0);
-    __amdgpu_buffer_rsrc_t cur_s = cur_c;
-    if (HAS_SIDE && use_side) cur_s = tile_rsrc(side_base, sld, m0, n0);
-    unsigned cur_lane_c[TN], cur_lane_s[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const bool ok = n0 + coln[j] < p.N;
-      cur_lane_c[j] = ok ? (unsigned)((4 * h * p.ldc + coln[j]) * 4) : DGVIT_OOB;
-      cur_lane_s[j] = (ok && use_side) ? (unsigned)((4 * h * sld + coln[j]) * 4) : DGVIT_OOB;
-    }
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt) {
-      const float* la = smem + (kt & 1) * STAGE;
-      const float* lb = la + A_TILE;
-      float* wa = smem + ((kt + 1) & 1) * STAGE;
-      float fa[2][TM][4], fb[2][TN][4];
-      load_frags(fa[0], fb[0], la, lb, 0);
-      FA::stash(ra, wa, tid);
-      FB::stash(rb, wa + A_TILE, tid);
-      if (kt + 2 < NK) {
-        FA::run4(ra, pa, kt + 2, klim);
-        FB::run4(rb, pb, kt + 2, klim);
-      } else {   // the stream runs on into the next tile
-        FA::run4(ra, pan, kt + 2 - NK, klim);
-        FB::run4(rb, pbn, kt + 2 - NK, klim);
-      }
-      // side inputs: rows of the leaving tile two drain steps ahead; its first two rows were requested by its own last iterations
-      if constexpr (HAS_SIDE) {
-        if (kt % DRAIN_EVERY == 0) {
-#pragma unroll
-          for (int q = 0; q < RPI; ++q) {
-            const int r = (kt / DRAIN_EVERY) * RPI + q + 2 * RPI;
-            if (r < 16) side_request(r, s_rs, lane_s);
-          }
-        }
-      }
-      if (kt % DRAIN_EVERY == 0) {
-#pragma unroll
-        for (int q = 0; q < RPI; ++q) drain_row((kt / DRAIN_EVERY) * RPI + q);
-      }
-      if constexpr (HAS_SIDE) {
-        if (kt >= NK - 2 * DRAIN_EVERY && kt % DRAIN_EVERY == 0) {   // ... of THIS tile, for its first two drain steps in the next one
-#pragma unroll
-          for (int q = 0; q < RPI; ++q) side_request(((kt - (NK - 2 * DRAIN_EVERY)) / DRAIN_EVERY) * RPI + q, cur_s, cur_lane_s);
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < BK / 8; ++g) {
-        if (g + 1 < BK / 8) load_frags(fa[(g + 1) & 1], fb[(g + 1) & 1], la, lb, g + 1);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][s4], fb[g & 1][j][s4], acc[i][j], 0, 0, 0);
-      }
-      // (no sched_group_barrier pattern here: with it the side-input variants spill 230-270 registers and every variant measured
-      //  slower; and without a sched_barrier per iteration the group solver does not finish on the unrolled body)
-      __syncthreads();
-    }
-    // ---- the tile becomes the leaving one
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) prev[i][j] = acc[i][j];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      bias_p[j] = bias_c[j];
-      lane_c[j] = cur_lane_c[j];
-      lane_s[j] = cur_lane_s[j];
-    }
-    c_rs = cur_c;
-    s_rs = cur_s;
-    if (EPI == EPI_GELU2) c2_rs = tile_rsrc(p.C2, p.ldc2, m0, n0);
-    if (!more) break;
-    id = nid;
-    m0 = nm0;
-    n0 = nn0;
-    pa = pan;
-    pb = pbn;
-  }
-  stamp(p, 2, tid);
-  // ---- the last tile leaves without a main loop to hide under
-  if constexpr (HAS_SIDE) {
-#pragma unroll
-    for (int r = 2 * RPI; r < 16; ++r) side_request(r, s_rs, lane_s);
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) drain_row(r);
-  stamp(p, 3, tid);
-  if (DIAG_STAMPS(p)) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(p, 7, tid);
-  }
-}
-
-#endif   // DGVIT_DIAG
 // ---- in-launch split-K policy -------------------------------------------------------------------------------------------
 // (a) few tiles, long K (small batches: T = 65 ... 2080 rows against K = 2048): every tile is cut so that the grid fills the chip;
 // (b) a big grid whose last partial round would leave most CUs idle (tiles mod 256 <= 128: measured at 25600 x 256 x 2048,
@@ -1337,55 +752,11 @@ inline GemmSplitPlan split_plan(int M, int N, int K, int BM, int BN, int BK, int
   return pl;
 }
 
-#ifdef DGVIT_DIAG
-template <class T, int LAYOUT, int EPI>
-int launch_persistent(const GemmParams& p, hipStream_t stream, bool* taken) {
-  *taken = false;
-  constexpr int NK = 16;   // k-tiles per output tile the pipelined kernel is built for: K = 256 at BK = 16, K = 512 at BK = 32
-  // built for the two tiles the automatic choice uses in these forms (every instantiation is a fully unrolled 16-iteration loop)
-  constexpr bool TILE_OK = (T::BM == 64 && T::BN == 128 && T::BK == 16) || (T::BM == 64 && T::BN == 64 && T::BK == 32);
-  // (the pipelined kernel knows the row-major epilogues only: EPI_UNPATCH never takes it)
-  if constexpr ((LAYOUT == GEMM_NT || LAYOUT == GEMM_NN) && EPI != EPI_SPLITK && EPI != EPI_UNPATCH && TILE_OK) {
-    constexpr int BM = T::BM, BN = T::BN, BK = T::BK;
-    if (p.K != NK * BK) return DGVIT_OK;
-    constexpr size_t lds = T::LDS_BYTES;
-    auto kern = gemm_f32_pipe_kernel<T, LAYOUT, EPI, NK>;
-    static int slots = 0;
-    if (!slots) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      int per_cu = 0;
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T::NT, lds);
-      if (e != hipSuccess || per_cu < 1) return dgvit_set_error(DGVIT_ERR_HIP, "gemm: occupancy query: %s", hipGetErrorString(e));
-      slots = 256 * per_cu;
-    }
-    const long long tiles = (long long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    if (g_gemm_persist == 1 && tiles < 2ll * slots) return DGVIT_OK;     // few tiles per slot: the per-tile kernel (and its tail split)
-    if (tiles >= (1ll << 31)) return DGVIT_OK;
-    GemmParams q = p;
-    q.stamps = g_gemm_stamps;
-    q.stamp_capacity = g_gemm_stamp_capacity;
-    // equal shares: rounds = ceil(tiles / slots) tiles per workgroup, as few workgroups as that needs (a multiple of 8 for the XCD order)
-    long long grid = slots;
-    if (g_gemm_persist_grid > 0) {
-      grid = g_gemm_persist_grid;
-    } else if (tiles > slots) {
-      const long long rounds = (tiles + slots - 1) / slots;
-      grid = std::min<long long>(slots, ((tiles + rounds - 1) / rounds + 7) / 8 * 8);
-    }
-    grid = std::min<long long>(grid, tiles);
-    const int slot = profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T::NT), lds, stream, q);
-    profile_end(slot, stream);
-    DGVIT_CHECK_LAUNCH("gemm_f32_pipe_kernel");
-    ++g_gemm_persist_launches;
-    *taken = true;
-  }
-  return DGVIT_OK;
-}
-#endif   // DGVIT_DIAG
+}  // namespace
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+#include "gemm_pipe.h"   // diagnostic build: gemm_f32_pipe_kernel and launch_persistent; empty in the product
+
+namespace {
 
 // the tallest / widest tile of DGVIT_TILES: gemm_f32's leading-dimension checks bound a tile's 32-bit row offsets with it
 #define DGVIT_MAX_TILE_ROWS 128
@@ -1433,8 +804,9 @@ int launch(const GemmParams& p0, int nsplit, hipStream_t stream) {
   if constexpr (VEC == 4 && !GATHER && EPI != EPI_SPLITK && EPI != EPI_UNPATCH && LAYOUT != GEMM_TN) {
     // whole tiles only, vector epilogue, plain row mapping: the persistent kernel (tile loop in the workgroup, next tile's fetch
     // under the epilogue) when a resident slot gets several tiles
+    constexpr bool TWO_OUT = EPI == EPI_GELU2 || EPI == EPI_GELU2D;   // as in the kernel: C2 is addressed with C's stride
     if (g_gemm_persist && (p.nsplit == 1 || g_gemm_persist == 2) && nsplit == 1 && p.evec && p.c_rgrp == 0 && p.res_mod == 0 &&
-        (EPI != EPI_GELU2 || p.ldc2 == p.ldc) && g_gemm_lds_pad == 0 && !p.ln_y) {
+        (!TWO_OUT || p.ldc2 == p.ldc) && g_gemm_lds_pad == 0 && !p.ln_y) {
       bool taken = false;
       const int rc = launch_persistent<T, LAYOUT, EPI>(p0, stream, &taken);
       if (rc != DGVIT_OK || taken) return rc;
@@ -1567,56 +939,4 @@ int gemm_f32(int layout, int epi, const GemmParams& p, int nsplit, hipStream_t s
   CASE(GEMM_TN, EPI_SPLITK)
 #undef CASE
   return dgvit_set_error(DGVIT_ERR_ARG, "gemm: unsupported layout/epilogue %d/%d", layout, epi);
-}
-
-// ---- grouped deterministic reductions ----------------------------------------------------------------------------------
-void reduce_group_init(ReduceGroup& g) { g.njobs = 0; g.first_block[0] = 0; }
-
-// launch every queued job as ONE kernel (no-op when empty)
-int reduce_group_flush(ReduceGroup& g, hipStream_t stream) {
-  if (g.njobs == 0) return DGVIT_OK;
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-  hipLaunchKernelGGL(reduce_group_kernel, dim3((unsigned)g.first_block[g.njobs]), dim3(256), 0, stream, g);
-  profile_end(slot, stream);
-  g.njobs = 0;
-  DGVIT_CHECK_LAUNCH("reduce_group");
-  return DGVIT_OK;
-}
-
-// queue: out1 gets the first n1 sums, out2 (may be null when n1 == n) the remaining n - n1, of nslab slabs slab_stride floats apart.
-// Jobs that cannot take the float4 path (odd sizes / alignment: tiny head Linears) run at once on the scalar kernel.
-int reduce_group_add(ReduceGroup& g, const float* slabs, float* out1, long long n1, float* out2, long long n, int nslab,
-                     long long slab_stride, hipStream_t stream) {
-  DGVIT_CHECK_ARG(slabs && out1 && n > 0 && n1 > 0 && n1 <= n && nslab >= 1 && (n1 == n || out2), "reduce_slabs: bad arguments");
-  if (!(n % 4 == 0 && n1 % 4 == 0 && slab_stride % 4 == 0 && al16(slabs) && al16(out1) && (n1 == n || al16(out2)))) {
-    const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-    hipLaunchKernelGGL(reduce_slabs_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, slabs, out1, out2, n, n1,
-                       nslab, slab_stride);
-    profile_end(slot, stream);
-    DGVIT_CHECK_LAUNCH("reduce_slabs");
-    return DGVIT_OK;
-  }
-  if (g.njobs == DGVIT_REDUCE_JOBS) TRY_RG(reduce_group_flush(g, stream));
-  ReduceJob& job = g.job[g.njobs];
-  job.slabs = slabs; job.out1 = out1; job.out2 = out2;
-  job.n4 = n / 4; job.n14 = n1 / 4; job.nslab = nslab; job.stride4 = slab_stride / 4;
-  job.cw_log = (job.n4 <= 1024 && nslab >= 64) ? 4 : 6;   // few columns, many slabs: 16 slab groups per block
-  const long long blocks = (job.n4 + (1 << job.cw_log) - 1) >> job.cw_log;
-  DGVIT_CHECK_ARG(blocks + g.first_block[g.njobs] < (1ll << 30), "reduce_slabs: too many blocks");
-  g.first_block[g.njobs + 1] = g.first_block[g.njobs] + (int)blocks;
-  ++g.njobs;
-  return DGVIT_OK;
-}
-
-// out1 gets the first n1 sums, out2 (may be null when n1 == n) the remaining n - n1
-int reduce_slabs2(const float* slabs, float* out1, long long n1, float* out2, long long n, int nslab, long long slab_stride,
-                  hipStream_t stream) {
-  ReduceGroup g;
-  reduce_group_init(g);
-  TRY_RG(reduce_group_add(g, slabs, out1, n1, out2, n, nslab, slab_stride, stream));
-  return reduce_group_flush(g, stream);
-}
-
-int reduce_slabs(const float* slabs, float* out, long long n, int nslab, long long slab_stride, hipStream_t stream) {
-  return reduce_slabs2(slabs, out, n, nullptr, n, nslab, slab_stride, stream);
 }

@@ -1,5 +1,5 @@
 // Internal prototypes of the launch functions implemented in the kernel translation units
-// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, gemm.hip); the schedules in encoder.hip, encoder_bf16.hip
+// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, gemm.hip, gemm_reduce.hip); the schedules in encoder.hip, encoder_bf16.hip
 // and cnn_api.hip call these.
 #pragma once
 #include "common.h"

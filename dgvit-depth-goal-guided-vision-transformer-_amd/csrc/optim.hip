@@ -58,7 +58,6 @@ inline unsigned grid_for(long long n4) {
   if (b > 2048) b = 2048;  // 8 workgroups per CU, grid-stride beyond
   return (unsigned)(b < 1 ? 1 : b);
 }
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
 

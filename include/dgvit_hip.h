@@ -269,7 +269,8 @@ int dgvit_tanh_gaussian_backward(const float* mean, const float* log_std_raw, co
  * -------------------------------------------------------------------------------------------- */
 /* generic GEMM C = op(A) op(B) (+ epilogue); layout 0 NT (A MxK, B NxK), 1 NN (A MxK, B KxN), 2 TN (A KxM, B KxN).
  * epilogue 0: C = acc + bias + res;  1: C = acc + bias, C2 = gelu(C);  2: C = acc * gelu'(aux);
- *          3: C = relu(acc + bias);  4: C = aux > 0 ? acc : 0.
+ *          3: C = relu(acc + bias);  4: C = aux > 0 ? acc : 0;  6: t = acc + bias, C = gelu'(t), C2 = gelu(t);  7: C = acc * aux;
+ *          8: C = gelu(acc + bias).  (5 and 9 are internal forms and are refused.)
  * layout 2 runs split over K with `scratch` slabs (dgvit_gemm_scratch_floats) and then reduces into C. */
 long long dgvit_gemm_scratch_floats(int layout, int M, int N, int K);
 int dgvit_gemm(int layout, int epilogue, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M,

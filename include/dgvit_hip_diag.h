@@ -42,7 +42,9 @@ void dgvit_set_gemm_diagnostics(int bits);
  * loop; NT / NN forms, 16-byte-aligned operands, K = 16 k-tiles of the chosen tile: 256 at 16-deep, 512 at 32-deep k-tiles).
  * mode 0 = never, 1 = when a resident workgroup slot gets at least two tiles and no tile is split, 2 = whenever the launch is
  * eligible.  workgroups > 0 overrides the grid (diagnostic; 0 = automatic).  Same results bit for bit as the per-tile kernel: the
- * k order of a tile does not change. */
+ * k order of a tile does not change.  The kernel implements epilogues 0 - 4 of dgvit_gemm (EPI_STORE, EPI_GELU2, EPI_DGELU, EPI_RELU,
+ * EPI_DRELU) only; launches with any other epilogue (EPI_GELU2D, EPI_DMUL, EPI_GELU, EPI_UNPATCH: the encoder's fc1 and its data
+ * gradient among them) run the per-tile kernel whatever the mode and are not counted. */
 void dgvit_set_gemm_persistent(int mode, int workgroups);
 /* launches that took the pipelined kernel since the library was loaded (tests check that they exercise it) */
 long long dgvit_gemm_persistent_launches(void);

@@ -9,7 +9,7 @@ results on chunks below 2 GiB.  Tolerances are those of tests/test_gpu_ops.py fo
 of non-zero terms of a sum).  Every test states its need, skips (with the numbers) if the device has less free, stays under 48 GiB and
 frees its tensors; each prints its peak allocation and wall time.
 
-Boundary branches reached (shape in each test's docstring): gemm.hip plan() per-workgroup descriptor rebase and num_records clamp, the
+Boundary branches reached (shape in each test's docstring): gemm_tile.h Fetch::plan per-workgroup descriptor rebase and num_records clamp, the
 direct C / residual / aux stores' clamp, the `lda*512` and `kchunk*ld*4` refusals and the new output-leading-dimension refusal; the
 int-row / widened-offset arithmetic of norm.hip; gather_rows_kernel's source index; dropout / cast with n > 2^31; the fused and tiled
 fp32 attention kernels' frame offsets past element 2^31 of qkv; the bf16 stream / ring GEMM, weight gradient, LayerNorm and the
@@ -799,7 +799,7 @@ def test_encoder_headline_width_with_fc1_output_past_4_gib(amd):
 
 def test_encoder_patch_gather_falls_back_at_2_29_pixels(amd):
     """128 x 160 @ 16 x 20, D 64, H 2, dh 32, M 64, depth 1.  B = 26 208 (5.37e8 pixels, under 2^29) embeds the patches through the
-    gather loader (gemm.hip plan_gather: one descriptor over the whole 2.15 GB image buffer, unsigned 32-bit byte offsets); B = 26 215
+    gather loader (gemm_tile.h Fetch::plan_gather: one descriptor over the whole 2.15 GB image buffer, unsigned 32-bit byte offsets); B = 26 215
     (2^29 pixels and more: the clamped descriptor would read zeros) must take the patchify fallback of encoder.hip:235.  At both
     batches the last 8 frames agree with the same frames run as a small batch at 2e-5, and frames 0, the last, and those around the
     image buffer's byte offset 2^31 agree with the fp64 oracle at 1e-4."""

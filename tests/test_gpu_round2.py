@@ -956,6 +956,79 @@ def test_persistent_gemm_equals_per_tile_kernel(layout, epi, M, N, K, tile, wgs)
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("layout,epi", [(0, 8), (0, 6), (1, 7)], ids=["gelu", "gelu2d", "dmul"])
+def test_persistent_gemm_leaves_its_missing_epilogues_to_the_per_tile_kernel(layout, epi):
+    """The pipelined kernel implements epilogues 0 - 4 only.  EPI_GELU (8: NT, bias), EPI_GELU2D (6: NT, bias, two outputs) and EPI_DMUL
+    (7: NN, aux) - what the encoder's fc1 and its data gradient use - at a shape it would otherwise take (K = 256 = 16 k-tiles of the
+    64 x 128 x 16 tile, no split) run the per-tile kernel with the knob set: the launch counter does not move, every output has the bits
+    of the run without the knob, and the values are right.  Operands and tolerance are those of test_gpu_ops.py::test_gemm_epilogues
+    (x ~ N(0, 1), weights 0.2 N(0, 1): |acc| is a few units, fp32 accumulation over K = 256 and the erf approximation stay below 2e-5)."""
+    import math
+    from dgvit_amd import functional as F
+    M, N, K, tile = 300, 256, 256, 64128016
+    g = torch.Generator().manual_seed(epi)
+    A64 = torch.randn(M, K, generator=g, dtype=torch.float64)
+    B64 = torch.randn((N, K) if layout == 0 else (K, N), generator=g, dtype=torch.float64) * 0.2
+    bias64 = torch.randn(N, generator=g, dtype=torch.float64) if layout == 0 else None
+    aux64 = torch.randn(M, N, generator=g, dtype=torch.float64) if epi == 7 else None
+    A, B = A64.float().cuda(), B64.float().cuda()
+    bias = bias64.float().cuda() if bias64 is not None else None
+    aux = aux64.float().cuda() if aux64 is not None else None
+
+    def run(mode):
+        with knobs(force_diag=True, gemm_tile=tile, gemm_persistent=(mode, 2), gemm_split=0) as lib:
+            before = lib.dgvit_gemm_persistent_launches()
+            out = F.op_gemm(layout, epi, A, B, M, N, K, bias=bias, aux=aux, want_c2=(epi == 6))
+            torch.cuda.synchronize()
+            moved = lib.dgvit_gemm_persistent_launches() - before
+        return (out if isinstance(out, tuple) else (out,)), moved
+
+    ref, _ = run(0)
+    got, moved = run(2)
+    assert moved == 0, "the pipelined kernel took an epilogue it does not implement"
+    for r, o in zip(ref, got):
+        assert torch.equal(r, o), f"max diff {(r - o).abs().max().item()}"
+    t = A64 @ (B64.t() if layout == 0 else B64) + (bias64 if bias64 is not None else 0)
+    cdf, pdf = 0.5 * (1 + torch.erf(t / math.sqrt(2))), torch.exp(-0.5 * t * t) / math.sqrt(2 * math.pi)
+    want = {8: (t * cdf,), 6: (cdf + t * pdf, t * cdf), 7: (t * aux64 if aux64 is not None else None,)}[epi]
+    for w, o in zip(want, got):
+        torch.testing.assert_close(o.double().cpu(), w, atol=1e-4, rtol=0.0)
+
+
+@pytest.mark.gpu
+def test_persistent_gemm_leaves_a_second_output_with_its_own_stride_to_the_per_tile_kernel():
+    """EPI_GELU2 with ldc2 != ldc: the pipelined kernel addresses C2 with C's stride, so the launch is not eligible (the two-output
+    condition of `launch`): the per-tile kernel runs, the counter does not move, and C / C2 have the bits of the run without the knob."""
+    from dgvit_amd import _lib
+    M, N, K, ldc2 = 203, 128, 256, 160
+    g = torch.Generator().manual_seed(9)
+    A = torch.randn(M, K, generator=g).cuda()
+    B = torch.randn(N, K, generator=g).cuda()
+    bias = torch.randn(N, generator=g).cuda()
+
+    def run(mode):
+        C = torch.empty(M, N, device="cuda")
+        C2 = torch.full((M, ldc2), 777.0, device="cuda")
+        with knobs(force_diag=True, gemm_tile=64128016, gemm_persistent=(mode, 2), gemm_split=0) as lib:
+            nsc = lib.dgvit_gemm_scratch_floats(0, M, N, K)
+            scratch = torch.zeros(max(nsc, 4), device="cuda")
+            before = lib.dgvit_gemm_persistent_launches()
+            rc = lib.dgvit_gemm(0, 1, A.data_ptr(), K, B.data_ptr(), K, C.data_ptr(), N, M, N, K, bias.data_ptr(), None, 0, C2.data_ptr(), ldc2,
+                                None, 0, scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "dgvit_gemm")
+            torch.cuda.synchronize()
+            moved = lib.dgvit_gemm_persistent_launches() - before
+        return C, C2, moved
+
+    C0, C20, _ = run(0)
+    C, C2, moved = run(2)
+    assert moved == 0, "the pipelined kernel took a launch whose C2 has its own stride"
+    assert torch.equal(C, C0) and torch.equal(C2, C20)
+    assert (C2[:, N:] == 777.0).all(), "columns between N and ldc2 were written"
+    torch.testing.assert_close(C2[:, :N], torch.nn.functional.gelu(C), atol=1e-5, rtol=1e-5)
+
+
+@pytest.mark.gpu
 def test_persistent_gemm_writes_nothing_outside_c():
     """Direct accumulator stores with the descriptor's range check: a C window inside a larger canary buffer stays intact around
     the matrix (rows past M and the columns between N and ldc)."""
