@@ -23,7 +23,7 @@ class dgvit_config(Structure):
 
 FLAG_DENSE_LAST_BLOCK = 1    # include/dgvit_hip.h: DGVIT_FLAG_*
 FLAG_WGRAD_OVERLAP = 2
-FLAG_LONG_SEQUENCE = 4      # fp32 encoder: K / V-tiled attention for N > 288 tokens
+FLAG_LONG_SEQUENCE = 4      # K / V-tiled attention for N > 288 tokens (fp32 and bf16 encoders)
 MAPS_GOAL = 0               # include/dgvit_hip.h: DGVIT_MAPS_* (the rows of an attention-maps call)
 MAPS_ALL = 1
 
@@ -125,6 +125,8 @@ SIGNATURES = {
     "dgvit_attention_probs": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_probs_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dgvit_attention_forward_bf16_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_attention_backward_bf16_tiled": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dgvit_profile_start": (_I, [_I]),
     "dgvit_profile_stop": (_I, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_longlong)]),
     "dgvit_profile_sampling": (_I, [_I]),
@@ -154,6 +156,7 @@ DIAG_SIGNATURES = {
     "dgvit_set_attention_bwd_single_pass": (None, [_I]),
     "dgvit_set_attention_single_query": (None, [_I]),
     "dgvit_set_attention_bf16_long": (None, [_I]),
+    "dgvit_set_attention_bf16_tiled_waves": (None, [_I]),
     "dgvit_set_gemm_wgrad_slice_major": (None, [_I]),
     "dgvit_attention_forward_queries": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_queries": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

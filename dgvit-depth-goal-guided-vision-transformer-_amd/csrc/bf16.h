@@ -103,4 +103,9 @@ int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N,
 
 int attention_bwd_bf16(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,
                        int N, int H, int dh, hipStream_t st);
+// attention_bf16_long.hip: the same core with K / V tiled through LDS, any N >= 1 (the bf16 encoder takes it for N > 288 under
+// DGVIT_FLAG_LONG_SEQUENCE); lse may be null in the forward, delta is B*H*N floats written in full by the backward
+int attention_fwd_bf16_tiled(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st);
+int attention_bwd_bf16_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,
+                             int N, int H, int dh, hipStream_t st);
 

@@ -294,7 +294,8 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
     TRY(gemm_bf16(BEPI_BF16, q, st));
   }
   float* lse = f.maps ? (float*)(lb + w.lse) : f.f32(lb, w.lse);   // (the no-grad layout has the slot too)
-  TRY(attention_fwd_bf16(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+  if (d.tiled) TRY(attention_fwd_bf16_tiled(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+  else TRY(attention_fwd_bf16(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
   if (f.maps) {   // before the shared qkv / lse are overwritten by the next layer
     const long long per_head = f.maps_rows == DGVIT_MAPS_ALL ? (long long)d.N * d.N : d.N;
     TRY(attention_probs_bf16(qkv, lse, f.maps + (long long)i * d.H * per_head, (long long)d.L * d.H * per_head, d.B, d.N, d.H, d.dh,
@@ -496,7 +497,8 @@ int layer_bwd_bf16(const BwdB& b, int i) {
     GemmBf16Params p = gpb(dxh, d.D, lw + wp.outT, d.D, dao, d.I, T, d.I, d.D);     // dao = dxmid Wo
     TRY(gemm_bf16(BEPI_BF16, p, st));
   }
-  TRY(attention_bwd_bf16(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
+  if (d.tiled) TRY(attention_bwd_bf16_tiled(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
+  else TRY(attention_bwd_bf16(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
   TRY(b.wgrad(dqkv, 3 * d.I, ln1, d.D, lg[L_QKV], nullptr, 3 * d.I, d.D));
   {
     GemmBf16Params p = gpb(dqkv, 3 * d.I, lw + wp.qkvT, 3 * d.I, dln, d.D, T, d.D, 3 * d.I);   // dln1 = dqkv Wqkv
@@ -589,4 +591,13 @@ extern "C" int dgvit_attention_backward_bf16(const unsigned short* qkv, const un
 extern "C" int dgvit_attention_forward_bf16(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh,
                                             void* stream) {
   return attention_fwd_bf16(qkv, out, lse, B, N, H, dh, N, (hipStream_t)stream);
+}
+extern "C" int dgvit_attention_forward_bf16_tiled(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh,
+                                                  int nq, void* stream) {
+  return attention_fwd_bf16_tiled(qkv, out, lse, B, N, H, dh, nq, (hipStream_t)stream);
+}
+extern "C" int dgvit_attention_backward_bf16_tiled(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout,
+                                                   const float* lse, unsigned short* dqkv, float* delta, int B, int N, int H, int dh,
+                                                   void* stream) {
+  return attention_bwd_bf16_tiled(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, (hipStream_t)stream);
 }

@@ -112,7 +112,7 @@ struct SplitBuf {
 struct Dims {
   int B, P, N, D, I, M, L, H, dh, pd, pool_mean;
   int proj;       // 0: heads == 1 and dim_head == dim -- the reference's Attention has no output projection (to_out = nn.Identity(), GoalFormer.py:56,66-69)
-  int tiled;      // DGVIT_FLAG_LONG_SEQUENCE and N > 288: the attention runs on the K / V-tiled kernels (attention_long.hip)
+  int tiled;      // DGVIT_FLAG_LONG_SEQUENCE and N > 288: the attention runs on the K / V-tiled kernels (attention_long.hip, attention_bf16_long.hip)
   long long T;
 };
 

@@ -702,6 +702,42 @@ def op_attention_bwd_bf16(qkv, out, dout, lse, heads, dim_head=64):
     return dqkv
 
 
+def op_attention_bf16_tiled(qkv, heads, dim_head=64, nq=None, want_lse=False, *, out=None, lse=None):
+    """The bf16 K / V-tiled attention kernels (any N; the bf16 encoder's path for N > 288 under long_sequence_bf16): out and lse rows
+    < nq (default N) are written, the other rows are left as they are (uninitialised unless `out` / `lse` are given)."""
+    lib = _lib.load()
+    qkv = _dev_bf16(qkv, "qkv")
+    B, N, W = qkv.shape
+    if W != 3 * heads * dim_head:
+        raise DgvitError(f"qkv last dim {W} != 3*{heads}*{dim_head}")
+    nq = N if nq is None else nq
+    out = torch.empty(B, N, heads * dim_head, dtype=torch.bfloat16, device=qkv.device) if out is None else _dev_bf16(out, "out")
+    if lse is None and want_lse:
+        lse = torch.empty(B, heads, N, dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = lib.dgvit_attention_forward_bf16_tiled(_ptr(qkv), _ptr(out), _ptr(lse), B, N, heads, dim_head, int(nq), _stream())
+    _lib.check(rc, "dgvit_attention_forward_bf16_tiled")
+    return (out, lse) if want_lse else out
+
+
+def op_attention_bwd_bf16_tiled(qkv, out, dout, lse, heads, dim_head=64, *, delta=None):
+    """Gradient on the bf16 tiled kernels (dense): every row of dqkv and all B*heads*N floats of `delta` (rowsum(dout o out), default:
+    a new tensor) are written."""
+    lib = _lib.load()
+    qkv, out, dout, lse = _dev_bf16(qkv, "qkv"), _dev_bf16(out, "out"), _dev_bf16(dout, "dout"), _dev(lse, "lse")
+    B, N, _ = qkv.shape
+    dqkv = torch.empty_like(qkv)
+    if delta is None:
+        delta = torch.empty(B * heads * N, dtype=torch.float32, device=qkv.device)
+    if delta.numel() < B * heads * N:
+        raise DgvitError(f"delta has {delta.numel()} floats, {B * heads * N} needed")
+    with torch.cuda.device(qkv.device):
+        rc = lib.dgvit_attention_backward_bf16_tiled(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _ptr(_dev(delta, "delta")), B, N,
+                                                     heads, dim_head, _stream())
+    _lib.check(rc, "dgvit_attention_backward_bf16_tiled")
+    return dqkv
+
+
 class Bf16Weights:
     """bf16 copies of an encoder's GEMM weights in one arena (dgvit_got_pack_weights_bf16).
 

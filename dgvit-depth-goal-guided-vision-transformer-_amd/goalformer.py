@@ -128,6 +128,7 @@ class GoT(nn.Module):
         self._cfg = (image_height, image_width, patch_height, patch_width, dim, depth, heads, dim_head, mlp_dim,
                      1 if pool == 'mean' else 0, 0)       # last entry: schedule flags (set_schedule)
         self.compute_dtype = torch.float32
+        self._long_sequence_bf16 = False   # set_schedule(long_sequence_bf16=True): the long-sequence request covers bf16 too
         self._bf16_weights = F_.Bf16Weights()
         self._grad_hook = None     # set by parallel.GradSync(overlap=True): called inside the backward with the gradient-ready events
         self.register_load_state_dict_post_hook(_weights_loaded)
@@ -153,24 +154,30 @@ class GoT(nn.Module):
         self._bf16_weights.invalidate()
         return self
 
-    def set_schedule(self, dense_last_block: bool = False, wgrad_overlap: bool = False, long_sequence: bool = False):
+    def set_schedule(self, dense_last_block: bool = False, wgrad_overlap: bool = False, long_sequence: bool = False,
+                     long_sequence_bf16: bool = False):
         """Per-module schedule options, passed to the C ABI with every call (``dgvit_config.flags``; nothing global).
         ``dense_last_block``: run the whole last block instead of its token-0 rows only (identical results; A/B measurements).
         ``wgrad_overlap``: the backward runs the weight-gradient GEMMs on a helper stream beside the data-gradient chain
         (+3..5 % frames/s at BASELINE config 3; per-kernel timings stop being interpretable).
         ``long_sequence``: lift the fp32 encoder's 288-token limit -- for N > 288 the attention runs on K / V-tiled kernels (N <= 288 is
-        unchanged, bit for bit); the backward needs B*H*N floats more scratch.  fp32 only: the bf16 configuration runs up to 288 tokens,
-        the limit both configurations share without this option."""
+        unchanged, bit for bit); the backward needs B*H*N floats more scratch.  fp32 only: with this option alone the bf16
+        configuration stays refused (it runs up to 288 tokens, the limit both configurations share without an option).
+        ``long_sequence_bf16``: the same option for both compute dtypes -- on an fp32 model it is ``long_sequence=True``; on a bf16
+        model (set before or after ``set_compute_dtype(torch.bfloat16)``) the attention of N > 288 tokens runs on the bf16 K / V-tiled
+        kernels, forward, backward and ``attention_maps``; N <= 288 is unchanged, bit for bit, and no buffer size changes.
+        Every option is reset by the next call that omits it."""
         from ._lib import FLAG_DENSE_LAST_BLOCK, FLAG_LONG_SEQUENCE, FLAG_WGRAD_OVERLAP
-        if long_sequence:
+        if long_sequence and not long_sequence_bf16:
             self._check_long_sequence_dtype(self.compute_dtype, True)
         flags = ((FLAG_DENSE_LAST_BLOCK if dense_last_block else 0) | (FLAG_WGRAD_OVERLAP if wgrad_overlap else 0)
-                 | (FLAG_LONG_SEQUENCE if long_sequence else 0))
+                 | (FLAG_LONG_SEQUENCE if long_sequence or long_sequence_bf16 else 0))
         self._cfg = (*self._cfg[:10], flags)
+        self._long_sequence_bf16 = bool(long_sequence_bf16)
         return self
 
     def long_sequence(self) -> bool:
-        """Whether ``set_schedule(long_sequence=True)`` is in effect."""
+        """Whether ``set_schedule(long_sequence=True)`` or ``set_schedule(long_sequence_bf16=True)`` is in effect."""
         from ._lib import FLAG_LONG_SEQUENCE
         return bool(self._cfg[10] & FLAG_LONG_SEQUENCE)
 
@@ -178,7 +185,8 @@ class GoT(nn.Module):
     def _check_long_sequence_dtype(dtype, long_sequence):
         if dtype == torch.bfloat16 and long_sequence:
             raise NotImplementedError("long_sequence (the K/V-tiled attention for more than 288 tokens) is implemented on the fp32 path "
-                                      "only; the bf16 configuration runs up to 288 tokens (e.g. 256x256 frames with 16x16 patches)")
+                                      "only; the bf16 configuration runs up to 288 tokens (e.g. 256x256 frames with 16x16 patches) "
+                                      "unless it is asked for with set_schedule(long_sequence_bf16=True), which covers both dtypes")
 
     def layer_dropout(self) -> float:
         """The transformer ``dropout`` p (the reference's nn.Dropout modules inside the blocks; they all share it)."""
@@ -196,7 +204,7 @@ class GoT(nn.Module):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute dtype {dtype} unsupported (torch.float32 or torch.bfloat16)")
         self._check_dropout_dtype(dtype)
-        self._check_long_sequence_dtype(dtype, self.long_sequence())
+        self._check_long_sequence_dtype(dtype, self.long_sequence() and not getattr(self, "_long_sequence_bf16", False))
         self.compute_dtype = dtype
         return self
 

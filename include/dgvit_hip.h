@@ -44,7 +44,7 @@ int dgvit_device_count(void);
 /* ----------------------------------------------------------------------------------------------
  * Encoder shape = the GoT constructor arguments (GoalFormer.py:124-154).  patch_h/patch_w are honoured
  * (the reference hard-wires 16x20, GoalFormer.py:137-139).  dim_head must be 64 or 32; tokens
- * N = (image_h/patch_h)*(image_w/patch_w) + 1 <= 288, or any N with DGVIT_FLAG_LONG_SEQUENCE (fp32 path).
+ * N = (image_h/patch_h)*(image_w/patch_w) + 1 <= 288, or any N with DGVIT_FLAG_LONG_SEQUENCE (fp32 and bf16 paths).
  * -------------------------------------------------------------------------------------------- */
 typedef struct dgvit_config {
   int image_h, image_w;
@@ -66,10 +66,11 @@ typedef struct dgvit_config {
  * MI355X, but concurrent kernels stretch each other's durations, so per-kernel timings (dgvit_profile_*, rocprof) stop being
  * interpretable.  Off: everything stays on the caller's stream. */
 #define DGVIT_FLAG_WGRAD_OVERLAP 2
-/* Lifts the N <= 288 token limit of the fp32 encoder: for N > 288 the attention forward and backward run on K / V-tiled kernels that
- * stream 64-row tiles through LDS (dgvit_attention_forward_tiled below); N <= 288 keeps the fused kernels, bit-identical to the flag
- * being unset.  The backward scratch (dgvit_got_backward_scratch_floats) grows by B*H*N floats when N > 288 and the flag is set; with
- * the flag unset every size, result and refusal is unchanged.  The bf16 configuration keeps its N <= 256 limit. */
+/* Lifts the N <= 288 token limit of the encoder, fp32 and bf16: for N > 288 the attention forward and backward run on K / V-tiled
+ * kernels that stream 64-row tiles through LDS (dgvit_attention_forward_tiled, dgvit_attention_forward_bf16_tiled below); N <= 288
+ * keeps the fused kernels, bit-identical to the flag being unset.  The fp32 backward scratch (dgvit_got_backward_scratch_floats) grows
+ * by B*H*N floats when N > 288 and the flag is set; the bf16 sizes (dgvit_got_bf16_workspace_bytes, _backward_scratch_bytes) follow
+ * the same formulas at every N.  With the flag unset every size, result and refusal is unchanged. */
 #define DGVIT_FLAG_LONG_SEQUENCE 4
 
 /* Parameter / gradient tables: arrays of DGVIT_NUM_GLOBAL_PARAMS + DGVIT_PARAMS_PER_LAYER*depth device
@@ -449,6 +450,13 @@ int dgvit_attention_forward_bf16(const unsigned short* qkv, unsigned short* out,
  * of scratch (rowsum(dout o out), handed from the dQ kernel to the dK/dV kernel) */
 int dgvit_attention_backward_bf16(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout, const float* lse,
                                   unsigned short* dqkv, float* delta, int B, int N, int H, int dh, void* stream);
+/* The same two on the K / V-tiled kernels the bf16 encoder uses for N > 288 under DGVIT_FLAG_LONG_SEQUENCE: any N >= 1, dh = 64.
+ * The forward computes the leading nq query rows (1 <= nq <= N) against every key and writes only those rows of out and lse (lse may
+ * be NULL); the backward is dense and writes all B*H*N floats of delta.  Deterministic; a grid of 2^31 workgroups or more is refused. */
+int dgvit_attention_forward_bf16_tiled(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh, int nq,
+                                       void* stream);
+int dgvit_attention_backward_bf16_tiled(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout,
+                                        const float* lse, unsigned short* dqkv, float* delta, int B, int N, int H, int dh, void* stream);
 /* attention maps in the bf16 configuration (see dgvit_got_forward_maps): the arguments of dgvit_got_forward_bf16 without
  * save_for_backward, plus maps and rows */
 int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,

@@ -94,6 +94,9 @@ void dgvit_set_attention_single_query(int on);
  * else the per-item kernel; bit 1 nine-wave workgroups (per-item forward, dq backward) for nine 32-token tiles, else eight waves with a second
  * round for one of them.  Default 3; -1 restores it.  Same results whatever the bits. */
 void dgvit_set_attention_bf16_long(int bits);
+/* A/B knob, K / V-tiled bf16 attention (dgvit_attention_forward_bf16_tiled / _backward_bf16_tiled): waves per workgroup = 32-row tiles
+ * of its query / key block, 4 (128 rows) or 8 (256 rows, default); any other value restores the default.  Same results either way. */
+void dgvit_set_attention_bf16_tiled_waves(int waves);
 /* A/B knob: 1 (default) the weight-gradient GEMMs deal (tile, k-slice) pairs to the XCDs k-slice major (an XCD reads its slices of dY and X
  * once); 0 the round 1-3 grid (tiles, 1, slices): an XCD owns a few tiles and all their slices.  Bit-identical results. */
 void dgvit_set_gemm_wgrad_slice_major(int on);
