@@ -209,6 +209,11 @@ extern "C" int dgvit_gather_rows(const float* src, const long long* idx, float* 
                                  long long nrows, void* stream) {
   return gather_rows(src, idx, out, nsel, row_floats, nrows, (hipStream_t)stream);
 }
+extern "C" int dgvit_gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                                         long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                                         const unsigned long long* seed_dev, void* stream) {
+  return gather_shift_frames(src, idx, out, shifts_out, nsel, H, W, row_floats, nrows, pad, stream_id, seed, seed_dev, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- SURVEY 8(f4)
 extern "C" long long dgvit_depth_preprocess_scratch_floats(int B, int H, int W) {

@@ -220,6 +220,15 @@ __device__ __forceinline__ uint4 drop_bits(long long i4, unsigned long long seed
 // the factor one random word gives: 1/keep (kept) or 0 (dropped)
 __device__ __forceinline__ float drop_factor(uint32_t r, float keep, float inv) { return (r * 2.3283064365386963e-10f < keep) ? inv : 0.f; }
 
+// ---- random-shift augmentation of sampled frames (embed.hip gather_shift_frames_kernel): a third family of the same counter space.
+//   ctr.z                        | counter (ctr.x, ctr.y) | words used
+//   0                            | float4 group           | emb-dropout, all four
+//   0x44000000 | (l << 2) | s    | float4 group           | transformer dropout sites, all four (table above)
+//   0x53000000 | stream          | sample number i        | x -> dy, y -> dx of sample i (stream 0: obs, 1: next_obs); z, w unused
+// A word r gives the shift (int)(((uint64)r * (2*pad + 1)) >> 32) - pad, uniform over [-pad, pad] up to 2^-32 (no modulo).
+#define DGVIT_SHIFT_STREAMS 0x10000
+__host__ __device__ __forceinline__ uint32_t shift_tag(int stream) { return 0x53000000u | (uint32_t)stream; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

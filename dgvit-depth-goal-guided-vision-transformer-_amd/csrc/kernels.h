@@ -46,6 +46,10 @@ int weight_pack(const float*, float*, int, int, int, int, hipStream_t);
 int avgpool(const float*, float*, int, int, int, hipStream_t);
 int avgpool_bwd_relu(const float*, const float*, float*, int, int, int, hipStream_t);
 int gather_rows(const float*, const long long*, float*, long long, long long, long long, hipStream_t);
+// gather_rows with the random shift of a (H, W) frame folded in (idx / shifts_out may be null; draw: the shift table in common.h)
+int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                        long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                        const unsigned long long* seed_dev, hipStream_t stream);
 int mean_bwd(const float*, float*, int, int, int, hipStream_t);
 int depth_normalize_u8(const float*, float*, float*, int, int, int, hipStream_t);
 long long depth_normalize_scratch_floats(int);

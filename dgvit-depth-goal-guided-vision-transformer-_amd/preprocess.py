@@ -7,6 +7,7 @@ The reference does this on the host with OpenCV for every camera message and eve
 Parity against OpenCV itself is unpinned (cv2 is not installed in the build image; see oracle/dgvit_oracle.py f4_*).
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -109,3 +110,65 @@ def depth_to_state(depth, noise_level=50, noise=None, seed=None, size=(128, 160)
                                       size[0], size[1], _stream())
     _lib.check(rc, "dgvit_depth_to_state")
     return state[0] if squeeze else state
+
+
+# ------------------------------------------------------------------------------------------------ random shift (DrQ), DESIGN.md 3.24
+def _shift_pad(pad, shape, what="pad"):
+    """``pad`` as an int after the checks every random-shift caller shares; host-only, runs before anything touches a device"""
+    if isinstance(pad, bool) or not isinstance(pad, numbers.Integral):
+        raise ValueError(f"{what} must be an integer number of pixels, got {pad!r}")
+    if pad < 0:
+        raise ValueError(f"{what} must be >= 0, got {pad}")
+    if pad == 0:
+        return 0
+    if len(shape) != 2:
+        raise ValueError(f"{what}: frames must be (H, W), got {tuple(shape)}")
+    if pad >= min(shape):
+        raise ValueError(f"{what}={pad} must be smaller than the frame's shorter side (H, W) = {tuple(shape)}")
+    return int(pad)
+
+
+def _shift_seed(device):
+    """The seed of one shifted batch, drawn as GoT.draw_dropout_seed() draws the dropout seed: an int from torch's CPU generator, or,
+    inside a stream capture, a 1-element int64 device tensor (a host value would be frozen into every replay)."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(1, dtype=torch.int64, device=device).random_()
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _gather_shift(src, idx, out, shifts, frame, nrows, pad, stream_id, seed):
+    """dgvit_gather_shift_frames on the current stream (the caller has made src's device current): out (B, row) <- rows ``idx`` (None:
+    0..B-1) of src (nrows, row), each shifted by its own draw; ``seed`` is an int or a 1-element int64 device tensor; ``shifts`` (B, 2)
+    int32 or None receives (dy, dx)."""
+    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    rc = _lib.load().dgvit_gather_shift_frames(_ptr(src), _ptr(idx), _ptr(out), _ptr(shifts), out.shape[0], frame[0], frame[1],
+                                               out.shape[1], nrows, pad, stream_id, 0 if seed_dev is not None else int(seed),
+                                               _ptr(seed_dev), _stream())
+    _lib.check(rc, "dgvit_gather_shift_frames")
+
+
+def random_shift(frames, pad, seed=None, stream_id=0, return_shifts=False):
+    """DrQ random shift of a batch that does not come from ``DeviceReplayBuffer`` (e.g. a behaviour-cloning loader): every frame of
+    ``frames`` (B, H, W) is padded by ``pad`` pixels with its border (``F.pad(mode="replicate")``) and cropped back at its own offset
+    (pad + dy, pad + dx), dy and dx uniform in [-pad, pad].  One kernel, one read and one write per pixel; the result is a new tensor.
+    ``seed`` (int, or a 1-element int64 device tensor for graph capture; default: drawn from torch's CPU generator) and ``stream_id``
+    fix the draw (include/dgvit_hip.h: dgvit_gather_shift_frames); ``return_shifts`` adds the (B, 2) int32 table of (dy, dx)."""
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError(f"frames: expected a tensor, got {type(frames).__name__}")
+    if frames.dim() != 3:
+        raise _lib.DgvitError(f"frames must be (B, H, W), got {tuple(frames.shape)}")
+    B, H, W = frames.shape
+    pad = _shift_pad(pad, (H, W))
+    x = _dev(frames, "frames").reshape(B, H * W)
+    row = (H * W + 3) & ~3
+    if row != H * W:                       # the kernel reads and writes rows of whole float4 groups
+        src = x.new_zeros(B, row)
+        src[:, :H * W] = x
+    else:
+        src = x if x.data_ptr() % 16 == 0 else x.clone()
+    out = torch.empty(B, row, dtype=torch.float32, device=x.device)
+    shifts = torch.empty(B, 2, dtype=torch.int32, device=x.device) if return_shifts else None
+    with torch.cuda.device(x.device):
+        _gather_shift(src, None, out, shifts, (H, W), B, pad, int(stream_id), _shift_seed(x.device) if seed is None else seed)
+    res = out[:, :H * W].reshape(B, H, W)
+    return (res, shifts) if return_shifts else res

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .preprocess import _gather_shift, _shift_pad, _shift_seed
 
 
 def _al4(n: int) -> int:
@@ -96,21 +97,39 @@ class DeviceReplayBuffer:
             raise RuntimeError("cannot sample from an empty buffer")
         return torch.randint(0, self.stored, (batch_size,), device=self.device, dtype=torch.int64, generator=self.gen)
 
-    def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None, random_shift: int = 0,
+               return_shifts: bool = False) -> Dict[str, torch.Tensor]:
         """Uniform sample with replacement -> dict of DEVICE tensors shaped like the reference's batch
-        (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip."""
+        (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip.
+
+        ``random_shift=p`` (p > 0) applies the DrQ augmentation inside the gather of ``obs`` and ``next_obs``: each sampled frame is
+        padded by p pixels with its border and cropped back at its own random offset, the two fields drawing independently (streams
+        0 and 1 of one seed per call; the seed comes from torch's CPU generator, or from the device inside a stream capture, and is
+        kept in ``self.shift_seed``).  ``return_shifts=True`` adds ``obs_shift`` and ``next_obs_shift``, (B, 2) int32 (dy, dx).
+        With ``random_shift=0`` nothing is drawn and the launches are the plain gathers."""
+        pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
         lib = _lib.load()
         idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
         B = idx.numel()
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         out = {}
+        if pad:
+            self.shift_seed = _shift_seed(self.device)
         with torch.cuda.device(self.device):
             for k, n in self.fields.items():
                 r = self.rows[k]
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
-                rc = lib.dgvit_gather_rows(ctypes.c_void_p(self.store[k].data_ptr()), ctypes.c_void_p(idx.data_ptr()),
-                                           ctypes.c_void_p(buf.data_ptr()), B, r, self.size, st)
-                _lib.check(rc, "dgvit_gather_rows")
+                if pad and k in ("obs", "next_obs"):
+                    shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
+                    _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
+                    if return_shifts:
+                        out[k + "_shift"] = shifts
+                else:
+                    rc = lib.dgvit_gather_rows(ctypes.c_void_p(self.store[k].data_ptr()), ctypes.c_void_p(idx.data_ptr()),
+                                               ctypes.c_void_p(buf.data_ptr()), B, r, self.size, st)
+                    _lib.check(rc, "dgvit_gather_rows")
                 out[k] = buf[:, :n].reshape(B, *self.shapes[k])
+        if return_shifts and not pad:
+            out["obs_shift"], out["next_obs_shift"] = (torch.zeros(B, 2, dtype=torch.int32, device=self.device) for _ in range(2))
         out["indexes"] = idx
         return out

@@ -346,6 +346,20 @@ int dgvit_cnn_backward_v2(const float* img, const float* const* params, float* c
 int dgvit_gather_rows(const float* src, const long long* idx, float* out, long long nsel, long long row_floats,
                       long long nrows, void* stream);
 
+/* The same gather with the DrQ random shift of a (H, W) frame folded into the pass (no extra traffic):
+ *   out[i][y][x] = src[clamp(idx[i], 0, nrows-1)][clamp(y + dy_i, 0, H-1)][clamp(x + dx_i, 0, W-1)]
+ * which is F.pad(frame, pad, mode="replicate") cropped at offset (pad + dy_i, pad + dx_i); dy_i, dx_i in [-pad, pad].
+ * Rows of src and out are row_floats long (a multiple of 4, >= H*W, <= 2^25); columns H*W .. row_floats of out are written as zeros, so
+ * pad == 0 gives the bytes of dgvit_gather_rows whenever those columns of src are zero (DeviceReplayBuffer keeps them zero).
+ * idx == NULL: the identity (src row i, i clamped to nrows-1).  shifts_out (int32, nsel x 2: dy then dx) is written when non-NULL.
+ * Draw: Philox4x32-10 keyed by the seed (seed_dev, when non-NULL, is a device pointer read at run time: graph capture), counter
+ * (i, 0, 0x53000000 | stream_id, 0); output word 0 gives dy and word 1 gives dx as (int)(((uint64)r * (2*pad+1)) >> 32) - pad.
+ * stream_id in [0, 65536) separates draws that share a seed (DeviceReplayBuffer: 0 = obs, 1 = next_obs).
+ * 0 <= pad < min(H, W); 1 <= nsel < 2^24; src and out 16-byte aligned. */
+int dgvit_gather_shift_frames(const float* src, const long long* idx /* may be NULL */, float* out, int* shifts_out /* may be NULL */,
+                              long long nsel, int H, int W, long long row_floats, long long nrows, int pad, int stream_id,
+                              unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * the depth-frame preprocessing in front of the path -- what env_lab.py does with OpenCV on the
  * host for every camera message (listener_callback :420-434: cv2.normalize MINMAX -> uint8, add_nose :78-89 (N(0, 50) noise,
