@@ -86,6 +86,10 @@ SIGNATURES = {
     "dgvit_attention_forward_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_tiled_scratch_floats": (_LL, [_I, _I, _I]),
     "dgvit_attention_backward_tiled": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
+    "dgvit_goal_attention_scratch_floats": (_LL, [_I, _I, _I]),
+    "dgvit_got_last_block_folds": (_I, [_CFG, _I, _F, _I]),
+    "dgvit_goal_attention_forward": (_I, [_P, _P, _P, _LL, _P, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_goal_attention_backward": (_I, [_P, _P, _P, _LL, _P, _LL, _P, _P, _P, _P, _LL, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
     "dgvit_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_dropout": (_I, [_P, _LL, _ULL, _F, _P]),
     "dgvit_cnn_workspace_floats": (_LL, [_I, _I, _I]),
@@ -156,6 +160,7 @@ DIAG_SIGNATURES = {
     "dgvit_set_gemm_bf16_l2_budget_kb": (None, [_I]),
     "dgvit_set_attention_bwd_single_pass": (None, [_I]),
     "dgvit_set_attention_single_query": (None, [_I]),
+    "dgvit_set_last_block_fold": (None, [_I]),
     "dgvit_set_attention_bf16_long": (None, [_I]),
     "dgvit_set_attention_bf16_tiled_waves": (None, [_I]),
     "dgvit_set_gemm_wgrad_slice_major": (None, [_I]),

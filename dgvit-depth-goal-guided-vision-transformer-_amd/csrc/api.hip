@@ -188,6 +188,27 @@ extern "C" long long dgvit_attention_backward_tiled_scratch_floats(int B, int N,
   if (B <= 0 || N <= 0 || H <= 0) return -1;
   return attention_bwd_tiled_scratch(B, N, H);
 }
+// the last block's attention with K and V folded into token 0's query (last_block.hip)
+extern "C" long long dgvit_goal_attention_scratch_floats(int B, int H, int D) {
+  if (B <= 0 || H <= 0 || D <= 0) return -1;
+  return 2ll * B * H * D;
+}
+extern "C" int dgvit_goal_attention_forward(const float* xn, const float* wqkv, const float* q, long long ldq, float* o, long long ldo, float* u,
+                                            float* r, float* p, int B, int N, int H, int dh, int D, void* stream) {
+  return goal_attention_fwd(xn, wqkv, q, ldq, o, ldo, u, r, (long long)H * D, p, B, N, H, dh, D, (hipStream_t)stream);
+}
+extern "C" int dgvit_goal_attention_backward(const float* xn, const float* wqkv, const float* q, long long ldq, const float* dout, long long lddo,
+                                             const float* u, const float* r, const float* p, float* dq, long long lddq, float* dxn, float* dwkv,
+                                             float* scratch, long long scratch_floats, int B, int N, int H, int dh, int D, void* stream) {
+  const long long hd = (long long)H * D;
+  if (!scratch || scratch_floats < dgvit_goal_attention_scratch_floats(B, H, D) || dgvit_goal_attention_scratch_floats(B, H, D) < 0)
+    return dgvit_set_error(DGVIT_ERR_WORKSPACE, "goal_attention_backward: scratch too small");
+  float* du = scratch;
+  float* dr = scratch + (long long)B * hd;
+  int rc = goal_attention_bwd_data(xn, wqkv, dout, lddo, u, hd, p, du, dr, hd, dq, lddq, dxn, B, N, H, dh, D, (hipStream_t)stream);
+  if (rc) return rc;
+  return goal_attention_wgrad(q, ldq, dout, lddo, du, hd, r, hd, dwkv, B, H, dh, D, (hipStream_t)stream);
+}
 extern "C" int dgvit_patchify(const float* img, float* patches, int B, int ih, int iw, int ph, int pw, void* stream) {
   return patchify(img, patches, B, ih, iw, ph, pw, (hipStream_t)stream);
 }

@@ -41,6 +41,7 @@ extern "C" void dgvit_set_gemm_bf16_tile(int tile) { g_gemm_bf16_tile_hint = til
 extern "C" void dgvit_set_gemm_bf16_mfma16(int on) { g_gemm_bf16_m16 = on ? 1 : 0; }
 extern "C" void dgvit_set_attention_bwd_single_pass(int on) { g_attn_bwd64 = on ? 1 : 0; }
 extern "C" void dgvit_set_attention_single_query(int on) { g_attn_q1 = on ? 1 : 0; }
+extern "C" void dgvit_set_last_block_fold(int on) { g_last_block_fold = on ? 1 : 0; }
 extern "C" void dgvit_set_attention_bf16_tiled_waves(int waves) { g_attn_bf16_tiled_waves = waves == 8 ? 8 : waves == 4 ? 4 : g_attn_bf16_tiled_waves_default; }
 extern "C" void dgvit_set_attention_bf16_long(int bits) { g_attn_bf16_long = bits < 0 ? g_attn_bf16_long_default : (bits & 3); }
 extern "C" void dgvit_set_gemm_wgrad_slice_major(int on) { g_gemm_zfold = on ? 1 : 0; }

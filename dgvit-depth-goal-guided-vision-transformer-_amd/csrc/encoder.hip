@@ -202,6 +202,16 @@ extern "C" long long dgvit_got_backward_scratch_floats(const dgvit_config* cfg, 
   return make_bs(d).total;
 }
 
+// does a training forward (save != 0) and its backward fold K and V of the pruned last block into token 0's query for this
+// configuration (schedule.h last_block_fold)?  1 / 0, negative on a bad configuration.  `maps` != 0: a dgvit_got_forward_maps call
+// (always no-grad: never folds, like every other no-grad forward).  16-byte aligned weights assumed.
+extern "C" int dgvit_got_last_block_folds(const dgvit_config* cfg, int batch, float lkeep, int maps) {
+  Dims d;
+  if (make_dims(cfg, batch, d)) return -1;
+  alignas(16) static const float aligned = 0.f;
+  return last_block_fold(d, !dense_last_block(cfg) && !d.pool_mean, lkeep < 1.f, maps != 0, maps == 0, &aligned) ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------------------------- forward
 namespace {
 
@@ -327,6 +337,8 @@ int gemm_layer(const Fwd& f, int i, float*& x) {
   // `tok` = rows processed, `rs` = row step (in token rows) of those rows inside the (T, .) buffers.
   const bool last = !f.dense_last() && !d.pool_mean && i == d.L - 1;
   const int tok = last ? d.B : T, rs = last ? d.N : 1;
+  // ... and with to_qkv bias-free, K and V fold into token 0's query: no K / V GEMM at all (last_block.hip)
+  const bool fold = last_block_fold(d, last, ldrop, f.maps != nullptr, save != 0, lp[L_QKV]);
   // x = attn(LN(x)) + x   (GoalFormer.py:103, 36-37, 71-82)
   // D <= 64 (the shipped model): a 64-wide GEMM tile holds whole rows of the residual stream, so each LayerNorm runs inside the
   // epilogue of the GEMM that produces its input (to_out -> LN2, fc2 -> the next block's LN1; bit-identical to the LayerNorm
@@ -338,16 +350,23 @@ int gemm_layer(const Fwd& f, int i, float*& x) {
     sk.attach(p);
     TRY(gemm_f32(GEMM_NT, EPI_STORE, p, 1, st));
   } else {
-    GemmParams kv = gp(lb + w.ln1, d.D, lp[L_QKV] + (long long)d.I * d.D, d.D, lb + w.qkv + d.I, 3 * d.I, T, 2 * d.I, d.D);
-    sk.attach(kv);
-    TRY(gemm_f32(GEMM_NT, EPI_STORE, kv, 1, st));
+    if (!fold) {
+      GemmParams kv = gp(lb + w.ln1, d.D, lp[L_QKV] + (long long)d.I * d.D, d.D, lb + w.qkv + d.I, 3 * d.I, T, 2 * d.I, d.D);
+      sk.attach(kv);
+      TRY(gemm_f32(GEMM_NT, EPI_STORE, kv, 1, st));
+    }
     GemmParams q = gp(lb + w.ln1, rs * d.D, lp[L_QKV], d.D, lb + w.qkv, rs * 3 * d.I, tok, d.I, d.D);
     sk.attach(q);
     TRY(gemm_f32(GEMM_NT, EPI_STORE, q, 1, st));
   }
   const LayerDrop dr_attn = f.site(i, DROP_ATTN);
   float* lse = save || f.maps ? lb + w.lse : nullptr;   // (a maps call reads the row statistics back)
-  if (d.tiled)
+  if (fold) {
+    // u, r behind q in the frame's rows of the qkv slot; the probabilities (B, H, N) in the lse slot
+    float* u = lb + w.qkv + d.I;
+    TRY(goal_attention_fwd(lb + w.ln1, lp[L_QKV], lb + w.qkv, (long long)rs * 3 * d.I, lb + w.ao, (long long)rs * d.I, u, u + (long long)d.H * d.D,
+                           3ll * d.N * d.I, lse, d.B, d.N, d.H, d.dh, d.D, st));
+  } else if (d.tiled)
     TRY(attention_fwd_tiled(lb + w.qkv, lb + w.ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
   else
     TRY(attention_fwd(lb + w.qkv, lb + w.ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
@@ -532,6 +551,7 @@ int backward_layer(const Bwd& b, int i) {
   const float* xin = i == 0 ? ws + w.x0 : ws + w.layer0 + w.layer_stride * (i - 1) + w.xout;
   const bool last = !dense_last_block(b.cfg) && !d.pool_mean && i == d.L - 1;   // see gemm_layer: only rows b*N carry gradient here
   const int tok = last ? d.B : T, rs = last ? d.N : 1;
+  const bool fold = last_block_fold(d, last, ldrop, false, true, lp[L_QKV]);
   // ---- feed-forward branch: xout = fc2(gelu(fc1(ln2))) + xmid
   // (helper-stream kernels are ordered among themselves, so the slab scratch is reused safely; a `join` before
   //  a main-stream kernel that overwrites a buffer makes sure the wgrads that read it have finished)
@@ -579,11 +599,17 @@ int backward_layer(const Bwd& b, int i) {
   }
   // (no output projection: the gradient of the attention output is the residual-stream gradient itself, I == D)
   const LayerDrop dr_attn = b.site(i, DROP_ATTN);
-  if (d.tiled)
-    TRY(attention_bwd_tiled(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, scratch + s.delta, s.delta_floats, d.B, d.N, d.H,
+  const float* dout = d.proj ? dao : dx2;
+  const long long fs_fold = 3ll * d.N * d.I;            // (fold) frame stride of u, r in the qkv slot and of du, dr in dqkv, all behind q / dq
+  float* du = dqkv + d.I;
+  if (fold)   // dr, du, dq (into the Q columns of dqkv) and EVERY row of dln1 (what dkv W_kv was); W_q^T dq comes on top below
+    TRY(goal_attention_bwd_data(lb + w.ln1, lp[L_QKV], dout, (long long)rs * d.I, lb + w.qkv + d.I, fs_fold, lb + w.lse, du,
+                                du + (long long)d.H * d.D, fs_fold, dqkv, (long long)rs * 3 * d.I, dln, d.B, d.N, d.H, d.dh, d.D, st));
+  else if (d.tiled)
+    TRY(attention_bwd_tiled(lb + w.qkv, lb + w.ao, dout, lb + w.lse, dqkv, scratch + s.delta, s.delta_floats, d.B, d.N, d.H,
                             d.dh, last ? 1 : d.N, st, ldrop ? &dr_attn : nullptr));
   else
-    TRY(attention_bwd(lb + w.qkv, lb + w.ao, d.proj ? dao : dx2, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st,
+    TRY(attention_bwd(lb + w.qkv, lb + w.ao, dout, lb + w.lse, dqkv, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st,
                       ldrop ? &dr_attn : nullptr));
   TRY(b.fork());
   if (!last) {
@@ -595,11 +621,16 @@ int backward_layer(const Bwd& b, int i) {
     // dWq from the token-0 rows, dWk/dWv from all rows; dln1 = dkv Wkv (+ dq Wq on the token-0 rows)
     const long long nq_slabs = wgrad_scratch(d.I, d.D, tok);
     TRY(wgrad(dqkv, rs * 3 * d.I, lb + w.ln1, rs * d.D, lg[L_QKV], nullptr, d.I, d.D, tok, slabs + s.sl_qkv, nq_slabs, sw, gq));
-    TRY(wgrad(dqkv + d.I, 3 * d.I, lb + w.ln1, d.D, lg[L_QKV] ? lg[L_QKV] + (long long)d.I * d.D : nullptr, nullptr, 2 * d.I, d.D, T,
-              slabs + s.sl_qkv + nq_slabs, s.n_qkv - nq_slabs, sw, gq));
-    GemmParams kv = gp(dqkv + d.I, 3 * d.I, lp[L_QKV] + (long long)d.I * d.D, d.D, dln, d.D, T, d.D, 2 * d.I);
-    sk.attach(kv);
-    TRY(gemm_f32(GEMM_NN, EPI_STORE, kv, 1, st));
+    float* dwkv = lg[L_QKV] ? lg[L_QKV] + (long long)d.I * d.D : nullptr;
+    if (fold) {   // dW_k = sum_b q du^T, dW_v = sum_b do r^T: one launch, straight into rows I..3I (no slabs)
+      TRY(goal_attention_wgrad(lb + w.qkv, (long long)rs * 3 * d.I, dout, (long long)rs * d.I, du, fs_fold, lb + w.qkv + d.I + (long long)d.H * d.D,
+                               fs_fold, dwkv, d.B, d.H, d.dh, d.D, sw));
+    } else {
+      TRY(wgrad(dqkv + d.I, 3 * d.I, lb + w.ln1, d.D, dwkv, nullptr, 2 * d.I, d.D, T, slabs + s.sl_qkv + nq_slabs, s.n_qkv - nq_slabs, sw, gq));
+      GemmParams kv = gp(dqkv + d.I, 3 * d.I, lp[L_QKV] + (long long)d.I * d.D, d.D, dln, d.D, T, d.D, 2 * d.I);
+      sk.attach(kv);
+      TRY(gemm_f32(GEMM_NN, EPI_STORE, kv, 1, st));
+    }
     GemmParams q = gp(dqkv, rs * 3 * d.I, lp[L_QKV], d.D, dln, rs * d.D, tok, d.D, d.I);
     q.res = dln; q.ldr = rs * d.D;
     sk.attach(q);

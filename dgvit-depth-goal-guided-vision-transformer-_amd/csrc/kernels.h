@@ -26,6 +26,19 @@ int attention_bwd_tiled(const float*, const float*, const float*, const float*, 
 // (query 0: probs[b * frame_stride + h * N + k]) or DGVIT_MAPS_ALL (probs[b * frame_stride + (h * N + q) * N + k])
 int attention_probs(const float* qkv, const float* lse, float* probs, long long frame_stride, int B, int N, int H, int dh, int rows,
                     hipStream_t st);
+// last_block.hip: the last block's attention with K and V folded into token 0's query.  u, r (and du, dr): head h of frame
+// b at b * fs + h * D; q / o / dout / dq: B rows of I floats at their row strides; wqkv = to_qkv.weight (3I, D); p (B, H, N) or null.
+constexpr long long GOAL_POOL_LDS_MAX = 159 * 1024;      // what a goal_pool workgroup may take at all (the operator entry points)
+constexpr long long GOAL_POOL_LDS_BUDGET = 80 * 1024;    // ... and inside the encoder: two workgroups per CU (160 KB); C3 needs 54.5 KB
+long long goal_pool_lds_bytes(int N, int D, int H);
+bool goal_attention_supports(int N, int D, int H, int dh);
+int goal_attention_fwd(const float* xn, const float* wqkv, const float* q, long long ldq, float* o, long long ldo, float* u, float* r,
+                       long long fs_ur, float* p, int B, int N, int H, int dh, int D, hipStream_t st);
+int goal_attention_bwd_data(const float* xn, const float* wqkv, const float* dout, long long lddo, const float* u, long long fs_ur,
+                            const float* p, float* du, float* dr, long long fs_d, float* dq, long long lddq, float* dxn, int B, int N, int H,
+                            int dh, int D, hipStream_t st);
+int goal_attention_wgrad(const float* q, long long ldq, const float* dout, long long lddo, const float* du, long long fs_d, const float* r,
+                         long long fs_ur, float* dwkv, int B, int H, int dh, int D, hipStream_t st);
 int patchify(const float*, float*, int, int, int, int, int, hipStream_t);
 int add_rows(const float*, long long, const float*, long long, float*, long long, long long, int, hipStream_t);
 int goal_row(const float*, const float*, float*, int, int, int, hipStream_t);

@@ -56,6 +56,7 @@ DGVIT_KNOB(int, g_gemm_zfold, 1)                // weight-gradient GEMMs: k-slic
 DGVIT_KNOB(int, g_attn_q1, 1)                   // one-query (token 0) fp32 attention forward / backward on plain FMAs for N <= 64
 DGVIT_KNOB(int, g_attn_bf16_long, 3)           // bf16 attention at 225..288 tokens: bit 0 the persistent forward (>= 512 items), bit 1 nine-wave workgroups for nine tiles
 DGVIT_KNOB(int, g_attn_bf16_tiled_waves, 8)     // K / V-tiled bf16 attention: waves per workgroup = 32-row tiles of its block (4 or 8; 8 measured faster)
+DGVIT_KNOB(int, g_last_block_fold, 1)           // the last block's K / V folded into token 0's query (last_block.hip; 0: the K / V GEMMs and attn_q1)
 #ifdef DGVIT_DIAG
 extern long long g_gemm_persist_launches;       // launches that took the pipelined kernel
 #endif

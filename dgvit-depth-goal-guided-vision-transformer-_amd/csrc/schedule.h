@@ -143,6 +143,20 @@ inline int make_dims(const dgvit_config* c, int batch, Dims& d) {
   return DGVIT_OK;
 }
 
+// The last block's K / V fold (last_block.hip): gemm_layer and backward_layer both ask here, so a forward and its backward
+// cannot disagree.  `last` = the block is the pruned (token-0) last one; `maps` = an attention-maps call (always no-grad: the backward
+// never sees one).  u and r (du and dr) live behind q (dq) in the frame's own N x 3I region of the qkv (dqkv) buffer, p in the lse slot.
+// `wqkv` = the block's to_qkv.weight: the head-batched products read it with 16-byte loads.  `save` = the forward keeps its activations
+// for a backward: a no-grad forward keeps the K / V GEMM, so that its features stay bit-identical to those of a maps call
+// (dgvit_got_forward_maps, rows = DGVIT_MAPS_GOAL: tests/test_gpu_attention_maps.py), which needs K for its probabilities.
+inline bool last_block_fold(const Dims& d, bool last, bool ldrop, bool maps, bool save, const float* wqkv) {
+  KNOB_IF(g_last_block_fold) {
+    return last && save && !ldrop && !d.tiled && !maps && al16(wqkv) && goal_attention_supports(d.N, d.D, d.H, d.dh) &&
+           goal_pool_lds_bytes(d.N, d.D, d.H) <= GOAL_POOL_LDS_BUDGET && d.I + 2ll * d.H * d.D <= 3ll * d.N * d.I;
+  }
+  return false;
+}
+
 enum { P_POS = 0, P_PW = 1, P_PB = 2, P_RMS = 3, P_L0 = 4 };
 enum { L_LN1W = 0, L_LN1B, L_QKV, L_OUTW, L_OUTB, L_LN2W, L_LN2B, L_FC1W, L_FC1B, L_FC2W, L_FC2B };
 // the to_out slots of the parameter table are unused (may be NULL) when the attention has no output projection

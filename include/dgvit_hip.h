@@ -308,6 +308,28 @@ long long dgvit_attention_backward_tiled_scratch_floats(int B, int N, int H);
 int dgvit_attention_backward_tiled(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* scratch,
                                    long long scratch_floats, int B, int N, int H, int dh, int nq, void* stream);
 
+/* Goal-token attention without K or V (the encoder's last block, where only token 0's query is needed and to_qkv has no bias): with
+ * xn (B, N, D) the normalised tokens, wqkv (3*H*dh, D) = to_qkv.weight and q (B rows of H*dh floats, ldq floats apart) token 0's query,
+ *   u[b][h] = W_k,h^T q[b][h]   p[b][h] = softmax_t(dh^-1/2 u[b][h] . xn[b][t])   r[b][h] = sum_t p[b][h][t] xn[b][t]   o[b][h] = W_v,h r[b][h]
+ * forward writes u, r (B, H, D), p (B, H, N; NULL = not kept) and o (B rows, ldo apart) = what dgvit_attention_forward gives for query
+ * row 0 of qkv = xn wqkv^T.  backward takes dout (B rows, lddo apart) and writes dq (B rows, lddq apart), dxn (B, N, D) -- EVERY row, the
+ * gradient through K and V only: the caller adds W_q^T dq on the token-0 rows -- and dwkv (2*H*dh, D) = the gradient of rows H*dh.. of
+ * wqkv (overwritten; NULL = not wanted); scratch holds dgvit_goal_attention_scratch_floats(B, H, D) floats.  Sums run in a fixed
+ * order (no atomics).  dh 64 or 32, D a multiple of 4 up to 1024, N * D floats within 159 KB of LDS; pointers 16-byte aligned, strides
+ * multiples of 4. */
+long long dgvit_goal_attention_scratch_floats(int B, int H, int D);
+/* 1 when a training forward (save != 0) of the encoder and its backward run the last block this way for `cfg` at `batch` frames
+ * (token-0 last block, cls pool, no transformer dropout (lkeep == 1), not the K / V-tiled long-sequence attention, dim_head 32 or 64, a
+ * frame's N * dim tokens plus 2 * heads * N floats within 80 KB of LDS), 0 when they keep the K / V GEMMs, negative on a bad
+ * configuration.  No-grad forwards and attention-maps calls (maps != 0) never fold: their features stay bit-identical to each other.
+ * No buffer size depends on it. */
+int dgvit_got_last_block_folds(const dgvit_config* cfg, int batch, float layer_dropout_keep, int maps);
+int dgvit_goal_attention_forward(const float* xn, const float* wqkv, const float* q, long long ldq, float* o, long long ldo, float* u, float* r,
+                                 float* p, int B, int N, int H, int dh, int D, void* stream);
+int dgvit_goal_attention_backward(const float* xn, const float* wqkv, const float* q, long long ldq, const float* dout, long long lddo,
+                                  const float* u, const float* r, const float* p, float* dq, long long lddq, float* dxn, float* dwkv,
+                                  float* scratch, long long scratch_floats, int B, int N, int H, int dh, int D, void* stream);
+
 /* 'b (h p1) (w p2) -> b (h w) (p1 p2)' (GoalFormer.py:138) */
 int dgvit_patchify(const float* img, float* patches, int B, int image_h, int image_w, int patch_h, int patch_w,
                    void* stream);

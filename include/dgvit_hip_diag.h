@@ -90,6 +90,9 @@ void dgvit_set_gemm_bf16_l2_budget_kb(int kb);
 void dgvit_set_attention_bwd_single_pass(int on);
 /* 0: a one-query attention (the last block's token 0) runs on the MFMA tile kernels as before round 4; 1 (default): attn_q1_*_kernel */
 void dgvit_set_attention_single_query(int on);
+/* A/B knob: 1 (default) the pruned last block folds K and V into token 0's query where the shape allows it (last_block.hip: no K / V
+ * GEMM, no dW_kv / dkv W_kv GEMMs); 0 the K / V GEMMs and the one-query attention.  Same results up to summation order. */
+void dgvit_set_last_block_fold(int on);
 /* A/B knob, bf16 attention at 225 <= N <= 288 tokens: bit 0 the persistent forward (attn_fwd_bf16_stream288_kernel) for >= 512 items,
  * else the per-item kernel; bit 1 nine-wave workgroups (per-item forward, dq backward) for nine 32-token tiles, else eight waves with a second
  * round for one of them.  Default 3; -1 restores it.  Same results whatever the bits. */

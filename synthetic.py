@@ -66,12 +66,25 @@ def fwd_flops_per_frame(image, patch, dim, depth, heads, dim_head=64, mlp_dim=20
     return 2.0 * P * pd * dim + depth * (2.0 * N * dim * 3 * I + 4.0 * N * N * I + 2.0 * N * I * dim + 4.0 * N * dim * mlp_dim)
 
 
-def fwd_flops_per_frame_executed(image, patch, dim, depth, heads, dim_head=64, mlp_dim=2048, prune_last=True):
+def last_block_folds(N, dim, heads, dim_head=64):
+    """The shape part of the encoder's rule (schedule.h last_block_fold; dgvit_got_last_block_folds) for folding K and V of the pruned
+    last block into token 0's query: a frame's N x dim tokens + 2 * heads * N floats within 80 KB of LDS, u and r behind q in the
+    frame's rows of the qkv buffer.  (Transformer dropout, the long-sequence flag, maps calls and no-grad forwards switch it off at run time.)"""
+    np4, I = (N + 3) // 4 * 4, heads * dim_head
+    return (dim_head in (32, 64) and dim % 4 == 0 and (N * dim + max(4, 2 * heads) * np4) * 4 <= 80 * 1024
+            and I + 2 * heads * dim <= 3 * N * I)
+
+
+def fwd_flops_per_frame_executed(image, patch, dim, depth, heads, dim_head=64, mlp_dim=2048, prune_last=True, training=True):
     """The FLOPs the schedule really executes: with the last block pruned to token 0 (K and V for every token,
     Q / attention / to_out / feed-forward for one row per frame) the last layer costs
-    2*N*D*2I (K, V) + 2*D*I (Q) + 4*N*I (one query row) + 2*I*D + 4*D*M instead of the dense layer."""
+    2*N*D*2I (K, V) + 2*D*I (Q) + 4*N*I (one query row) + 2*I*D + 4*D*M instead of the dense layer; where K and V fold into the
+    query (training forwards, training=True) 3*2*D*I (Q, u, o) + 4*N*H*D (scores and the pooled rows r) + 2*I*D + 4*D*M.
+    No-grad forwards keep the K / V GEMM (training=False)."""
     P = (image[0] // patch[0]) * (image[1] // patch[1])
     pd, N, I = patch[0] * patch[1], P + 1, heads * dim_head
     layer = 2.0 * N * dim * 3 * I + 4.0 * N * N * I + 2.0 * N * I * dim + 4.0 * N * dim * mlp_dim
     last = 2.0 * N * dim * 2 * I + 2.0 * dim * I + 4.0 * N * I + 2.0 * I * dim + 4.0 * dim * mlp_dim
+    if training and last_block_folds(N, dim, heads, dim_head):
+        last = 3 * 2.0 * dim * I + 4.0 * N * heads * dim + 2.0 * I * dim + 4.0 * dim * mlp_dim
     return 2.0 * P * pd * dim + (depth - 1) * layer + (last if prune_last else layer)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B of library knobs on the C3 training step in ONE process (boxes differ by several %, so A/B across gpurun
-calls says nothing): python tools/ab_knobs.py grouped_reduce|wgrad_overlap|gemm_diagnostics [rounds] [value of the 1-arm]"""
+calls says nothing): python tools/ab_knobs.py grouped_reduce|wgrad_overlap|gemm_diagnostics|last_block_fold [rounds] [value of the 1-arm]
+[value of the 0-arm].  Both arms at the same value is an A/A run: the spread an A/B difference has to exceed."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -10,6 +11,7 @@ lib = dgvit_amd.diagnostic_library().__enter__()   # libdgvit_hip_diag.so: the A
 knob = sys.argv[1] if len(sys.argv) > 1 else "grouped_reduce"
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
 on_value = int(sys.argv[3]) if len(sys.argv) > 3 else 1      # value passed for the "1" arm (bit masks: gemm_diagnostics 8 = LDS-image epilogue)
+off_value = int(sys.argv[4]) if len(sys.argv) > 4 else 0     # ... and for the "0" arm (== on_value: A/A)
 if knob == "wgrad_overlap":      # a per-module schedule option now (dgvit_config.flags), not a library knob
     setter = lambda v: model.trans.set_schedule(wgrad_overlap=bool(v))
 else:
@@ -32,7 +34,7 @@ def step():
 res = {0: [], 1: []}
 for r in range(rounds):
     for v in (0, 1):
-        setter(on_value if v else 0)
+        setter(on_value if v else off_value)
         for _ in range(3):
             step()
         torch.cuda.synchronize()
@@ -43,4 +45,4 @@ for r in range(rounds):
         res[v].append((time.perf_counter() - t0) / 10 * 1e3)
 for v in (0, 1):
     xs = sorted(res[v])
-    print(f"{knob}={v}: median {xs[len(xs)//2]:.3f} ms  min {xs[0]:.3f}  all {[round(x, 3) for x in res[v]]}")
+    print(f"{knob}={on_value if v else off_value} (arm {v}): median {xs[len(xs)//2]:.3f} ms  min {xs[0]:.3f}  all {[round(x, 3) for x in res[v]]}")
