@@ -278,9 +278,10 @@ int launch_fwd_pipe(const float* qkv, float* out, float* lse, int B, int N, int 
   constexpr size_t lds = (size_t)2 * 64 * (DH + 4) * sizeof(float);
   const int items = B * H;
   const int grid = items < 4 * 256 ? items : 4 * 256;      // four resident workgroups per CU
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * B * H * (double)N * N * DH, stream);
-  hipLaunchKernelGGL(attn_fwd_pipe_kernel<DH>, dim3(grid), dim3(128), lds, stream, qkv, out, lse, N, H, scale, items);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * B * H * (double)N * N * DH, stream);
+    hipLaunchKernelGGL(attn_fwd_pipe_kernel<DH>, dim3(grid), dim3(128), lds, stream, qkv, out, lse, N, H, scale, items);
+  }
   DGVIT_CHECK_LAUNCH("attention_fwd_pipe");
   return DGVIT_OK;
 }
@@ -690,15 +691,11 @@ int launch_bwd64(const float* qkv, const float* o, const float* dout, const floa
                  hipStream_t stream) {
   constexpr size_t lds = (size_t)(2 * 64 * (DH + 4) + 64 * 68) * sizeof(float);   // 52 KB at dim_head 64: three workgroups per CU
   auto kern = attn_bwd64_kernel<DH>;
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "attention_bwd: %s", hipGetErrorString(e));
-    once.mark(bit);
+  TRY(allow_dynamic_lds<attn_bwd64_kernel<DH>>((int)lds, "attention_bwd"));
+  {
+    ProfileScope t(PROF_ATTN_BWD, 8.0 * B * H * (double)N * N * DH, stream);
+    hipLaunchKernelGGL(kern, dim3(B * H), dim3(256), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale);
   }
-  const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * B * H * (double)N * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(256), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale);
-  profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("attention_bwd64");
   return DGVIT_OK;
 }
@@ -816,9 +813,10 @@ __global__ void __launch_bounds__(256) attn_q1_bwd_kernel(const float* __restric
 template <int DH>
 int launch_q1_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, hipStream_t stream) {
   const int items = B * H;
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * items * (double)N * DH, stream);
-  hipLaunchKernelGGL(attn_q1_fwd_kernel<DH>, dim3((items + 3) / 4), dim3(256), 0, stream, qkv, out, lse, N, H, scale, items);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * items * (double)N * DH, stream);
+    hipLaunchKernelGGL(attn_q1_fwd_kernel<DH>, dim3((items + 3) / 4), dim3(256), 0, stream, qkv, out, lse, N, H, scale, items);
+  }
   DGVIT_CHECK_LAUNCH("attention_fwd (one query)");
   return DGVIT_OK;
 }
@@ -827,9 +825,10 @@ template <int DH>
 int launch_q1_bwd(const float* qkv, const float* o, const float* dout, const float* lse, float* dqkv, int B, int N, int H, float scale,
                   hipStream_t stream) {
   const int items = B * H;
-  const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * items * (double)N * DH, stream);
-  hipLaunchKernelGGL(attn_q1_bwd_kernel<DH>, dim3((items + 3) / 4), dim3(256), 0, stream, qkv, o, dout, lse, dqkv, N, H, scale, items);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_ATTN_BWD, 8.0 * items * (double)N * DH, stream);
+    hipLaunchKernelGGL(attn_q1_bwd_kernel<DH>, dim3((items + 3) / 4), dim3(256), 0, stream, qkv, o, dout, lse, dqkv, N, H, scale, items);
+  }
   DGVIT_CHECK_LAUNCH("attention_bwd (one query)");
   return DGVIT_OK;
 }
@@ -841,16 +840,11 @@ int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, fl
   const int NP = (N + 31) / 32 * 32;
   const size_t lds = (size_t)2 * NP * (DH + 4) * sizeof(float);
   auto kern = attn_fwd_kernel<DH, NW, NKT_CT, DROP>;
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    const int maxlds = 2 * MAX_TOKENS * (DH + 4) * (int)sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd: %s", hipGetErrorString(e));
-    once.mark(bit);
+  TRY((allow_dynamic_lds<attn_fwd_kernel<DH, NW, NKT_CT, DROP>>(2 * MAX_TOKENS * (DH + 4) * (int)sizeof(float), "attention_fwd")));
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * B * H * (double)nq * N * DH, stream);
+    hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, out, lse, N, H, scale, nq, drop);
   }
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, out, lse, N, H, scale, nq, drop);
-  profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("attention_fwd");
   return DGVIT_OK;
 }
@@ -861,16 +855,11 @@ int launch_bwd(const float* qkv, const float* o, const float* dout, const float*
   const int NP = (N + 31) / 32 * 32;
   const size_t lds = ((size_t)2 * NP * (DH + 4) + 2 * NP) * sizeof(float);
   auto kern = attn_bwd_kernel<DH, NW, NKT_CT, DROP>;
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    const int maxlds = (2 * MAX_TOKENS * (DH + 4) + 2 * MAX_TOKENS) * (int)sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, maxlds);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "attention_bwd: %s", hipGetErrorString(e));
-    once.mark(bit);
+  TRY((allow_dynamic_lds<attn_bwd_kernel<DH, NW, NKT_CT, DROP>>((2 * MAX_TOKENS * (DH + 4) + 2 * MAX_TOKENS) * (int)sizeof(float), "attention_bwd")));
+  {
+    ProfileScope t(PROF_ATTN_BWD, 8.0 * B * H * (double)nq * N * DH, stream);
+    hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale, nq, drop);
   }
-  const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(64 * NW), lds, stream, qkv, o, dout, lse, dqkv, N, H, scale, nq, drop);
-  profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("attention_bwd");
   return DGVIT_OK;
 }

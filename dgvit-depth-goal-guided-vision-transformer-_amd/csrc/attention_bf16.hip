@@ -123,7 +123,6 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_kernel(const bf16_t* __
 // is free for the next item's DMA), and after the compute (the next item has landed -- the loader wave waited for it -- and this
 // item's K / V buffers are free; the compute waves' output stores simply stay in flight).
 // Rows >= N read zero through the buffer range check (V must be finite there: its probabilities are exact zeros).
-typedef __attribute__((address_space(3))) void* attn_lds_ptr_t;
 template <bool HAS_LSE>
 __global__ void __launch_bounds__(512) attn_fwd_bf16_stream_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse,
                                                                    int N, int H, float scale, int nq, int nitems) {
@@ -158,11 +157,11 @@ __global__ void __launch_bounds__(512) attn_fwd_bf16_stream_kernel(const bf16_t*
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base + 2 * I), 0, bytes, 0x00020000);
     unsigned char* kd = smem + buf * IMG + sw * 1024, *vd = smem + (2 + buf) * IMG + sw * 1024, *qd = Qs + sw * 1024;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (attn_lds_ptr_t)(kd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
+    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(kd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (attn_lds_ptr_t)(vd + j * 8192), 16, offv + j * dstep, 0, 0, 0);
+    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(vd + j * 8192), 16, offv + j * dstep, 0, 0, 0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (attn_lds_ptr_t)(qd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
+    for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (lds_ptr_t)(qd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
   };
   const unsigned fsw = (unsigned)((li >> 1) & 7);
   const int nqt = (nq + 31) / 32;
@@ -254,8 +253,8 @@ __global__ void __launch_bounds__(640) attn_fwd_bf16_stream288_kernel(const bf16
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base + 2 * I), 0, bytes, 0x00020000);
     unsigned char* kd = smem + buf * IMG + sw * 1024, *vd = smem + (2 + buf) * IMG + sw * 1024;
     const int passes = sw < 4 ? 5 : 4;   // wave-uniform
-    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (attn_lds_ptr_t)(kd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
-    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (attn_lds_ptr_t)(vd + j * 8192), 16, offv + j * dstep, 0, 0, 0);
+    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(kd + j * 8192), 16, offk + j * dstep, 0, 0, 0);
+    for (int j = 0; j < passes; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(vd + j * 8192), 16, offv + j * dstep, 0, 0, 0);
   };
   const unsigned fsw = (unsigned)((li >> 1) & 7);
   const int nqt = (nq + 31) / 32;
@@ -466,13 +465,6 @@ __global__ void __launch_bounds__(512) attn_bwd_dkv_bf16_kernel(const bf16_t* __
 
 }  // namespace
 
-// raise the dynamic-LDS limit of each kernel (once per device, by the callers' DeviceOnce)
-static bool raise_lds(const void* const* kerns, int n, int bytes) {
-  for (int i = 0; i < n; ++i)
-    if (hipFuncSetAttribute(kerns[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-  return true;
-}
-
 int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
   DGVIT_CHECK_ARG(qkv && out && B > 0 && H > 0, "attention_bf16: bad arguments");
   DGVIT_CHECK_ARG(dh == 64, "attention_bf16: dim_head=%d unsupported (64)", dh);
@@ -482,49 +474,28 @@ int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N,
   const size_t lds = (size_t)2 * NP * 128;
   const float scale = 1.0f / sqrtf((float)dh);
   const double flops = 4.0 * (double)nq * N * dh * H * B;
-  const int slot = profile_begin(PROF_ATTN_FWD, flops, st);
   // many items of more than four query tiles (BASELINE config 5: N = 197, 5280 items): the persistent kernel with LDS-DMA prefetch
   const long long items = (long long)B * H;
-  static int cached_cus = 0;
-  if (!cached_cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cached_cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  const int cus = cached_cus;
   if (N <= 224 && (N + 31) / 32 > 4 && items >= 512 && 3ll * H * dh * 2 * 256 < (1ll << 31)) {
-    static DeviceOnce once;
-    if (const unsigned long long bit = once.pending()) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_bf16_stream_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_bf16_stream_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd_bf16: cannot raise the dynamic LDS limit");
-      once.mark(bit);
-    }
-    const unsigned grid = (unsigned)(items < cus ? items : cus);
+    TRY((allow_dynamic_lds<attn_fwd_bf16_stream_kernel<true>, attn_fwd_bf16_stream_kernel<false>>(160 * 1024, "attention_fwd_bf16")));
+    const int cus = device_cus();
+    const unsigned grid = (unsigned)(items < cus ? items : cus);   // one persistent workgroup per CU
+    ProfileScope t(PROF_ATTN_FWD, flops, st);
     if (lse) hipLaunchKernelGGL((attn_fwd_bf16_stream_kernel<true>), dim3(grid), dim3(512), 160 * 1024, st, qkv, out, lse, N, H, scale, nq, (int)items);
     else hipLaunchKernelGGL((attn_fwd_bf16_stream_kernel<false>), dim3(grid), dim3(512), 160 * 1024, st, qkv, out, lse, N, H, scale, nq, (int)items);
   } else if (N > 224 && (g_attn_bf16_long & 1) && items >= 512 && 3ll * H * dh * 2 * 288 < (1ll << 31)) {
     constexpr int LDS288 = 4 * 288 * 128;   // K, V double-buffered: 144 KB
-    static DeviceOnce once;
-    if (const unsigned long long bit = once.pending()) {
-      const void* k[2] = {reinterpret_cast<const void*>(&attn_fwd_bf16_stream288_kernel<true>), reinterpret_cast<const void*>(&attn_fwd_bf16_stream288_kernel<false>)};
-      if (!raise_lds(k, 2, LDS288)) return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd_bf16: cannot raise the dynamic LDS limit");
-      once.mark(bit);
-    }
-    const unsigned grid = (unsigned)(items < cus ? items : cus);
+    TRY((allow_dynamic_lds<attn_fwd_bf16_stream288_kernel<true>, attn_fwd_bf16_stream288_kernel<false>>(LDS288, "attention_fwd_bf16")));
+    const int cus = device_cus();
+    const unsigned grid = (unsigned)(items < cus ? items : cus);   // one persistent workgroup per CU
+    ProfileScope t(PROF_ATTN_FWD, flops, st);
     if (lse) hipLaunchKernelGGL((attn_fwd_bf16_stream288_kernel<true>), dim3(grid), dim3(640), LDS288, st, qkv, out, lse, N, H, scale, nq, (int)items);
     else hipLaunchKernelGGL((attn_fwd_bf16_stream288_kernel<false>), dim3(grid), dim3(640), LDS288, st, qkv, out, lse, N, H, scale, nq, (int)items);
   } else {
-    if (lds > 64 * 1024) {   // N > 256: K + V images above the default 64 KB
-      static DeviceOnce once;
-      if (const unsigned long long bit = once.pending()) {
-        const void* k[3] = {reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<4>), reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<8>),
-                            reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<9>)};
-        if (!raise_lds(k, 3, 2 * 288 * 128)) return dgvit_set_error(DGVIT_ERR_HIP, "attention_fwd_bf16: cannot raise the dynamic LDS limit");
-        once.mark(bit);
-      }
-    }
+    if (lds > 64 * 1024)   // N > 256: K + V images above the default 64 KB
+      TRY((allow_dynamic_lds<attn_fwd_bf16_kernel<4>, attn_fwd_bf16_kernel<8>, attn_fwd_bf16_kernel<9>>(2 * 288 * 128, "attention_fwd_bf16")));
     const int nqt = (nq + 31) / 32;
+    ProfileScope t(PROF_ATTN_FWD, flops, st);
     if (nqt > 8 && (g_attn_bf16_long & 2))
       hipLaunchKernelGGL((attn_fwd_bf16_kernel<9>), dim3((unsigned)((long long)B * H)), dim3(576), lds, st, qkv, out, lse, N, H, scale, nq);
     else if (nqt > 4)
@@ -532,7 +503,6 @@ int attention_fwd_bf16(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N,
     else
       hipLaunchKernelGGL((attn_fwd_bf16_kernel<4>), dim3((unsigned)((long long)B * H)), dim3(256), lds, st, qkv, out, lse, N, H, scale, nq);
   }
-  profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("attn_fwd_bf16_kernel");
   return DGVIT_OK;
 }
@@ -546,26 +516,21 @@ int attention_bwd_bf16(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout,
   const int NP = (N + 31) / 32 * 32;
   const size_t lds_q = (size_t)2 * NP * 128 + (size_t)64 * (NP + 8) * 2;                            // 109 KB at NP = 288
   const size_t lds_kv = (size_t)2 * NP * 128 + (size_t)2 * 64 * (NP + 8) * 2 + (size_t)2 * NP * 4;  // 148 KB at NP = 288
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    const void* kq[2] = {reinterpret_cast<const void*>(&attn_bwd_dq_bf16_kernel<8>), reinterpret_cast<const void*>(&attn_bwd_dq_bf16_kernel<9>)};
-    const void* kkv[1] = {reinterpret_cast<const void*>(&attn_bwd_dkv_bf16_kernel)};
-    if (!raise_lds(kq, 2, 120 * 1024) || !raise_lds(kkv, 1, 160 * 1024))
-      return dgvit_set_error(DGVIT_ERR_HIP, "attention_bwd_bf16: cannot raise the dynamic LDS limit");
-    once.mark(bit);
-  }
+  TRY((allow_dynamic_lds<attn_bwd_dq_bf16_kernel<8>, attn_bwd_dq_bf16_kernel<9>>(120 * 1024, "attention_bwd_bf16")));
+  TRY((allow_dynamic_lds<attn_bwd_dkv_bf16_kernel>(160 * 1024, "attention_bwd_bf16")));
   const float scale = 1.0f / sqrtf((float)dh);
   const double flops = 10.0 * (double)N * N * dh * H * B;   // 2.5 x forward
-  const int slot = profile_begin(PROF_ATTN_BWD, flops, st);
-  if (NP > 256 && (g_attn_bf16_long & 2))
-    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<9>), dim3((unsigned)((long long)B * H)), dim3(576), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
-                       H, scale);
-  else
-    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<8>), dim3((unsigned)((long long)B * H)), dim3(512), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
-                       H, scale);
-  hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, dim3((unsigned)((long long)B * H)), dim3(512), lds_kv, st, qkv, dout, lse, delta, dqkv, N, H,
-                     scale);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_ATTN_BWD, flops, st);
+    if (NP > 256 && (g_attn_bf16_long & 2))
+      hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<9>), dim3((unsigned)((long long)B * H)), dim3(576), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
+                         H, scale);
+    else
+      hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<8>), dim3((unsigned)((long long)B * H)), dim3(512), lds_q, st, qkv, out, dout, lse, dqkv, delta, N,
+                         H, scale);
+    hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, dim3((unsigned)((long long)B * H)), dim3(512), lds_kv, st, qkv, dout, lse, delta, dqkv, N, H,
+                       scale);
+  }
   DGVIT_CHECK_LAUNCH("attention_bwd_bf16");
   return DGVIT_OK;
 }

@@ -337,11 +337,12 @@ int tiled_grid(const char* what, int B, int H, int rows, int block, long long& g
 template <int NW>
 int launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
   long long grid;
-  if (int rc = tiled_grid("attention_fwd_bf16_tiled", B, H, nq, 32 * NW, grid)) return rc;
+  TRY(tiled_grid("attention_fwd_bf16_tiled", B, H, nq, 32 * NW, grid));
   const float scale = 1.0f / sqrtf((float)dh);
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * (double)nq * N * dh * H * B, st);
-  hipLaunchKernelGGL((attn_fwd_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_FWD, st, qkv, out, lse, N, H, scale, nq);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * (double)nq * N * dh * H * B, st);
+    hipLaunchKernelGGL((attn_fwd_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_FWD, st, qkv, out, lse, N, H, scale, nq);
+  }
   DGVIT_CHECK_LAUNCH("attention_fwd_bf16_tiled");
   return DGVIT_OK;
 }
@@ -350,20 +351,16 @@ template <int NW>
 int launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B, int N, int H,
                int dh, hipStream_t st) {
   long long grid;
-  if (int rc = tiled_grid("attention_bwd_bf16_tiled", B, H, N, 32 * NW, grid)) return rc;
-  static DeviceOnce once;   // (the first call is made outside any graph capture: hipFuncSetAttribute is not a stream operation)
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_bf16_tiled_kernel<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "attention_bwd_bf16_tiled: cannot raise the dynamic LDS limit");
-    once.mark(bit);
-  }
+  TRY(tiled_grid("attention_bwd_bf16_tiled", B, H, N, 32 * NW, grid));
+  TRY(allow_dynamic_lds<attn_bwd_dkv_bf16_tiled_kernel<NW>>(LDS_DKV, "attention_bwd_bf16_tiled"));
   const float scale = 1.0f / sqrtf((float)dh);
-  const int slot = profile_begin(PROF_ATTN_BWD, 10.0 * (double)N * N * dh * H * B, st);   // 2.5 x forward
-  hipLaunchKernelGGL((attn_bwd_dq_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DQ, st, qkv, out, dout, lse, dqkv, delta, N, H,
-                     scale);
-  hipLaunchKernelGGL((attn_bwd_dkv_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DKV, st, qkv, dout, lse, (const float*)delta,
-                     dqkv, N, H, scale);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_ATTN_BWD, 10.0 * (double)N * N * dh * H * B, st);   // 2.5 x forward
+    hipLaunchKernelGGL((attn_bwd_dq_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DQ, st, qkv, out, dout, lse, dqkv, delta, N, H,
+                       scale);
+    hipLaunchKernelGGL((attn_bwd_dkv_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DKV, st, qkv, dout, lse, (const float*)delta,
+                       dqkv, N, H, scale);
+  }
   DGVIT_CHECK_LAUNCH("attention_bwd_bf16_tiled");
   return DGVIT_OK;
 }

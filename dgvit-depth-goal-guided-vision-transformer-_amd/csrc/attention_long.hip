@@ -25,12 +25,6 @@
 
 namespace {
 
-#define TRY_TILED(expr)  \
-  do {                   \
-    int rc_ = (expr);    \
-    if (rc_) return rc_; \
-  } while (0)
-
 constexpr int LQ = 128;   // rows of the workgroup's own block (4 waves x 32)
 constexpr int LK = 64;    // rows of one streamed tile
 
@@ -394,27 +388,17 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dkv_tiled_kernel(const float*
   }
 }
 
-template <typename K>
-int allow_lds(K kern, size_t lds, DeviceOnce& once, const char* what) {
-  if (const unsigned long long bit = once.pending()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-    once.mark(bit);
-  }
-  return DGVIT_OK;
-}
-
 template <int DH, bool DROP>
 int launch_fwd_tiled(const float* qkv, float* out, float* lse, int B, int N, int H, float scale, int nq, const LayerDrop& drop,
                      hipStream_t stream) {
   constexpr size_t lds = (size_t)2 * 2 * LK * (DH + 4) * sizeof(float);
   auto kern = attn_fwd_tiled_kernel<DH, DROP>;
-  static DeviceOnce once;
-  TRY_TILED(allow_lds(kern, lds, once, "attention_fwd_tiled"));
+  TRY((allow_dynamic_lds<attn_fwd_tiled_kernel<DH, DROP>>((int)lds, "attention_fwd_tiled")));
   const long long grid = (long long)B * H * ((nq + LQ - 1) / LQ);
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, qkv, out, lse, N, H, scale, nq, drop);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * B * H * (double)nq * N * DH, stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, qkv, out, lse, N, H, scale, nq, drop);
+  }
   DGVIT_CHECK_LAUNCH("attention_fwd_tiled");
   return DGVIT_OK;
 }
@@ -426,14 +410,14 @@ int launch_bwd_tiled(const float* qkv, const float* o, const float* dout, const 
   constexpr size_t lds_dkv = (size_t)2 * (2 * LK * (DH + 4) + 2 * LK) * sizeof(float);
   auto kdq = attn_bwd_dq_tiled_kernel<DH, DROP>;
   auto kdkv = attn_bwd_dkv_tiled_kernel<DH, DROP>;
-  static DeviceOnce once_dq, once_dkv;
-  TRY_TILED(allow_lds(kdq, lds_dq, once_dq, "attention_bwd_tiled"));
-  TRY_TILED(allow_lds(kdkv, lds_dkv, once_dkv, "attention_bwd_tiled"));
+  TRY((allow_dynamic_lds<attn_bwd_dq_tiled_kernel<DH, DROP>>((int)lds_dq, "attention_bwd_tiled")));
+  TRY((allow_dynamic_lds<attn_bwd_dkv_tiled_kernel<DH, DROP>>((int)lds_dkv, "attention_bwd_tiled")));
   const long long gq = (long long)B * H * ((nq + LQ - 1) / LQ), gk = (long long)B * H * ((N + LQ - 1) / LQ);
-  const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * B * H * (double)nq * N * DH, stream);
-  hipLaunchKernelGGL(kdq, dim3((unsigned)gq), dim3(256), lds_dq, stream, qkv, o, dout, lse, dqkv, delta, N, H, scale, nq, drop);
-  hipLaunchKernelGGL(kdkv, dim3((unsigned)gk), dim3(256), lds_dkv, stream, qkv, dout, lse, (const float*)delta, dqkv, N, H, scale, nq, drop);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_ATTN_BWD, 8.0 * B * H * (double)nq * N * DH, stream);
+    hipLaunchKernelGGL(kdq, dim3((unsigned)gq), dim3(256), lds_dq, stream, qkv, o, dout, lse, dqkv, delta, N, H, scale, nq, drop);
+    hipLaunchKernelGGL(kdkv, dim3((unsigned)gk), dim3(256), lds_dkv, stream, qkv, dout, lse, (const float*)delta, dqkv, N, H, scale, nq, drop);
+  }
   DGVIT_CHECK_LAUNCH("attention_bwd_tiled");
   return DGVIT_OK;
 }
@@ -450,7 +434,7 @@ int check_tiled(const char* what, const float* qkv, int B, int N, int H, int dh,
 }  // namespace
 
 int attention_fwd_tiled(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t stream, const LayerDrop* drop) {
-  TRY_TILED(check_tiled("attention_fwd_tiled", qkv, B, N, H, dh, nq));
+  TRY(check_tiled("attention_fwd_tiled", qkv, B, N, H, dh, nq));
   DGVIT_CHECK_ARG(out, "attention_fwd_tiled: bad arguments");
   const float scale = 1.0f / sqrtf((float)dh);
   if (drop && drop->keep < 1.f) {
@@ -467,7 +451,7 @@ long long attention_bwd_tiled_scratch(int B, int N, int H) { return (long long)B
 
 int attention_bwd_tiled(const float* qkv, const float* o, const float* dout, const float* lse, float* dqkv, float* scratch,
                         long long scratch_floats, int B, int N, int H, int dh, int nq, hipStream_t stream, const LayerDrop* drop) {
-  TRY_TILED(check_tiled("attention_bwd_tiled", qkv, B, N, H, dh, nq));
+  TRY(check_tiled("attention_bwd_tiled", qkv, B, N, H, dh, nq));
   DGVIT_CHECK_ARG(o && dout && lse && dqkv && scratch, "attention_bwd_tiled: bad arguments");
   if (scratch_floats < attention_bwd_tiled_scratch(B, N, H))
     return dgvit_set_error(DGVIT_ERR_WORKSPACE, "attention_bwd_tiled: scratch %lld < %lld floats", scratch_floats, attention_bwd_tiled_scratch(B, N, H));

@@ -137,7 +137,7 @@ int check_probs(const void* qkv, const float* lse, const float* probs, int B, in
 
 int attention_probs(const float* qkv, const float* lse, float* probs, long long frame_stride, int B, int N, int H, int dh, int rows,
                     hipStream_t st) {
-  if (const int rc = check_probs(qkv, lse, probs, B, N, H, dh, rows)) return rc;
+  TRY(check_probs(qkv, lse, probs, B, N, H, dh, rows));
   DGVIT_CHECK_ARG(dh == 64 || dh == 32, "attention maps: dim_head=%d unsupported (64 or 32)", dh);
   return dh == 64 ? launch_probs<64>(qkv, lse, probs, frame_stride, B, N, H, rows, st)
                   : launch_probs<32>(qkv, lse, probs, frame_stride, B, N, H, rows, st);
@@ -145,7 +145,7 @@ int attention_probs(const float* qkv, const float* lse, float* probs, long long 
 
 int attention_probs_bf16(const bf16_t* qkv, const float* lse, float* probs, long long frame_stride, int B, int N, int H, int dh, int rows,
                          hipStream_t st) {
-  if (const int rc = check_probs(qkv, lse, probs, B, N, H, dh, rows)) return rc;
+  TRY(check_probs(qkv, lse, probs, B, N, H, dh, rows));
   DGVIT_CHECK_ARG(dh == 64, "attention maps (bf16): dim_head=%d unsupported (64)", dh);
   return launch_probs<64>(qkv, lse, probs, frame_stride, B, N, H, rows, st);
 }

@@ -8,6 +8,22 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float fx4 __attribute__((ext_vector_type(4)));
 
+// ---- device helpers of the LDS-DMA kernels (gemm_bf16.hip, gemm_bf16_stream.hip, attention_bf16.hip)
+typedef __attribute__((address_space(3))) void* lds_ptr_t;   // the LDS operand of __builtin_amdgcn_raw_ptr_buffer_load_lds
+constexpr unsigned BUF_OOB = 0x80000000u;                     // a buffer offset past every range: the load gives zeros, the store is dropped
+
+__device__ __forceinline__ int xcd_chunk(int id, int n) {
+  // blocks are dealt round-robin over the 8 XCDs: give each XCD one contiguous chunk of the tile grid (bijective)
+  const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 // GELU for outputs that are rounded to bf16: x * sigmoid(x (c0 + c1 x^2 + c2 x^4)) with the coefficients fitted (minimax over |x| <= 12) to the
 // erf form x Phi(x): |difference| <= 2.6e-5 everywhere (a bf16 ulp at 1.0 is 7.8e-3), exact 0 at 0 and the exact limits x and -0 in the tails
 // (x^2 is clamped at 64, beyond which the sigmoid has saturated).  5 packed + 1 plain + 4 transcendental VALU instructions per PAIR of values

@@ -627,15 +627,11 @@ size_t mlp_block_lds(int D) {
 template <int NKT>
 int launch_attn(const AttnBlockArgs& a, hipStream_t st) {
   const size_t lds = attn_block_lds(NKT, a.D, a.dh);
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_block_kernel<NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "attn_block_kernel: hipFuncSetAttribute failed");
-    once.mark(bit);
+  TRY(allow_dynamic_lds<attn_block_kernel<NKT>>(160 * 1024, "attn_block_kernel"));
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(attn_block_kernel<NKT>, dim3(a.B * a.H * a.NQ), dim3(256), lds, st, a);
   }
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(attn_block_kernel<NKT>, dim3(a.B * a.H * a.NQ), dim3(256), lds, st, a);
-  profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("attn_block_kernel");
   return DGVIT_OK;
 }
@@ -689,14 +685,12 @@ int block_path_layer(const float* x, const float* ln1, float* xout, float* ln1_o
 #ifdef DGVIT_DIAG
   aa.stamps = g_block_stamp_now ? g_block_stamps : nullptr;
 #endif
-  int rc;
   switch (NKT) {
-    case 1: rc = launch_attn<1>(aa, st); break;
-    case 2: rc = launch_attn<2>(aa, st); break;
-    case 3: rc = launch_attn<3>(aa, st); break;
-    default: rc = launch_attn<4>(aa, st); break;
+    case 1: TRY(launch_attn<1>(aa, st)); break;
+    case 2: TRY(launch_attn<2>(aa, st)); break;
+    case 3: TRY(launch_attn<3>(aa, st)); break;
+    default: TRY(launch_attn<4>(aa, st)); break;
   }
-  if (rc) return rc;
   MlpBlockArgs ma = {};
   ma.tok = token0_only ? B : B * N; ma.N = N; ma.D = D; ma.H = H; ma.M = M; ma.C = M / BHC; ma.NQ = aa.NQ; ma.rstep = token0_only ? N : 1;
   ma.x = x; ma.apart = slabs; ma.bout = lp[L_OUTB]; ma.ln2w = lp[L_LN2W]; ma.ln2b = lp[L_LN2B];
@@ -707,12 +701,7 @@ int block_path_layer(const float* x, const float* ln1, float* xout, float* ln1_o
 #endif
   ma.out = xout; ma.lnw = next_ln ? next_ln[0] : nullptr; ma.lnb = next_ln ? next_ln[1] : nullptr; ma.ln_out = ln1_out;
   if (rms_g && feat && token0_only) { ma.rms_g = rms_g; ma.feat = feat; }
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "mlp_block_kernel: hipFuncSetAttribute failed");
-    once.mark(bit);
-  }
+  TRY(allow_dynamic_lds<mlp_block_kernel>(160 * 1024, "mlp_block_kernel"));
   const int grid = ((ma.tok + 31) / 32) * ma.C;
   // Up to one workgroup per CU (a dynamic-LDS request above half the CU's 160 KB keeps a second one out): the last arriver reads the
   // other workgroups' write-through partials with sc1 loads instead of an agent-scope acquire -- the form MI355X_MICROARCH.md measures
@@ -722,9 +711,10 @@ int block_path_layer(const float* x, const float* ln1, float* xout, float* ln1_o
   size_t lds = mlp_block_lds(D);
   ma.sc1_reads = grid <= 256 ? 1 : 0;
   if (ma.sc1_reads && lds < 82 * 1024) lds = 82 * 1024;
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(mlp_block_kernel, dim3(grid), dim3(256), lds, st, ma);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(mlp_block_kernel, dim3(grid), dim3(256), lds, st, ma);
+  }
   DGVIT_CHECK_LAUNCH("mlp_block_kernel");
   return DGVIT_OK;
 }

@@ -3,17 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "../../include/dgvit_hip.h"
 #include "knobs.h"
+#include "launch.h"   // dgvit_set_error, TRY / HIP_TRY, allow_dynamic_lds, device_cus, ProfileScope
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---- error reporting (thread-local message, negative return codes from include/dgvit_hip.h) ------
-int dgvit_set_error(int code, const char* fmt, ...);
-
+// ---- error reporting (thread-local message, negative return codes from include/dgvit_hip.h; dgvit_set_error: launch.h) ------
 #define DGVIT_CHECK_ARG(cond, ...)                                   \
   do {                                                               \
     if (!(cond)) return dgvit_set_error(DGVIT_ERR_ARG, __VA_ARGS__); \
@@ -26,20 +23,6 @@ int dgvit_set_error(int code, const char* fmt, ...);
   } while (0)
 
 inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }   // float4 accesses need it
-
-// Kernel attributes (the dynamic-LDS limit above 64 KB) are per DEVICE: a flag per device ordinal, set on the first launch on
-// that device (a process-wide `static bool` would leave a second GPU of a single-process host without the attribute).
-// Racing threads may both set the attribute: harmless, it is idempotent.
-struct DeviceOnce {
-  std::atomic<unsigned long long> done{0};
-  unsigned long long pending() const {    // 0: already done on the current device, else the device's bit for mark()
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const unsigned long long bit = 1ull << (dev & 63);
-    return (done.load(std::memory_order_relaxed) & bit) ? 0ull : bit;
-  }
-  void mark(unsigned long long bit) { done.fetch_or(bit, std::memory_order_relaxed); }
-};
 
 // ---- GEMM -----------------------------------------------------------------------------------
 // C[m][n] = sum_k Aop[m][k] * Bop[k][n]   (fp32 in, fp32 accumulate on v_mfma_f32_32x32x2_f32)
@@ -109,11 +92,6 @@ struct GemmSplitPlan {
 // the split decision for C (M x N) = A B over K with the tile the automatic choice picks; used for sizing and at launch
 GemmSplitPlan gemm_split_plan(int layout, int M, int N, int K);
 GemmSplitPlan gemm_split_plan_gather(int M, int N, int K);   // A gathered from an image: the 64 x 64 x 32 tile
-
-// live timing hooks (profile.hip); slot < 0 = not recording
-int profile_begin(int kind, double work, hipStream_t st);
-void profile_end(int slot, hipStream_t st);
-enum { PROF_GEMM = 0, PROF_ATTN_FWD = 1, PROF_ATTN_BWD = 2, PROF_OTHER = 3 };
 
 int gemm_f32(int layout, int epi, const GemmParams& p, int nsplit, hipStream_t stream);
 

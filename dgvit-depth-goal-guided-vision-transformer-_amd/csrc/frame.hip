@@ -276,17 +276,12 @@ size_t mlp_lds(int NP, int D) { return sizeof(float) * ((size_t)NP * (D + 4) + (
 template <int NKT>
 int launch_pair(const FrameArgs& aa, const FrameArgs& ab, hipStream_t st) {
   const size_t la = attn_lds(aa.NP, aa.D, aa.dh), lb = mlp_lds(ab.NP, ab.D);
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(frame_attn_kernel<NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlp_kernel<NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "frame kernels: hipFuncSetAttribute failed");
-    once.mark(bit);
+  TRY((allow_dynamic_lds<frame_attn_kernel<NKT>, frame_mlp_kernel<NKT>>(160 * 1024, "frame kernels")));
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(frame_attn_kernel<NKT>, dim3(aa.B * aa.H), dim3(256), la, st, aa);
+    hipLaunchKernelGGL(frame_mlp_kernel<NKT>, dim3(ab.B * ab.C), dim3(256), lb, st, ab);
   }
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(frame_attn_kernel<NKT>, dim3(aa.B * aa.H), dim3(256), la, st, aa);
-  hipLaunchKernelGGL(frame_mlp_kernel<NKT>, dim3(ab.B * ab.C), dim3(256), lb, st, ab);
-  profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("frame kernels");
   return DGVIT_OK;
 }
@@ -332,14 +327,12 @@ int frame_path_forward(const float* x0, const float* const* params, int L, float
     ab.x_out = XM;
     ab.lnw = lp[L_LN2W]; ab.lnb = lp[L_LN2B]; ab.w1 = lp[L_FC1W]; ab.b1 = lp[L_FC1B]; ab.w2 = lp[L_FC2W];
     ab.part_out = PB;
-    int rc;
     switch (NP / 32) {
-      case 1: rc = launch_pair<1>(aa, ab, st); break;
-      case 2: rc = launch_pair<2>(aa, ab, st); break;
-      case 3: rc = launch_pair<3>(aa, ab, st); break;
-      default: rc = launch_pair<4>(aa, ab, st); break;
+      case 1: TRY(launch_pair<1>(aa, ab, st)); break;
+      case 2: TRY(launch_pair<2>(aa, ab, st)); break;
+      case 3: TRY(launch_pair<3>(aa, ab, st)); break;
+      default: TRY(launch_pair<4>(aa, ab, st)); break;
     }
-    if (rc) return rc;
   }
   hipLaunchKernelGGL(frame_final_kernel, dim3((B + 3) / 4), dim3(256), 0, st, XM, params[P_L0 + PER * (L - 1) + L_FC2B], PB, C, params[P_RMS], feat, B, N, D);
   DGVIT_CHECK_LAUNCH("frame_final_kernel");

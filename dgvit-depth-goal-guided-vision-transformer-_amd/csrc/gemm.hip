@@ -770,13 +770,8 @@ int launch(const GemmParams& p0, int nsplit, hipStream_t stream) {
   constexpr int A_TILE = AKC ? BM * (BK + 4) : BK * (BM + 4);
   constexpr int B_TILE = BKC ? BN * (BK + 4) : BK * (BN + 4);
   constexpr size_t lds = 2 * (A_TILE + B_TILE) * sizeof(float);
-  static DeviceOnce once;
   auto kern = gemm_f32_kernel<T, LAYOUT, VEC, EPI, GATHER>;
-  if (const unsigned long long bit = once.pending()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    once.mark(bit);
-  }
+  TRY((allow_dynamic_lds<gemm_f32_kernel<T, LAYOUT, VEC, EPI, GATHER>>(160 * 1024, "gemm")));
   GemmParams p = p0;
   if (p.ln_y) {   // fused LayerNorm: the whole output row must sit in this tile's LDS image, vector path
     DGVIT_CHECK_ARG(EPI == EPI_STORE && VEC == 4 && !GATHER && LAYOUT != GEMM_TN && p.evec && p.N == BN && BN == 64 && p.c_rgrp == 0,
@@ -819,9 +814,10 @@ int launch(const GemmParams& p0, int nsplit, hipStream_t stream) {
     p.zsplit = nsplit;
     grid = dim3((unsigned)(blocks * nsplit), 1, 1);
   }
-  const int slot = profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, stream);
-  hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds + (size_t)g_gemm_lds_pad, stream, p);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_GEMM, 2.0 * p.M * p.N * p.K, stream);
+    hipLaunchKernelGGL(kern, grid, dim3(T::NT), lds + (size_t)g_gemm_lds_pad, stream, p);
+  }
   DGVIT_CHECK_LAUNCH("gemm_f32_kernel");
   return DGVIT_OK;
 }

@@ -28,14 +28,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ int xcd_chunk(int id, int n) {
-  // blocks are dealt round-robin over the 8 XCDs: give each XCD one contiguous chunk of the tile grid (bijective)
-  const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
 template <int BM_, int BN_, int WM_, int WN_>
 struct BTile {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, NW = WM_ * WN_, NT = 64 * NW;
@@ -211,15 +203,8 @@ struct Ring {
   static_assert(T::NW == 8 && T::BM % 128 == 0 && T::BN % 128 == 0 && NS >= 3, "ring kernel: 8 waves, 128-row multiples");
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-#define DGVIT_BUF_OOB 0x80000000u
 
 // STAMP: diagnostic build (tools/bf16_stamps.py): wave 0 / wave 4 lane 0 of every workgroup write s_memtime at the start
 // of each of its first 8 tiles, after the tile's main loop and after its epilogue, to a buffer nothing else reads.
@@ -323,16 +308,16 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
 #pragma unroll
       for (int i = 0; i < 2; ++i) {   // k-rows lt * 32 + 2 * wave + srow + 16 i
         const bool rok = live && lt * 32 + 2 * wave + srow + 16 * i < lklen;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(dst + i * 8192), 16, (rok && la_ok) ? base_a + i * stepA : DGVIT_BUF_OOB, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)(dst + i * 8192), 16, (rok && la_ok) ? base_a + i * stepA : BUF_OOB, 0, 0, 0);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const bool rok = live && lt * 32 + 2 * wave + srow + 16 * i < lklen;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(dst + 16384 + i * 8192), 16, (rok && lb_ok) ? base_b + i * stepB : DGVIT_BUF_OOB, 0, 0,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(dst + 16384 + i * 8192), 16, (rok && lb_ok) ? base_b + i * stepB : BUF_OOB, 0, 0,
                                                  0);
       }
     } else {
-      const unsigned dead = (ltile < ntiles && lt * 32 + sc * 8 < lklen) ? 0u : DGVIT_BUF_OOB;
+      const unsigned dead = (ltile < ntiles && lt * 32 + sc * 8 < lklen) ? 0u : BUF_OOB;
       const unsigned oa = (offA + (unsigned)lt * 64u) | dead, ob = (offB + (unsigned)lt * 64u) | dead;
 #pragma unroll
       for (int i = 0; i < R::GA; ++i)
@@ -501,16 +486,16 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
       const long long crow0 = p.c_rgrp > 0 ? m0 + m0 / p.c_rgrp + 1 : m0;
       constexpr int CES = (EPI == BEPI_F32 || EPI == BEPI_F32_PLAIN) ? 4 : 2;
       const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<unsigned char*>(p.C) + ((long long)v_slice(vt) * p.slab_stride + crow0 * p.ldc + n0) * CES, 0, (int)DGVIT_BUF_OOB,
+          reinterpret_cast<unsigned char*>(p.C) + ((long long)v_slice(vt) * p.slab_stride + crow0 * p.ldc + n0) * CES, 0, (int)BUF_OOB,
           0x00020000);
       __amdgpu_buffer_rsrc_t rsX = rsC;   // second operand of the epilogue: residual (fp32) / pre-activation copy / aux (bf16)
       if (EPI == BEPI_F32 && p.res)
         rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res) + ((long long)(p.res_mod > 0 ? 0 : m0) * p.ldr + n0), 0,
-                                                (int)DGVIT_BUF_OOB, 0x00020000);
+                                                (int)BUF_OOB, 0x00020000);
       if (EPI == BEPI_GELU2_BF16)
-        rsX = __builtin_amdgcn_make_buffer_rsrc(p.C2 + ((long long)m0 * p.ldc2 + n0), 0, (int)DGVIT_BUF_OOB, 0x00020000);
+        rsX = __builtin_amdgcn_make_buffer_rsrc(p.C2 + ((long long)m0 * p.ldc2 + n0), 0, (int)BUF_OOB, 0x00020000);
       if (EPI == BEPI_DGELU_BF16)
-        rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.aux) + ((long long)m0 * p.ldaux + n0), 0, (int)DGVIT_BUF_OOB,
+        rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.aux) + ((long long)m0 * p.ldaux + n0), 0, (int)BUF_OOB,
                                                 0x00020000);
       fx4 bias4 = {0.f, 0.f, 0.f, 0.f};
       if (p.bias && ncol) bias4 = *reinterpret_cast<const fx4*>(p.bias + gn);
@@ -524,7 +509,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
 #pragma unroll
         for (int hq = 0; hq < 2 * NQ; ++hq) {
           const int ml = wr * WTM + i * 32 + (hq / NQ) * 16 + (hq % NQ) * RPI + erow;
-          const unsigned xoff = (m0 + ml < p.M && ncol) ? ((unsigned)ml * (unsigned)p.ldaux + coln) * 2u : DGVIT_BUF_OOB;
+          const unsigned xoff = (m0 + ml < p.M && ncol) ? ((unsigned)ml * (unsigned)p.ldaux + coln) * 2u : BUF_OOB;
           dst[hq] = __builtin_amdgcn_raw_buffer_load_b64(rsX, xoff, 0, 0);
         }
       };
@@ -538,7 +523,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
       auto res_load = [&](int g, int q) -> fx4 {   // g = 2 i + half: one 16-row group of the wave's tile; q: its q-th row piece
         const int ml = wr * WTM + g * 16 + q * RPI + erow, gm = m0 + ml;
         const unsigned rr = p.res_mod > 0 ? (unsigned)(gm % p.res_mod) + 1u : (unsigned)ml;
-        const unsigned roff = (gm < p.M && ncol) ? (rr * (unsigned)p.ldr + coln) * 4u : DGVIT_BUF_OOB;
+        const unsigned roff = (gm < p.M && ncol) ? (rr * (unsigned)p.ldr + coln) * 4u : BUF_OOB;
         return __builtin_bit_cast(fx4, __builtin_amdgcn_raw_buffer_load_b128(rsX, roff, 0, 0));
       };
       if (use_res) {
@@ -571,7 +556,7 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
             const bool ok = gm < p.M && ncol;
             v += bias4;
             const long long crow = p.c_rgrp > 0 ? gm + gm / p.c_rgrp + 1 : gm;
-            const unsigned coff = ok ? ((unsigned)(crow - crow0) * (unsigned)p.ldc + coln) * CES : DGVIT_BUF_OOB;
+            const unsigned coff = ok ? ((unsigned)(crow - crow0) * (unsigned)p.ldc + coln) * CES : BUF_OOB;
             if (EPI == BEPI_F32 || EPI == BEPI_F32_PLAIN) {
               if (use_res) {   // this piece's residual arrived a group ago; its register takes the next group's piece at once
                 v += resv[EPI == BEPI_F32 ? q : 0];
@@ -611,31 +596,16 @@ __global__ void __launch_bounds__(512) gemm_bf16_ring_kernel(const GemmBf16Param
   wait_vmcnt<0>();   // the trailing (all-zero) LDS-DMAs must land before the workgroup gives its LDS back
 }
 
-int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 // one ring-kernel instantiation: raise its dynamic-LDS limit on first use on this device, then launch it
 template <class T, int EPI, bool STAMP, bool TN, bool M16>
 int launch_ring(const GemmBf16Params& p, int grid, int vtiles, long long* stamps, hipStream_t st) {
   constexpr int LDS = Ring<T, EPI>::LDS;
   auto kern = gemm_bf16_ring_kernel<T, EPI, STAMP, TN, M16>;
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "gemm_bf16: cannot raise the dynamic LDS limit to %d bytes", LDS);
-    once.mark(bit);
+  TRY((allow_dynamic_lds<gemm_bf16_ring_kernel<T, EPI, STAMP, TN, M16>>(LDS, "gemm_bf16")));
+  {
+    ProfileScope t(PROF_GEMM, 2.0 * p.M * p.N * p.K, st, !STAMP);   // (a stamped launch is a measurement of its own: not counted)
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, p, vtiles, stamps);
   }
-  const int slot = STAMP ? -1 : profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, p, vtiles, stamps);
-  if (!STAMP) profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("gemm_bf16_ring_kernel");
   return DGVIT_OK;
 }
@@ -660,7 +630,8 @@ int launch(const GemmBf16Params& p_in, hipStream_t st) {
     DGVIT_CHECK_ARG(S == 1 || EPI == BEPI_F32_PLAIN, "gemm_bf16: split-K needs the plain fp32 epilogue");
     const long long vtiles = tiles * S;
     DGVIT_CHECK_ARG(vtiles < (1ll << 30), "gemm_bf16: too many tiles");
-    const int grid = (int)(vtiles < num_cus() ? vtiles : num_cus());   // one persistent workgroup per CU
+    const int cus = device_cus();
+    const int grid = (int)(vtiles < cus ? vtiles : cus);   // one persistent workgroup per CU
 #ifdef DGVIT_DIAG
     if constexpr (EPI == BEPI_BF16) {
       if (g_gemm_bf16_stamps) return launch_ring<T, EPI, true, false, false>(p, grid, (int)vtiles, g_gemm_bf16_stamps, st);
@@ -677,16 +648,11 @@ int launch(const GemmBf16Params& p_in, hipStream_t st) {
     else return launch_ring<T, EPI, false, false, false>(p, grid, (int)vtiles, nullptr, st);
   } else {
     DGVIT_CHECK_ARG(p.ksplit <= 1 && !p.tn, "gemm_bf16: split-K / TN need the 256 x 256 tile");
-    static DeviceOnce once;
-    if (const unsigned long long bit = once.pending()) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<T, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              T::LDS) != hipSuccess)
-        return dgvit_set_error(DGVIT_ERR_HIP, "gemm_bf16: cannot raise the dynamic LDS limit to %d bytes", T::LDS);
-      once.mark(bit);
+    TRY((allow_dynamic_lds<gemm_bf16_kernel<T, EPI>>(T::LDS, "gemm_bf16")));
+    {
+      ProfileScope t(PROF_GEMM, 2.0 * p.M * p.N * p.K, st);
+      hipLaunchKernelGGL((gemm_bf16_kernel<T, EPI>), dim3((unsigned)tiles), dim3(T::NT), T::LDS, st, p);
     }
-    const int slot = profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, st);
-    hipLaunchKernelGGL((gemm_bf16_kernel<T, EPI>), dim3((unsigned)tiles), dim3(T::NT), T::LDS, st, p);
-    profile_end(slot, st);
   }
   DGVIT_CHECK_LAUNCH("gemm_bf16_kernel");
   return DGVIT_OK;

@@ -43,29 +43,15 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-constexpr unsigned OOB = 0x80000000u;
 constexpr int PIECE = 256 * 128;   // bytes of one piece: 256 rows x 64 k
 constexpr int NSLOT = 5;
-
-__device__ __forceinline__ int xcd_chunk(int id, int n) {
-  // blocks are dealt round-robin over the 8 XCDs: give each XCD one contiguous chunk of the tile grid (bijective)
-  const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
 
 // s_waitcnt lgkmcnt(0) as the BUILTIN (simm16: vmcnt 63, expcnt 7, lgkmcnt 0): hipcc's own wait insertion sees it, so it does not put
 // conservative `lgkmcnt(8)` waits in front of the next half's MFMAs for fragments this wait has already covered (an inline-asm wait is
 // invisible to its scoreboard; with the LDS busy taking DMA data those spurious waits stalled the MFMA stream).
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Issue order of one half (one basic block: 12 fragment reads of the NEXT half, 32 MFMAs, 4 LDS-DMAs): the four B fragments first,
 // then per A row block its 4 MFMAs followed by the read of the block's next fragment, and one DMA after every second block, so that
@@ -231,7 +217,7 @@ __device__ __forceinline__ void stream_body(const GemmBf16Params& p, int ntiles)
   // that a whole half (fragment reads, 32 MFMAs, 4 DMAs) is ONE basic block whose issue order sched_group_barrier can pin.
   // Past the last tile the same instructions still issue (every lane out of range: zeros into a free slot): the vmcnt bookkeeping
   // never changes.
-  unsigned ldead = lchunk * 8 < p.K ? 0u : OOB;
+  unsigned ldead = lchunk * 8 < p.K ? 0u : BUF_OOB;
   // (`other`: the rows of the SIMD partner, wave ^ 4 -- 32 rows and four 1 KB chunks away, same swizzle since (wave & 1) is the same)
   const int pw = wave < 4 ? 4 : -4;
   auto dma_a = [&](int i, int other = 0) {
@@ -253,7 +239,7 @@ __device__ __forceinline__ void stream_body(const GemmBf16Params& p, int ntiles)
       ltile += gridDim.x;
       if (ltile < ntiles) set_load_tile(ltile);
     }
-    ldead = (ltile < ntiles && lt * 64 + lchunk * 8 < p.K) ? 0u : OOB;
+    ldead = (ltile < ntiles && lt * 64 + lchunk * 8 < p.K) ? 0u : BUF_OOB;
   };
 
   // ---- compute side ------------------------------------------------------------------------------------------------------
@@ -434,7 +420,7 @@ __device__ __forceinline__ void stream_body(const GemmBf16Params& p, int ntiles)
       unsigned char* stg = smem + s1 * PIECE + wave * 1024;
       const int rr = lane >> 4, rc = lane & 15;                                               // read-back: row 4 u + rr, piece rc
       const unsigned rowpart = (unsigned)(wr * 128 + rr) * (unsigned)p.ldc * ES, rowstep = 4u * (unsigned)p.ldc * ES;
-      const unsigned coloff = n0 + wc * 64 + 4 * rc < p.N ? (unsigned)(wc * 64 + 4 * rc) * ES : OOB;
+      const unsigned coloff = n0 + wc * 64 + 4 * rc < p.N ? (unsigned)(wc * 64 + 4 * rc) * ES : BUF_OOB;
       fx4 bv[4];
       if (EPI != BEPI_F32_PLAIN && p.bias) {
         wait_vmcnt<NDMA>();   // the bias DMA (issued before this phase's four piece DMAs) has landed; same wave: no barrier needed
@@ -492,7 +478,7 @@ __device__ __forceinline__ void stream_body(const GemmBf16Params& p, int ntiles)
         const int r8 = lane >> 3, k8 = lane & 7;                                      // read-back: row 8 u + r8 of the block, 16-byte piece k8
         const unsigned rd0 = (unsigned)r8 * 128u + (((unsigned)k8 ^ (unsigned)((r8 >> 1) & 3)) << 4);      // u = 0: swizzle (r8 >> 1) & 7
         const unsigned rd1 = 8192u + (unsigned)r8 * 128u + (((unsigned)k8 ^ (unsigned)(4 + ((r8 >> 1) & 3))) << 4);   // u = 1: rows 8..15
-        unsigned off8 = (unsigned)(wr * 128 + r8) * (unsigned)p.ldc * 2u + (n0 + wc * 64 + 8 * k8 < p.N ? (unsigned)(wc * 64 + 8 * k8) * 2u : OOB);
+        unsigned off8 = (unsigned)(wr * 128 + r8) * (unsigned)p.ldc * 2u + (n0 + wc * 64 + 8 * k8 < p.N ? (unsigned)(wc * 64 + 8 * k8) * 2u : BUF_OOB);
         const unsigned rowstep8 = 8u * (unsigned)p.ldc * 2u;
         stage(0, 0);
 #pragma unroll
@@ -563,17 +549,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_stream_kernel(const GemmBf16Par
   }
 }
 
-int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return n;
-}
-
 template <int EPI, int DIAG = 0>
 int launch_stream(const GemmBf16Params& p_in, hipStream_t st) {
   GemmBf16Params p = p_in;
@@ -607,16 +582,13 @@ int launch_stream(const GemmBf16Params& p_in, hipStream_t st) {
   DGVIT_CHECK_ARG(EPI != BEPI_GELU2_BF16 || p.ldc2 == p.ldc, "gemm_bf16: the GELU epilogue with a pre-activation copy needs ldc2 == ldc");
   constexpr int LDS = NSLOT * PIECE;
   auto kern = gemm_bf16_stream_kernel<EPI, DIAG>;
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "gemm_bf16: cannot raise the dynamic LDS limit to %d bytes", LDS);
-    once.mark(bit);
+  TRY((allow_dynamic_lds<gemm_bf16_stream_kernel<EPI, DIAG>>(LDS, "gemm_bf16")));
+  const int cus = device_cus();
+  const int grid = (int)(tiles < cus ? tiles : cus);   // one persistent workgroup per CU
+  {
+    ProfileScope t(PROF_GEMM, 2.0 * p.M * p.N * p.K, st);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, p, (int)tiles);
   }
-  const int grid = (int)(tiles < num_cus() ? tiles : num_cus());   // one persistent workgroup per CU
-  const int slot = profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, p, (int)tiles);
-  profile_end(slot, st);
   DGVIT_CHECK_LAUNCH("gemm_bf16_stream_kernel");
   return DGVIT_OK;
 }

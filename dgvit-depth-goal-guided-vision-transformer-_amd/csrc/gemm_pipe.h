@@ -322,12 +322,11 @@ int launch_persistent(const GemmParams& p, hipStream_t stream, bool* taken) {
     if (p.K != NK * BK) return DGVIT_OK;
     constexpr size_t lds = T::LDS_BYTES;
     auto kern = gemm_f32_pipe_kernel<T, LAYOUT, EPI, NK>;
+    TRY((allow_dynamic_lds<gemm_f32_pipe_kernel<T, LAYOUT, EPI, NK>>(160 * 1024, "gemm")));
     static int slots = 0;
     if (!slots) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
       int per_cu = 0;
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T::NT, lds);
+      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, T::NT, lds);
       if (e != hipSuccess || per_cu < 1) return dgvit_set_error(DGVIT_ERR_HIP, "gemm: occupancy query: %s", hipGetErrorString(e));
       slots = 256 * per_cu;
     }
@@ -346,9 +345,10 @@ int launch_persistent(const GemmParams& p, hipStream_t stream, bool* taken) {
       grid = std::min<long long>(slots, ((tiles + rounds - 1) / rounds + 7) / 8 * 8);
     }
     grid = std::min<long long>(grid, tiles);
-    const int slot = profile_begin(PROF_GEMM, 2.0 * p.M * p.N * p.K, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T::NT), lds, stream, q);
-    profile_end(slot, stream);
+    {
+      ProfileScope t(PROF_GEMM, 2.0 * p.M * p.N * p.K, stream);
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(T::NT), lds, stream, q);
+    }
     DGVIT_CHECK_LAUNCH("gemm_f32_pipe_kernel");
     ++g_gemm_persist_launches;
     *taken = true;

@@ -3,12 +3,6 @@
 // common.h); every sum is taken in a fixed order, so results are bit-identical from run to run.
 #include "common.h"
 
-#define TRY_RG(expr)      \
-  do {                    \
-    int rc_ = (expr);     \
-    if (rc_) return rc_;  \
-  } while (0)
-
 namespace {
 
 // out1[0..n1) , out2[0..n-n1)  <-  sum over slabs of slab[z][0..n), for up to DGVIT_REDUCE_JOBS independent jobs in ONE launch
@@ -78,9 +72,10 @@ void reduce_group_init(ReduceGroup& g) { g.njobs = 0; g.first_block[0] = 0; }
 // launch every queued job as ONE kernel (no-op when empty)
 int reduce_group_flush(ReduceGroup& g, hipStream_t stream) {
   if (g.njobs == 0) return DGVIT_OK;
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-  hipLaunchKernelGGL(reduce_group_kernel, dim3((unsigned)g.first_block[g.njobs]), dim3(256), 0, stream, g);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(reduce_group_kernel, dim3((unsigned)g.first_block[g.njobs]), dim3(256), 0, stream, g);
+  }
   g.njobs = 0;
   DGVIT_CHECK_LAUNCH("reduce_group");
   return DGVIT_OK;
@@ -92,14 +87,15 @@ int reduce_group_add(ReduceGroup& g, const float* slabs, float* out1, long long 
                      long long slab_stride, hipStream_t stream) {
   DGVIT_CHECK_ARG(slabs && out1 && n > 0 && n1 > 0 && n1 <= n && nslab >= 1 && (n1 == n || out2), "reduce_slabs: bad arguments");
   if (!(n % 4 == 0 && n1 % 4 == 0 && slab_stride % 4 == 0 && al16(slabs) && al16(out1) && (n1 == n || al16(out2)))) {
-    const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-    hipLaunchKernelGGL(reduce_slabs_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, slabs, out1, out2, n, n1,
-                       nslab, slab_stride);
-    profile_end(slot, stream);
+    {
+      ProfileScope t(PROF_OTHER, 0.0, stream);
+      hipLaunchKernelGGL(reduce_slabs_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, slabs, out1, out2, n, n1,
+                         nslab, slab_stride);
+    }
     DGVIT_CHECK_LAUNCH("reduce_slabs");
     return DGVIT_OK;
   }
-  if (g.njobs == DGVIT_REDUCE_JOBS) TRY_RG(reduce_group_flush(g, stream));
+  if (g.njobs == DGVIT_REDUCE_JOBS) TRY(reduce_group_flush(g, stream));
   ReduceJob& job = g.job[g.njobs];
   job.slabs = slabs; job.out1 = out1; job.out2 = out2;
   job.n4 = n / 4; job.n14 = n1 / 4; job.nslab = nslab; job.stride4 = slab_stride / 4;
@@ -116,7 +112,7 @@ int reduce_slabs2(const float* slabs, float* out1, long long n1, float* out2, lo
                   hipStream_t stream) {
   ReduceGroup g;
   reduce_group_init(g);
-  TRY_RG(reduce_group_add(g, slabs, out1, n1, out2, n, nslab, slab_stride, stream));
+  TRY(reduce_group_add(g, slabs, out1, n1, out2, n, nslab, slab_stride, stream));
   return reduce_group_flush(g, stream);
 }
 

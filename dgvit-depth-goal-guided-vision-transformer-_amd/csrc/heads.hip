@@ -374,24 +374,17 @@ bool w1_vec(const HeadArgs& a) {
 int mlp_head_forward(const dgvit_mlp_desc* d, const float* const* in, const float* const* params, float* h1, float* h2, float* y,
                      hipStream_t stream) {
   HeadArgs a;
-  int rc = fill_args(a, d, in, params);
-  if (rc) return rc;
+  TRY(fill_args(a, d, in, params));
   DGVIT_CHECK_ARG(h1 && h2 && y, "mlp_head_forward: null output");
   a.h1 = h1; a.h2 = h2; a.y = y;
   const size_t lds = fwd_lds(a.KP, a.n1, a.n2);
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    const int mx = (int)fwd_lds(HMAXK, HMAXN, HMAXN);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_head_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_head_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "mlp_head_forward: hipFuncSetAttribute failed");
-    once.mark(bit);
-  }
+  TRY((allow_dynamic_lds<mlp_head_fwd_kernel<true>, mlp_head_fwd_kernel<false>>((int)fwd_lds(HMAXK, HMAXN, HMAXN), "mlp_head_forward")));
   const dim3 grid((a.B + HR - 1) / HR, a.towers);
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-  if (w1_vec(a)) hipLaunchKernelGGL(mlp_head_fwd_kernel<true>, grid, dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL(mlp_head_fwd_kernel<false>, grid, dim3(256), lds, stream, a);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    if (w1_vec(a)) hipLaunchKernelGGL(mlp_head_fwd_kernel<true>, grid, dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(mlp_head_fwd_kernel<false>, grid, dim3(256), lds, stream, a);
+  }
   DGVIT_CHECK_LAUNCH("mlp_head_forward");
   return DGVIT_OK;
 }
@@ -410,8 +403,7 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
                       const float* const* dy, float* const* din, float* const* dparams, float* scratch, long long scratch_floats,
                       hipStream_t stream) {
   HeadArgs a;
-  int rc = fill_args(a, d, in, params);
-  if (rc) return rc;
+  TRY(fill_args(a, d, in, params));
   DGVIT_CHECK_ARG(h1 && h2 && dy && din && dparams, "mlp_head_backward: null pointer");
   const long long need = mlp_head_backward_scratch(d);
   DGVIT_CHECK_ARG(scratch && scratch_floats >= need, "mlp_head_backward: scratch %lld < %lld floats", scratch_floats, need);
@@ -430,28 +422,22 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
   a.direct = nwg == 1;
   a.part = scratch; a.part_stride = po.total;
   const size_t lds = bwd_lds(a.KP, a.n1, a.n2, a.n3, a.heads3);
-  static DeviceOnce once;
-  if (const unsigned long long bit = once.pending()) {
-    const int mx = (int)bwd_lds(HMAXK, HMAXN, HMAXN, 4, 2);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_head_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_head_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-      return dgvit_set_error(DGVIT_ERR_HIP, "mlp_head_backward: hipFuncSetAttribute failed");
-    once.mark(bit);
-  }
+  TRY((allow_dynamic_lds<mlp_head_bwd_kernel<true>, mlp_head_bwd_kernel<false>>((int)bwd_lds(HMAXK, HMAXN, HMAXN, 4, 2), "mlp_head_backward")));
   // a twin head runs both towers in ONE launch (blockIdx.y): tower 0 writes dx, tower 1 writes its input gradient to scratch and a
   // small kernel adds it (x = t0 + t1: the order is fixed); the two towers used to be two launches one behind the other
   bool any_dx = false;
   for (int s = 0; s < a.nseg; ++s) any_dx = any_dx || a.dx[s];
   const bool vec = w1_vec(a);
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-  a.dx1 = (a.towers == 2 && any_dx) ? scratch + (need - (((long long)a.B * a.K0 + 3) & ~3ll)) : nullptr;
-  if (vec) hipLaunchKernelGGL(mlp_head_bwd_kernel<true>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL(mlp_head_bwd_kernel<false>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
-  if (a.dx1) {
-    const long long n = (long long)a.B * a.K0;
-    hipLaunchKernelGGL(head_dx_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    a.dx1 = (a.towers == 2 && any_dx) ? scratch + (need - (((long long)a.B * a.K0 + 3) & ~3ll)) : nullptr;
+    if (vec) hipLaunchKernelGGL(mlp_head_bwd_kernel<true>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(mlp_head_bwd_kernel<false>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
+    if (a.dx1) {
+      const long long n = (long long)a.B * a.K0;
+      hipLaunchKernelGGL(head_dx_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    }
   }
-  profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("mlp_head_backward");
   if (a.direct) return DGVIT_OK;
   // fixed-order sums of the per-workgroup partials: one grouped launch per 8 tensors
@@ -464,14 +450,14 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
       if (!out) return DGVIT_OK;
       return reduce_group_add(g, base + off, out, n, nullptr, n, nwg, stride, stream);
     };
-    if ((rc = add(po.w1, a.dw1[t], (long long)a.n1 * a.K0))) return rc;
-    if ((rc = add(po.b1, a.db1[t], a.n1))) return rc;
-    if ((rc = add(po.w2, a.dw2[t], (long long)a.n2 * a.n1))) return rc;
-    if ((rc = add(po.b2, a.db2[t], a.n2))) return rc;
+    TRY(add(po.w1, a.dw1[t], (long long)a.n1 * a.K0));
+    TRY(add(po.b1, a.db1[t], a.n1));
+    TRY(add(po.w2, a.dw2[t], (long long)a.n2 * a.n1));
+    TRY(add(po.b2, a.db2[t], a.n2));
     for (int j = 0; j < a.heads3; ++j) {
       if (!a.dyp[t][j]) continue;
-      if ((rc = add(po.w3[j], a.dw3[t][j], (long long)a.n3 * a.n2))) return rc;
-      if ((rc = add(po.b3[j], a.db3[t][j], a.n3))) return rc;
+      TRY(add(po.w3[j], a.dw3[t][j], (long long)a.n3 * a.n2));
+      TRY(add(po.b3[j], a.db3[t][j], a.n3));
     }
   }
   return reduce_group_flush(g, stream);

@@ -1,7 +1,8 @@
 // A/B and diagnostic knobs of the kernels and schedules.
 //
 // Product build (libdgvit_hip.so): every knob is a compile-time constant with its shipped default -- the library has NO mutable
-// process-global state besides one-time initialisation (helper stream, per-device kernel attributes): nothing a second host
+// process-global state besides one-time initialisation (helper stream, and per device ordinal in atomics the kernel attributes and the
+// compute-unit count: launch.h's allow_dynamic_lds and device_cus): nothing a second host
 // thread (autograd's backward thread) could flip in the middle of a step, and the code of the switched-off alternatives
 // (clock stamps, timing diagnostics, the pipelined persistent GEMM, the per-frame inference path, the non-default MFMA shape)
 // is not in the binary.  The two schedule options a caller may legitimately want per call travel in dgvit_config.flags.

@@ -362,26 +362,17 @@ __global__ void __launch_bounds__(256) head_proj_wgrad_kernel(const float* __res
   }
 }
 
-int allow_goal_lds(const void* kern, DeviceOnce& once, const char* what) {
-  if (const unsigned long long bit = once.pending()) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GOAL_POOL_LDS_MAX);
-    if (e != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-    once.mark(bit);
-  }
-  return DGVIT_OK;
-}
-
 template <int J>
 int launch_pool_fwd(const float* xn, const float* u, long long fs_u, float* r, long long fs_r, float* p, int B, int N, int D, int H, float scale,
                     hipStream_t st) {
   auto kern = goal_pool_fwd_kernel<J>;
-  static DeviceOnce once;   // (the first call is made outside any graph capture: hipFuncSetAttribute is not a stream operation)
-  if (int rc = allow_goal_lds(reinterpret_cast<const void*>(kern), once, "goal_pool_fwd")) return rc;
+  TRY(allow_dynamic_lds<goal_pool_fwd_kernel<J>>((int)GOAL_POOL_LDS_MAX, "goal_pool_fwd"));
   const long long np = (N + 3) & ~3;
   const size_t lds = (size_t)((long long)N * D + GP_WAVES * np) * sizeof(float);
-  const int slot = profile_begin(PROF_ATTN_FWD, 4.0 * B * H * (double)N * D, st);
-  hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GP_WAVES), lds, st, xn, u, fs_u, r, fs_r, p, N, D, H, scale * DGVIT_LOG2E);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_ATTN_FWD, 4.0 * B * H * (double)N * D, st);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GP_WAVES), lds, st, xn, u, fs_u, r, fs_r, p, N, D, H, scale * DGVIT_LOG2E);
+  }
   DGVIT_CHECK_LAUNCH("goal_pool_fwd");
   return DGVIT_OK;
 }
@@ -390,13 +381,13 @@ template <int J>
 int launch_pool_bwd(const float* xn, const float* p, const float* u, long long fs_u, const float* dr, float* du, long long fs_d, float* dxn,
                     int B, int N, int D, int H, float scale, hipStream_t st) {
   auto kern = goal_pool_bwd_kernel<J>;
-  static DeviceOnce once;
-  if (int rc = allow_goal_lds(reinterpret_cast<const void*>(kern), once, "goal_pool_bwd")) return rc;
+  TRY(allow_dynamic_lds<goal_pool_bwd_kernel<J>>((int)GOAL_POOL_LDS_MAX, "goal_pool_bwd"));
   const long long np = (N + 3) & ~3;
   const size_t lds = (size_t)((long long)N * D + 2ll * H * np) * sizeof(float);
-  const int slot = profile_begin(PROF_ATTN_BWD, 8.0 * B * H * (double)N * D, st);
-  hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GP_WAVES), lds, st, xn, p, u, fs_u, dr, du, fs_d, dxn, N, D, H, scale);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_ATTN_BWD, 8.0 * B * H * (double)N * D, st);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * GP_WAVES), lds, st, xn, p, u, fs_u, dr, du, fs_d, dxn, N, D, H, scale);
+  }
   DGVIT_CHECK_LAUNCH("goal_pool_bwd");
   return DGVIT_OK;
 }
@@ -422,10 +413,11 @@ bool goal_attention_supports(int N, int D, int H, int dh) {
 int head_proj(const float* in, long long ld_in, const float* W, float* out, long long fs_out, int B, int H, int dh, int D, hipStream_t st) {
   DGVIT_CHECK_ARG(in && W && out && al16(in) && ld_in % 4 == 0, "head_proj: bad arguments");
   const dim3 grid((B + HP_FRAMES - 1) / HP_FRAMES, H);
-  const int slot = profile_begin(PROF_OTHER, 2.0 * B * H * (double)dh * D, st);
-  if (dh == 64) hipLaunchKernelGGL(head_proj_kernel<64>, grid, dim3(256), 0, st, in, ld_in, W, out, fs_out, B, D);
-  else hipLaunchKernelGGL(head_proj_kernel<32>, grid, dim3(256), 0, st, in, ld_in, W, out, fs_out, B, D);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 2.0 * B * H * (double)dh * D, st);
+    if (dh == 64) hipLaunchKernelGGL(head_proj_kernel<64>, grid, dim3(256), 0, st, in, ld_in, W, out, fs_out, B, D);
+    else hipLaunchKernelGGL(head_proj_kernel<32>, grid, dim3(256), 0, st, in, ld_in, W, out, fs_out, B, D);
+  }
   DGVIT_CHECK_LAUNCH("head_proj");
   return DGVIT_OK;
 }
@@ -433,10 +425,11 @@ int head_proj(const float* in, long long ld_in, const float* W, float* out, long
 int head_proj_t(const float* in, long long fs_in, const float* W, float* out, long long ld_out, int B, int H, int dh, int D, hipStream_t st) {
   DGVIT_CHECK_ARG(in && W && out && al16(in) && al16(W) && fs_in % 4 == 0, "head_proj_t: bad arguments");
   const dim3 grid((B + HP_FRAMES - 1) / HP_FRAMES, H);
-  const int slot = profile_begin(PROF_OTHER, 2.0 * B * H * (double)dh * D, st);
-  if (dh == 64) hipLaunchKernelGGL(head_proj_t_kernel<64>, grid, dim3(256), 0, st, in, fs_in, W, out, ld_out, B, D);
-  else hipLaunchKernelGGL(head_proj_t_kernel<32>, grid, dim3(256), 0, st, in, fs_in, W, out, ld_out, B, D);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 2.0 * B * H * (double)dh * D, st);
+    if (dh == 64) hipLaunchKernelGGL(head_proj_t_kernel<64>, grid, dim3(256), 0, st, in, fs_in, W, out, ld_out, B, D);
+    else hipLaunchKernelGGL(head_proj_t_kernel<32>, grid, dim3(256), 0, st, in, fs_in, W, out, ld_out, B, D);
+  }
   DGVIT_CHECK_LAUNCH("head_proj_t");
   return DGVIT_OK;
 }
@@ -466,8 +459,8 @@ int goal_attention_fwd(const float* xn, const float* wqkv, const float* q, long 
   DGVIT_CHECK_ARG(wqkv && al16(wqkv) && o, "goal_attention_fwd: bad arguments");
   const long long I = (long long)H * dh;
   const float scale = 1.0f / sqrtf((float)dh);
-  if (int rc = head_proj(q, ldq, wqkv + I * D, u, fs_ur, B, H, dh, D, st)) return rc;
-  if (int rc = goal_pool_fwd(xn, u, fs_ur, r, fs_ur, p, B, N, D, H, scale, st)) return rc;
+  TRY(head_proj(q, ldq, wqkv + I * D, u, fs_ur, B, H, dh, D, st));
+  TRY(goal_pool_fwd(xn, u, fs_ur, r, fs_ur, p, B, N, D, H, scale, st));
   return head_proj_t(r, fs_ur, wqkv + 2 * I * D, o, ldo, B, H, dh, D, st);
 }
 
@@ -480,8 +473,8 @@ int goal_attention_bwd_data(const float* xn, const float* wqkv, const float* dou
   DGVIT_CHECK_ARG(wqkv && al16(wqkv) && dq, "goal_attention_bwd: bad arguments");
   const long long I = (long long)H * dh;
   const float scale = 1.0f / sqrtf((float)dh);
-  if (int rc = head_proj(dout, lddo, wqkv + 2 * I * D, dr, fs_d, B, H, dh, D, st)) return rc;
-  if (int rc = goal_pool_bwd(xn, p, u, fs_ur, dr, du, fs_d, dxn, B, N, D, H, scale, st)) return rc;
+  TRY(head_proj(dout, lddo, wqkv + 2 * I * D, dr, fs_d, B, H, dh, D, st));
+  TRY(goal_pool_bwd(xn, p, u, fs_ur, dr, du, fs_d, dxn, B, N, D, H, scale, st));
   return head_proj_t(du, fs_d, wqkv + I * D, dq, lddq, B, H, dh, D, st);
 }
 
@@ -493,10 +486,11 @@ int goal_attention_wgrad(const float* q, long long ldq, const float* dout, long 
   DGVIT_CHECK_ARG(al16(q) && al16(dout) && al16(du) && al16(r) && ldq % 4 == 0 && lddo % 4 == 0 && fs_d % 4 == 0 && fs_ur % 4 == 0,
                   "goal_attention_wgrad: operands must be 16-byte aligned");
   const dim3 grid((dh / WG_ROWS) * ((D + 255) / 256), H, 2);
-  const int slot = profile_begin(PROF_OTHER, 4.0 * B * H * (double)dh * D, st);
-  if (dh == 64) hipLaunchKernelGGL(head_proj_wgrad_kernel<64>, grid, dim3(256), 0, st, q, ldq, du, fs_d, dout, lddo, r, fs_ur, dwkv, B, D, H, al16(dwkv) ? 1 : 0);
-  else hipLaunchKernelGGL(head_proj_wgrad_kernel<32>, grid, dim3(256), 0, st, q, ldq, du, fs_d, dout, lddo, r, fs_ur, dwkv, B, D, H, al16(dwkv) ? 1 : 0);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 4.0 * B * H * (double)dh * D, st);
+    if (dh == 64) hipLaunchKernelGGL(head_proj_wgrad_kernel<64>, grid, dim3(256), 0, st, q, ldq, du, fs_d, dout, lddo, r, fs_ur, dwkv, B, D, H, al16(dwkv) ? 1 : 0);
+    else hipLaunchKernelGGL(head_proj_wgrad_kernel<32>, grid, dim3(256), 0, st, q, ldq, du, fs_d, dout, lddo, r, fs_ur, dwkv, B, D, H, al16(dwkv) ? 1 : 0);
+  }
   DGVIT_CHECK_LAUNCH("head_proj_wgrad");
   return DGVIT_OK;
 }

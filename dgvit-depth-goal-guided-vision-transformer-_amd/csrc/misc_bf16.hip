@@ -206,10 +206,11 @@ __global__ void __launch_bounds__(256) residual_add_bf16_kernel(const float* __r
 int residual_add_bf16(const float* x, const bf16_t* delta, float* xout, int rows, int D, int rs, hipStream_t st) {
   DGVIT_CHECK_ARG(x && delta && xout && rows > 0 && D > 0 && D % 4 == 0, "residual_add_bf16: bad arguments");
   const long long n4 = (long long)rows * (D / 4);
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(residual_add_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, delta, xout, (long long)rows,
-                     D / 4, (long long)rs * D);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(residual_add_bf16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, delta, xout, (long long)rows,
+                       D / 4, (long long)rs * D);
+  }
   DGVIT_CHECK_LAUNCH("residual_add_bf16");
   return DGVIT_OK;
 }
@@ -287,17 +288,18 @@ static int layernorm_launch(const float* x, const bf16_t* delta, const bf16_t* d
                             bf16_t* y, float* mean, float* rstd, int T, int D, float eps, int rs, hipStream_t st) {
   DGVIT_CHECK_ARG(x && gamma && beta && y && T > 0, "layernorm_bf16: bad arguments");
   DGVIT_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 1024, "layernorm_bf16: D=%d must be a multiple of 4 and <= 1024", D);
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  const dim3 grid((unsigned)((T + 3) / 4)), blk(256);
-  if (D <= 256)
-    hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<1, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
-  else if (D <= 512)
-    hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<2, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
-  else if (D <= 768)     // (ViT-Base: no dead fourth chunk in the row loops)
-    hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<3, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
-  else
-    hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<4, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    const dim3 grid((unsigned)((T + 3) / 4)), blk(256);
+    if (D <= 256)
+      hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<1, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
+    else if (D <= 512)
+      hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<2, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
+    else if (D <= 768)     // (ViT-Base: no dead fourth chunk in the row loops)
+      hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<3, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
+    else
+      hipLaunchKernelGGL((layernorm_fwd_bf16_kernel<4, ADD>), grid, blk, 0, st, x, delta, delta2, xout, gamma, beta, y, mean, rstd, T, D, eps, rs);
+  }
   DGVIT_CHECK_LAUNCH("layernorm_fwd_bf16");
   return DGVIT_OK;
 }
@@ -447,9 +449,10 @@ __global__ void __launch_bounds__(1024) colpart_reduce_kernel(const float* __res
 // out (cols) = sum of nblk partial rows
 static int colpart_reduce_n(const float* part, float* out, int nblk, int cols, hipStream_t st) {
   DGVIT_CHECK_ARG(part && out && nblk > 0 && cols > 0, "colpart_reduce: bad arguments");
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((cols + 63) / 64), dim3(1024), 0, st, part, out, nblk, cols);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((cols + 63) / 64), dim3(1024), 0, st, part, out, nblk, cols);
+  }
   DGVIT_CHECK_LAUNCH("colpart_reduce");
   return DGVIT_OK;
 }
@@ -458,9 +461,10 @@ static int colpart_reduce_n(const float* part, float* out, int nblk, int cols, h
 int colsum_bf16(const bf16_t* src, long long ld, float* out, float* part, int rows, int cols, hipStream_t st) {
   DGVIT_CHECK_ARG(src && out && part && rows > 0 && cols > 0 && cols % 8 == 0 && ld % 8 == 0, "colsum_bf16: cols and ld must be multiples of 8");
   const int nblk = colsum_bf16_blocks(rows), rpb = (rows + nblk - 1) / nblk;
-  const int slot = profile_begin(PROF_OTHER, 0.0, st);
-  hipLaunchKernelGGL(colsum_bf16_kernel, dim3((cols + 511) / 512, nblk), dim3(256), 0, st, src, ld, part, rows, cols, rpb);
-  profile_end(slot, st);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((cols + 511) / 512, nblk), dim3(256), 0, st, src, ld, part, rows, cols, rpb);
+  }
   DGVIT_CHECK_LAUNCH("colsum_bf16");
   return colpart_reduce_n(part, out, nblk, cols, st);
 }

@@ -295,16 +295,17 @@ int layernorm_bwd_bf16(const bf16_t* dy, const float* x, const float* mean, cons
   DGVIT_CHECK_ARG(T > 0 && D > 0 && D % 4 == 0 && D <= 1024, "layernorm_bwd_bf16: D=%d must be a multiple of 4, <= 1024", D);
   const int nb = layernorm_bwd_blocks(T);
   const int nch = (D + 255) / 256;
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
 #define LNB(NCH)                                                                                                              \
   hipLaunchKernelGGL((layernorm_bwd_kernel<NCH, bf16_t>), dim3(nb), dim3(256), 0, stream, dy, x, mean, rstd, gamma, dres, dx, dxb, \
                      partial, T, D, rs)
-  if (nch == 1) LNB(1);
-  else if (nch == 2) LNB(2);
-  else if (nch == 3) LNB(3);
-  else LNB(4);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    if (nch == 1) LNB(1);
+    else if (nch == 2) LNB(2);
+    else if (nch == 3) LNB(3);
+    else LNB(4);
+  }
 #undef LNB
-  profile_end(slot, stream);
   DGVIT_CHECK_LAUNCH("layernorm_bwd_bf16");
   return ln_param_grads(partial, dgamma, dbeta, D, nb, stream, nullptr);
 }

@@ -69,10 +69,11 @@ int adam_step(float* p, const float* g, float* m, float* v, long long n, float l
   DGVIT_CHECK_ARG((step >= 1 || step_dev) && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam_step: bad hyper-parameters");
   const double bc1 = 1.0 - pow((double)beta1, (double)(step >= 1 ? step : 1));
   const double bc2 = 1.0 - pow((double)beta2, (double)(step >= 1 ? step : 1));
-  const int slot = profile_begin(PROF_OTHER, 0.0, stream);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, (float)(lr / bc1), beta1, beta2,
-                     (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev);
-  profile_end(slot, stream);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, (float)(lr / bc1), beta1, beta2,
+                       (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev);
+  }
   DGVIT_CHECK_LAUNCH("adam_step");
   return DGVIT_OK;
 }

@@ -1,5 +1,5 @@
 // Host-side pieces shared by the translation units of the C ABI (api.hip, encoder.hip, encoder_bf16.hip, cnn_api.hip, diag_api.hip):
-// error macros, the fp32 weight-gradient GEMM, the encoder's dimensions and parameter slots, and the schedule steps that the fp32 and
+// the fp32 weight-gradient GEMM, the encoder's dimensions and parameter slots, and the schedule steps that the fp32 and
 // the bf16 encoder have in common.  Internal: not installed.
 #pragma once
 #include <algorithm>
@@ -7,18 +7,6 @@
 #include "../../include/dgvit_hip.h"
 #include "common.h"
 #include "kernels.h"
-
-#define TRY(expr)          \
-  do {                     \
-    int rc_ = (expr);      \
-    if (rc_) return rc_;   \
-  } while (0)
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return dgvit_set_error(DGVIT_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
-  } while (0)
 
 inline long long al4(long long n) { return (n + 3) & ~3ll; }
 
