@@ -38,6 +38,7 @@ class dgvit_grad_events(Structure):
     _fields_ = [("n_layers", c_int), ("layer", POINTER(c_void_p)), ("head", c_void_p)]
 
 
+GRAD_NORM_PARTIALS = 512    # include/dgvit_hip.h: DGVIT_GRAD_NORM_PARTIALS (doubles of scratch for dgvit_grad_sqnorm_partials)
 NUM_GLOBAL_PARAMS = 4
 PARAMS_PER_LAYER = 11
 ABI_VERSION = 7
@@ -108,6 +109,10 @@ SIGNATURES = {
     "dgvit_resize_bilinear": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "dgvit_adam_step": (_I, [_P, _P, _P, _P, _LL, _F, _F, _F, _F, _F, _LL, _P, _P]),
     "dgvit_soft_update": (_I, [_P, _P, _LL, _F, _P]),
+    "dgvit_grad_sqnorm_partials": (_I, [_P, _LL, _P, _I, _P]),
+    "dgvit_grad_clip_coef": (_I, [_P, _F, _P, _P]),
+    "dgvit_adam_step_scaled": (_I, [_P, _P, _P, _P, _LL, _F, _F, _F, _F, _F, _LL, _P, _P, _P]),
+    "dgvit_scale_by_device_scalar": (_I, [_P, _LL, _P, _P]),
     "dgvit_got_bf16_weight_elems": (_LL, [_CFG]),
     "dgvit_got_pack_weights_bf16": (_I, [_CFG, _TABLE, _P, _LL, _I, _P]),
     "dgvit_got_bf16_workspace_bytes": (_LL, [_CFG, _I, _I]),

@@ -224,6 +224,20 @@ extern "C" int dgvit_adam_step(float* p, const float* g, float* m, float* v, lon
 extern "C" int dgvit_soft_update(float* target, const float* source, long long n, float tau, void* stream) {
   return soft_update(target, source, n, tau, (hipStream_t)stream);
 }
+extern "C" int dgvit_grad_sqnorm_partials(const float* g, long long n, double* partials, int accumulate, void* stream) {
+  return grad_sqnorm_partials(g, n, partials, accumulate, (hipStream_t)stream);
+}
+extern "C" int dgvit_grad_clip_coef(const double* partials, float max_norm, float* out, void* stream) {
+  return grad_clip_coef(partials, max_norm, out, (hipStream_t)stream);
+}
+extern "C" int dgvit_adam_step_scaled(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                                      float eps, float weight_decay, long long step, const long long* step_dev,
+                                      const float* grad_scale_dev, void* stream) {
+  return adam_step_scaled(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, grad_scale_dev, (hipStream_t)stream);
+}
+extern "C" int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, void* stream) {
+  return scale_by_device_scalar(x, n, scale_dev, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- replay staging
 extern "C" int dgvit_gather_rows(const float* src, const long long* idx, float* out, long long nsel, long long row_floats,

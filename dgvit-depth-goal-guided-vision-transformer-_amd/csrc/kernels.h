@@ -51,6 +51,12 @@ int relu_bwd(const float*, const float*, float*, long long, hipStream_t);
 int adam_step(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
               hipStream_t);
 int soft_update(float*, const float*, long long, float, hipStream_t);
+// gradient-norm clipping on flat buffers (optim.hip)
+int grad_sqnorm_partials(const float* g, long long n, double* partials, int accumulate, hipStream_t);
+int grad_clip_coef(const double* partials, float max_norm, float* out, hipStream_t);
+int adam_step_scaled(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
+                     const float* grad_scale_dev, hipStream_t);
+int scale_by_device_scalar(float* x, long long n, const float* scale_dev, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
 // the single-channel frame gradient from conv1's column gradient (rows of KP floats, 25 real taps): no ReLU mask

@@ -4,15 +4,33 @@
 //   adam_step   : torch.optim.Adam semantics (bias-corrected, eps added to sqrt(v_hat), optional L2 weight decay)
 //   soft_update : target <- target * (1 - tau) + source * tau
 // Algorithmic bytes: Adam 28 B/parameter (read p,g,m,v; write p,m,v), soft update 12 B/parameter.
+// Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, attention_imitating.py:45-67) between the backward and Adam:
+//   grad_sqnorm_partials   : per-workgroup sums of g*g over a flat gradient buffer, in double (4 B/parameter, one read)
+//   grad_clip_coef         : partials -> total norm and the clamped coefficient max_norm / (norm + 1e-6), both left on the device
+//   adam_step_scaled       : adam_step with the gradient multiplied by that device-side coefficient as it is read (still 28 B/parameter)
+//   scale_by_device_scalar : x <- x * *scale, the in-place form for a stand-alone clip (8 B/parameter)
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
+// a * b rounded to fp32 on its own.  HIP's __fmul_rn is a plain product that the compiler may contract into a following add; with
+// contraction switched off for this expression the product keeps its own rounding wherever the function is inlined.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// SCALED: every gradient element is first multiplied by *grad_scale_dev (the clip coefficient of grad_clip_coef_kernel) and rounded to
+// fp32 on its own -- mul_rounded: never contracted into the weight-decay FMA -- so the step is bit-identical to an unscaled step on a
+// gradient buffer that was multiplied by the same scalar beforehand.  SCALED = false is the kernel as it always was.
+template <bool SCALED>
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long long n4, float lr_c, float beta1, float beta2,
                                                    float inv_sqrt_bc2, float eps, float wd, float lr,
-                                                   const long long* __restrict__ step_dev) {
+                                                   const long long* __restrict__ step_dev, const float* __restrict__ grad_scale_dev) {
+  float gscale = 1.f;
+  if (SCALED) gscale = *grad_scale_dev;
   if (step_dev) {   // graph-capturable form: bias corrections from the device-side step counter
     const float t = (float)*step_dev;
     lr_c = lr / (1.f - powf(beta1, t));
@@ -28,6 +46,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
+      if (SCALED) ge[e] = mul_rounded(gscale, ge[e]);
       const float gg = ge[e] + wd * pe[e];
       me[e] = beta1 * me[e] + (1.f - beta1) * gg;
       ve[e] = beta2 * ve[e] + (1.f - beta2) * gg * gg;
@@ -53,6 +72,83 @@ __global__ void __launch_bounds__(256) soft_update_kernel(float* __restrict__ tg
   }
 }
 
+// Sum of g*g over a flat buffer, one partial per workgroup.  The grid is ALWAYS DGVIT_GRAD_NORM_PARTIALS workgroups, so which elements
+// a lane sums -- and with that the result, bit for bit -- depends on n alone, never on the device.  Accumulation is in double: the pass
+// is HBM-bound at 4 B/element, the fp64 FMAs ride along, and the rounding of a lane's sum does not grow with the elements it walks.
+// Four float4 loads are in flight per lane (latency, not issue rate, bounds a streaming read); the four of a round go into four
+// accumulators in a fixed order.  Workgroup b owns partials[b]: a plain store (or, accumulating, its own earlier value plus the sum,
+// ordered by the stream) -- no atomics, no counters, nothing to zero beforehand.
+__global__ void __launch_bounds__(256) grad_sqnorm_partials_kernel(const float* __restrict__ g, long long n4, double* __restrict__ partials,
+                                                                   int accumulate) {
+  __shared__ double wave_sum[4];
+  const long long stride = (long long)DGVIT_GRAD_NORM_PARTIALS * 256;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    float4 q[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q[u] = reinterpret_cast<const float4*>(g)[i + u * stride];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      acc[u] = fma((double)q[u].x, (double)q[u].x, acc[u]);
+      acc[u] = fma((double)q[u].y, (double)q[u].y, acc[u]);
+      acc[u] = fma((double)q[u].z, (double)q[u].z, acc[u]);
+      acc[u] = fma((double)q[u].w, (double)q[u].w, acc[u]);
+    }
+  }
+  for (; i < n4; i += stride) {
+    const float4 q = reinterpret_cast<const float4*>(g)[i];
+    acc[0] = fma((double)q.x, (double)q.x, acc[0]);
+    acc[0] = fma((double)q.y, (double)q.y, acc[0]);
+    acc[0] = fma((double)q.z, (double)q.z, acc[0]);
+    acc[0] = fma((double)q.w, (double)q.w, acc[0]);
+  }
+  double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double tot = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+    partials[blockIdx.x] = accumulate ? partials[blockIdx.x] + tot : tot;
+  }
+}
+
+// One workgroup: the partials summed in a fixed order in double, then torch.nn.utils.clip_grad_norm_'s arithmetic in fp32:
+//   clip_coef = max_norm / (total_norm + 1e-6), which torch evaluates as (total_norm + 1e-6).reciprocal() * max_norm (Tensor.__rtruediv__),
+//   then clamp(max=1.0).  A NaN norm keeps a NaN coefficient as torch.clamp does (fminf would return 1); an infinite norm gives 0.
+__global__ void __launch_bounds__(256) grad_clip_coef_kernel(const double* __restrict__ partials, float max_norm, float* __restrict__ out) {
+  __shared__ double wave_sum[4];
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < DGVIT_GRAD_NORM_PARTIALS / 256; ++k) s += partials[k * 256 + threadIdx.x];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt((wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]));
+    const float coef = mul_rounded(__fdiv_rn(1.f, __fadd_rn(norm, 1e-6f)), max_norm);
+    out[0] = norm;
+    out[1] = coef > 1.f ? 1.f : coef;
+  }
+}
+static_assert(DGVIT_GRAD_NORM_PARTIALS % 256 == 0 && DGVIT_GRAD_NORM_PARTIALS >= 512 && DGVIT_GRAD_NORM_PARTIALS <= 2048,
+              "grad_clip_coef_kernel reads DGVIT_GRAD_NORM_PARTIALS / 256 partials per thread");
+
+__global__ void __launch_bounds__(256) scale_by_device_scalar_kernel(float* __restrict__ x, long long n4, const float* __restrict__ scale_dev) {
+  const float s = *scale_dev;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 t = reinterpret_cast<float4*>(x)[i];
+    t.x = mul_rounded(s, t.x);
+    t.y = mul_rounded(s, t.y);
+    t.z = mul_rounded(s, t.z);
+    t.w = mul_rounded(s, t.w);
+    reinterpret_cast<float4*>(x)[i] = t;
+  }
+}
+
 inline unsigned grid_for(long long n4) {
   long long b = (n4 + 255) / 256;
   if (b > 2048) b = 2048;  // 8 workgroups per CU, grid-stride beyond
@@ -71,10 +167,68 @@ int adam_step(float* p, const float* g, float* m, float* v, long long n, float l
   const double bc2 = 1.0 - pow((double)beta2, (double)(step >= 1 ? step : 1));
   {
     ProfileScope t(PROF_OTHER, 0.0, stream);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, (float)(lr / bc1), beta1, beta2,
-                       (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, (float)(lr / bc1), beta1, beta2,
+                       (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev, (const float*)nullptr);
   }
   DGVIT_CHECK_LAUNCH("adam_step");
+  return DGVIT_OK;
+}
+
+// adam_step on the gradient g * *grad_scale_dev (a device scalar, read when the kernel runs): the clipped step without a clipped copy
+int adam_step_scaled(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, long long step, const long long* step_dev, const float* grad_scale_dev, hipStream_t stream) {
+  DGVIT_CHECK_ARG(p && g && m && v, "adam_step_scaled: p, g, m and v must not be null");
+  DGVIT_CHECK_ARG(grad_scale_dev, "adam_step_scaled: grad_scale_dev must not be null (the unscaled step is adam_step)");
+  DGVIT_CHECK_ARG(n > 0 && n % 4 == 0, "adam_step_scaled: n=%lld must be a positive multiple of 4", n);
+  DGVIT_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v), "adam_step_scaled: buffers must be 16-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) == 0, "adam_step_scaled: grad_scale_dev must be 4-byte aligned");
+  DGVIT_CHECK_ARG((step >= 1 || step_dev) && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam_step_scaled: bad hyper-parameters");
+  const double bc1 = 1.0 - pow((double)beta1, (double)(step >= 1 ? step : 1));
+  const double bc2 = 1.0 - pow((double)beta2, (double)(step >= 1 ? step : 1));
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, (float)(lr / bc1), beta1, beta2,
+                       (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev, grad_scale_dev);
+  }
+  DGVIT_CHECK_LAUNCH("adam_step_scaled");
+  return DGVIT_OK;
+}
+
+int grad_sqnorm_partials(const float* g, long long n, double* partials, int accumulate, hipStream_t stream) {
+  DGVIT_CHECK_ARG(g && partials, "grad_sqnorm_partials: g and partials must not be null");
+  DGVIT_CHECK_ARG(n > 0 && n % 4 == 0, "grad_sqnorm_partials: n=%lld must be a positive multiple of 4", n);
+  DGVIT_CHECK_ARG(al16(g) && al16(partials), "grad_sqnorm_partials: g and partials must be 16-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(grad_sqnorm_partials_kernel, dim3(DGVIT_GRAD_NORM_PARTIALS), dim3(256), 0, stream, g, n / 4, partials, accumulate);
+  }
+  DGVIT_CHECK_LAUNCH("grad_sqnorm_partials");
+  return DGVIT_OK;
+}
+
+int grad_clip_coef(const double* partials, float max_norm, float* out, hipStream_t stream) {
+  DGVIT_CHECK_ARG(partials && out, "grad_clip_coef: partials and out must not be null");
+  DGVIT_CHECK_ARG(std::isfinite(max_norm) && max_norm > 0.f, "grad_clip_coef: max_norm=%g must be finite and greater than 0", (double)max_norm);
+  DGVIT_CHECK_ARG(al16(partials), "grad_clip_coef: partials must be 16-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 3) == 0, "grad_clip_coef: out must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, stream, partials, max_norm, out);
+  }
+  DGVIT_CHECK_LAUNCH("grad_clip_coef");
+  return DGVIT_OK;
+}
+
+int scale_by_device_scalar(float* x, long long n, const float* scale_dev, hipStream_t stream) {
+  DGVIT_CHECK_ARG(x && scale_dev, "scale_by_device_scalar: x and scale_dev must not be null");
+  DGVIT_CHECK_ARG(n > 0 && n % 4 == 0, "scale_by_device_scalar: n=%lld must be a positive multiple of 4", n);
+  DGVIT_CHECK_ARG(al16(x), "scale_by_device_scalar: x must be 16-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(scale_dev) & 3) == 0, "scale_by_device_scalar: scale_dev must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(scale_by_device_scalar_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, x, n / 4, scale_dev);
+  }
+  DGVIT_CHECK_LAUNCH("scale_by_device_scalar");
   return DGVIT_OK;
 }
 

@@ -5,6 +5,10 @@ per-parameter Python loop ``soft_update`` (utils.py:31-33).  Here the parameters
 one flat fp32 buffer (its *home*: each ``nn.Parameter`` keeps its identity, its ``.data`` becomes a view), and both
 updates are one HBM-bound HIP kernel per contiguous run of that buffer (``dgvit_adam_step`` / ``dgvit_soft_update``).
 
+Gradient-norm clipping (``clip_grad_norm_(…, 10)`` of the reference's behaviour-cloning loop, attention_imitating.py:45-67) rides on
+the same buffers: ``FlatAdam(max_grad_norm=…)`` folds it into the step (one streaming read for the norm, the coefficient stays on the
+device, Adam applies it while it reads the gradient), and ``clip_grad_norm_`` here is torch's function over the flat runs.
+
 There is one owner of parameter storage per module: ``flatten_parameters(module)`` creates (or returns) the module's
 home and ``FlatAdam`` adopts it, so an optimiser and a Polyak update on the same network share the same buffer.
 Layout of a home: for every ``GoT`` encoder inside the module its trainable parameters in the C ABI's table order --
@@ -13,6 +17,7 @@ followed by all remaining parameters in ``parameters()`` order.  Two networks of
 layout, which is what the one-kernel ``soft_update`` needs.
 """
 import ctypes
+import math
 import weakref
 from typing import Iterable, List, Union
 
@@ -110,9 +115,9 @@ class _Home:
             self.exp_avg_sq = torch.zeros_like(self.flat)
         return self.exp_avg, self.exp_avg_sq
 
-    def grad_run(self, idx: List[int]) -> torch.Tensor:
-        """Gradients of the parameters ``idx`` (adjacent slots) as one flat tensor laid out like their slots: zero copy when
-        they already are views of one buffer with that layout (the fused encoder backward's), else one multi-tensor copy."""
+    def grad_view(self, idx: List[int]):
+        """The gradients of the parameters ``idx`` (adjacent slots) as one flat tensor when they already are views of one buffer laid
+        out like their slots (the fused encoder backward's), else None."""
         lo = self.offsets[idx[0]]
         hi = self.offsets[idx[-1]] + _al4(self.params[idx[-1]].numel())
         g0 = self.params[idx[0]].grad
@@ -120,9 +125,22 @@ class _Home:
         if o0 % 4 == 0 and g0.data_ptr() % 16 == 0 and (o0 + hi - lo) * 4 <= g0.untyped_storage().nbytes() and all(
                 self.params[i].grad.untyped_storage().data_ptr() == st and self.params[i].grad.is_contiguous()
                 and self.params[i].grad.storage_offset() - o0 == self.offsets[i] - lo for i in idx):
-            self.zero_copy_elems += hi - lo
             return torch.empty(0, dtype=g0.dtype, device=g0.device).set_(g0.untyped_storage(), o0, (hi - lo,))
-        self.copied_elems += hi - lo
+        return None
+
+    def grad_run(self, idx: List[int], count: bool = True) -> torch.Tensor:
+        """Gradients of the parameters ``idx`` (adjacent slots) as one flat tensor laid out like their slots: zero copy when
+        they already are views of one buffer with that layout (``grad_view``), else one multi-tensor copy.  ``count``: an optimiser
+        step's call, added to ``zero_copy_elems`` / ``copied_elems``."""
+        lo = self.offsets[idx[0]]
+        hi = self.offsets[idx[-1]] + _al4(self.params[idx[-1]].numel())
+        view = self.grad_view(idx)
+        if view is not None:
+            if count:
+                self.zero_copy_elems += hi - lo
+            return view
+        if count:
+            self.copied_elems += hi - lo
         if self.gflat is None:
             self.gflat = torch.zeros_like(self.flat)
         views = [self.gflat[self.offsets[i]:self.offsets[i] + self.params[i].numel()].view_as(self.params[i]) for i in idx]
@@ -183,6 +201,62 @@ def home_of(module: torch.nn.Module) -> _Home:
     return h
 
 
+def _check_max_norm(value, what: str) -> float:
+    """a positive finite number (bool is not one), or ValueError"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value > 0) or not math.isfinite(value):
+        raise ValueError(f"{what} must be a positive finite number, got {value!r}")
+    return float(value)
+
+
+def _adjacent_runs(params, steps_of=None, who="FlatAdam"):
+    """[(home, [param indices])]: maximal runs of adjacent slots (of one section of one home) among those ``params`` that have a
+    gradient; with ``steps_of(home)`` (per-slot step counts) a run also ends where the count changes."""
+    by_home = {}
+    for p in params:
+        if p.grad is None:
+            continue
+        ent = _HOME_OF.get(p)
+        if ent is None or not ent[0].intact():
+            raise _lib.DgvitError(f"{who}: parameter storage was replaced (e.g. by .to() or deepcopy); rebuild the optimiser")
+        by_home.setdefault(id(ent[0]), (ent[0], []))[1].append(ent[1])
+    runs = []
+    for home, idx in by_home.values():
+        idx.sort()
+        cur = [idx[0]]
+        steps = steps_of(home) if steps_of is not None else None
+        for a, b in zip(idx, idx[1:]):
+            if b == a + 1 and (steps is None or steps[b] == steps[a]) and home.sections[b] == home.sections[a]:
+                cur.append(b)
+            else:
+                runs.append((home, cur))
+                cur = [b]
+        runs.append((home, cur))
+    return runs
+
+
+class _ClipScratch:
+    """Device scratch of one gradient-norm clip: DGVIT_GRAD_NORM_PARTIALS doubles and, behind them, the two floats of
+    dgvit_grad_clip_coef (total norm, coefficient).  Never zeroed: the first norm launch of a clip writes every partial."""
+
+    def __init__(self, device):
+        self.device = device
+        self.buf = torch.empty(_lib.GRAD_NORM_PARTIALS + 1, dtype=torch.float64, device=device)
+        out = self.buf[_lib.GRAD_NORM_PARTIALS:].view(torch.float32)
+        self.norm, self.coef = out[0], out[1]            # 0-d views
+
+    def measure(self, lib, flats, max_norm: float) -> None:
+        """norm of the concatenation of the flat buffers ``flats`` and its coefficient for ``max_norm``: len(flats) + 1 launches"""
+        with torch.cuda.device(self.device):
+            for k, g in enumerate(flats):
+                if g.device != self.device:
+                    raise _lib.DgvitError("gradient-norm clipping needs all gradients on one device")
+                rc = lib.dgvit_grad_sqnorm_partials(ctypes.c_void_p(g.data_ptr()), g.numel(), ctypes.c_void_p(self.buf.data_ptr()),
+                                                    int(k > 0), _stream())
+                _lib.check(rc, "dgvit_grad_sqnorm_partials")
+            rc = lib.dgvit_grad_clip_coef(ctypes.c_void_p(self.buf.data_ptr()), max_norm, ctypes.c_void_p(self.norm.data_ptr()), _stream())
+            _lib.check(rc, "dgvit_grad_clip_coef")
+
+
 class FlatAdam:
     """``torch.optim.Adam`` semantics (amsgrad=False) with one HIP kernel per contiguous run of a flat parameter buffer.
 
@@ -192,10 +266,25 @@ class FlatAdam:
     gradient later starts its bias correction at 1 then.  Build it after ``module.to(device)``.  ``capturable=True`` keeps
     the step counter in device memory (like torch's ``capturable`` optimisers) so that ``step()`` can be recorded into a HIP
     graph; every replay must then see the same set of parameters with gradients.
+
+    ``max_grad_norm`` (None: off; else a positive number): ``step()`` clips the global 2-norm of the gradients to it first, like
+    ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` followed by the step (attention_imitating.py:66-67).  The norm covers
+    exactly this optimiser's parameters that have a gradient at this step.  It is one streaming read per run of the flat buffers
+    (double accumulation, fixed summation order); the coefficient ``min(max_grad_norm / (norm + 1e-6), 1)`` stays in device memory
+    and Adam multiplies each gradient element by it as it reads it (weight decay is added to the clipped gradient, as in
+    clip-then-step).  Nothing synchronises, so the step stays graph-capturable, with ``capturable`` True or False.  Unlike
+    clip-then-step the ``.grad`` tensors are NOT modified: the clipped gradient is never written.  ``last_grad_norm`` is the norm
+    before clipping as a 0-d device tensor (a view of the optimiser's scratch, overwritten by the next step; None before the first
+    clipped step).  ``max_grad_norm`` is a plain attribute read on every ``step()``; it is passed as a kernel argument, so a
+    captured graph keeps the value it was captured with.  It is not part of ``state_dict()`` (it is not optimiser state in torch
+    either).
     """
 
     def __init__(self, params: Union[torch.nn.Module, Iterable], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 capturable: bool = False):
+                 capturable: bool = False, max_grad_norm=None):
+        if max_grad_norm is not None:
+            _check_max_norm(max_grad_norm, "FlatAdam: max_grad_norm")
+        self.max_grad_norm, self._clip, self.last_grad_norm = max_grad_norm, None, None
         self.capturable, self._step_dev = bool(capturable), None
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         items = [params] if isinstance(params, torch.nn.Module) else list(params)
@@ -270,30 +359,13 @@ class FlatAdam:
 
     def _runs(self):
         """[(home, [param indices])]: maximal runs of adjacent slots whose parameters have a gradient and equal step counts."""
-        by_home = {}
-        for p in self.params:
-            if p.grad is None:
-                continue
-            ent = _HOME_OF.get(p)
-            if ent is None or not ent[0].intact():
-                raise _lib.DgvitError("FlatAdam: parameter storage was replaced (e.g. by .to() or deepcopy); rebuild the optimiser")
-            by_home.setdefault(id(ent[0]), (ent[0], []))[1].append(ent[1])
-        runs = []
-        for home, idx in by_home.values():
-            idx.sort()
-            cur = [idx[0]]
-            steps = self._state(home).steps
-            for a, b in zip(idx, idx[1:]):
-                if b == a + 1 and steps[b] == steps[a] and home.sections[b] == home.sections[a]:
-                    cur.append(b)
-                else:
-                    runs.append((home, cur))
-                    cur = [b]
-            runs.append((home, cur))
-        return runs
+        return _adjacent_runs(self.params, lambda home: self._state(home).steps)
 
     @torch.no_grad()
     def step(self) -> None:
+        max_norm = self.max_grad_norm
+        if max_norm is not None:
+            max_norm = _check_max_norm(max_norm, "FlatAdam: max_grad_norm")
         lib = _lib.load()
         runs = self._runs()
         if not runs:
@@ -307,20 +379,34 @@ class FlatAdam:
                 self._step_dev = torch.full((1,), self._state(runs[0][0]).steps[runs[0][1][0]], dtype=torch.int64, device=runs[0][0].flat.device)
             self._step_dev += 1                      # a device op: replayed with the graph
             step_ptr = ctypes.c_void_p(self._step_dev.data_ptr())
-        for home, idx in runs:
+        grads = None
+        if max_norm is not None:
+            # every run's gradient resolved once, for the norm and for Adam; 2 * runs + 1 launches in all
+            grads = [home.grad_run(idx) for home, idx in runs]
+            if self._clip is None or self._clip.device != grads[0].device:
+                self._clip = _ClipScratch(grads[0].device)
+                self.last_grad_norm = self._clip.norm
+            self._clip.measure(lib, grads, max_norm)
+        for k, (home, idx) in enumerate(runs):
             lo = home.offsets[idx[0]]
             n = home.offsets[idx[-1]] + _al4(home.params[idx[-1]].numel()) - lo
-            g = home.grad_run(idx)
+            g = grads[k] if grads is not None else home.grad_run(idx)
             st = self._state(home)
             m, v = st.moments()
             t = st.steps[idx[0]] + 1
             for i in idx:
                 st.steps[i] = t
             with torch.cuda.device(home.flat.device):
-                rc = lib.dgvit_adam_step(ctypes.c_void_p(home.flat.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr()),
-                                         ctypes.c_void_p(m.data_ptr() + 4 * lo), ctypes.c_void_p(v.data_ptr() + 4 * lo), n,
-                                         self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t, step_ptr, _stream())
-            _lib.check(rc, "dgvit_adam_step")
+                if grads is None:
+                    rc = lib.dgvit_adam_step(ctypes.c_void_p(home.flat.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr()),
+                                             ctypes.c_void_p(m.data_ptr() + 4 * lo), ctypes.c_void_p(v.data_ptr() + 4 * lo), n,
+                                             self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t, step_ptr, _stream())
+                else:
+                    rc = lib.dgvit_adam_step_scaled(ctypes.c_void_p(home.flat.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr()),
+                                                    ctypes.c_void_p(m.data_ptr() + 4 * lo), ctypes.c_void_p(v.data_ptr() + 4 * lo), n,
+                                                    self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t, step_ptr,
+                                                    ctypes.c_void_p(self._clip.coef.data_ptr()), _stream())
+            _lib.check(rc, "dgvit_adam_step" if grads is None else "dgvit_adam_step_scaled")
         # the kernel wrote the parameters through raw pointers: no autograd version counter moved
         F_.notify_parameters_changed(self.params)
 
@@ -404,3 +490,76 @@ def hard_update(target: torch.nn.Module, source: torch.nn.Module) -> None:
     tb, sb = _flat_pair(target, source)
     tb.flat.copy_(sb.flat)
     F_.notify_parameters_changed(target)
+
+
+_CLIP_SCRATCH = {}    # device -> _ClipScratch of the stand-alone clip_grad_norm_
+_FLT_MAX = 3.4028234663852886e38
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` (attention_imitating.py:66) on the flat buffers: scales the ``.grad`` of ``parameters`` (a
+    module, a tensor or an iterable of tensors; a repeated entry counts once) in place by ``min(max_norm / (norm + 1e-6), 1)`` and
+    returns their total 2-norm as a 0-d device tensor.  Nothing synchronises unless ``error_if_nonfinite`` asks for the read-back.
+
+    Gradients that are adjacent views of one flat buffer (the fused encoder backward's) form one run: one norm launch and one
+    in-place scale launch over the whole run (its padding lanes are zero).  The remaining gradients (heads, log_alpha) are gathered
+    by their home for the norm, as Adam gathers them, and scaled with one ``torch._foreach_mul_`` by the device coefficient.
+    Parameters that have no flat home yet get one (as ``FlatAdam`` gives them).  Only ``norm_type=2`` exists here; gradients must be
+    on the device -- there is no CPU path.  ``foreach`` is accepted and ignored.  ``max_norm=inf`` measures without scaling.
+    ``FlatAdam(max_grad_norm=…)`` does the same without the write pass."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"dgvit_amd.optim.clip_grad_norm_ supports norm_type=2 only (got {norm_type!r}); use "
+                         "torch.nn.utils.clip_grad_norm_ for other norms")
+    max_norm = float(max_norm)
+    if not (max_norm > 0):
+        raise ValueError(f"clip_grad_norm_: max_norm must be greater than 0, got {max_norm!r}")
+    if isinstance(parameters, torch.nn.Module):
+        modules, items = [parameters], list(parameters.parameters())
+    else:
+        modules, items = [], [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    params, seen = [], set()
+    for p in items:
+        if not isinstance(p, torch.Tensor):
+            raise TypeError(f"clip_grad_norm_: expected a module, a tensor or an iterable of tensors, got {type(p).__name__}")
+        if p.grad is not None and id(p) not in seen:
+            seen.add(id(p))
+            params.append(p)
+    if not params:
+        return torch.tensor(0.0)
+    if not all(p.grad.is_cuda and p.is_cuda for p in params):
+        raise _lib.DgvitError("clip_grad_norm_: gradients must be on a ROCm device; there is no CPU path")
+    if not all(p.grad.dtype == torch.float32 and p.dtype == torch.float32 and p.is_leaf for p in params):
+        raise _lib.DgvitError("clip_grad_norm_: fp32 leaf tensors with fp32 gradients only")
+    lib = _lib.load()
+    for m in modules:
+        home_of(m)
+    loose = [p for p in params if _HOME_OF.get(p) is None or not _HOME_OF[p][0].intact()]
+    if loose:
+        _Home(loose)
+    flats, in_place, gathered = [], [], []
+    for home, idx in _adjacent_runs(params, who="clip_grad_norm_"):
+        view = home.grad_view(idx)
+        if view is not None:
+            in_place.append(view)
+            flats.append(view)
+        else:
+            flats.append(home.grad_run(idx, count=False))
+            gathered.extend(home.params[i].grad for i in idx)
+    dev = flats[0].device
+    scratch = _CLIP_SCRATCH.get(dev)
+    if scratch is None:
+        scratch = _CLIP_SCRATCH[dev] = _ClipScratch(dev)
+    scratch.measure(lib, flats, min(max_norm, _FLT_MAX))
+    total = scratch.norm.clone()        # the scratch is overwritten by the next call
+    if error_if_nonfinite and not bool(torch.isfinite(total)):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    with torch.cuda.device(dev):
+        for g in in_place:
+            rc = lib.dgvit_scale_by_device_scalar(ctypes.c_void_p(g.data_ptr()), g.numel(), ctypes.c_void_p(scratch.coef.data_ptr()), _stream())
+            _lib.check(rc, "dgvit_scale_by_device_scalar")
+        if gathered:
+            torch._foreach_mul_(gathered, scratch.coef)
+    return total

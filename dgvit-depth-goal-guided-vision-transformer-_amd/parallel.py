@@ -26,6 +26,11 @@ _OVERLAP_HW_QUEUES = 8
 
 
 class GradSync:
+    """All-reduce of the gradients of ``modules`` across ranks (see the module docstring): ``zero_grad()``, backward, ``sync()``,
+    then the optimiser step.  Gradient-norm clipping needs nothing extra: ``FlatAdam(max_grad_norm=…)`` and
+    ``optim.clip_grad_norm_`` read the gradients where Adam reads them, at ``step()`` / at the call, so the rule "sync, then step"
+    makes every rank compute the norm of the same reduced gradients and therefore the same coefficient, bit for bit."""
+
     def __init__(self, modules: Iterable[torch.nn.Module], process_group=None, bucket_bytes: int = 64 << 20,
                  force_collective: bool = False, overlap: bool = False):
         """``force_collective``: issue the all-reduce even in a world of one rank (a 1-rank RCCL group reduces a buffer onto

@@ -412,6 +412,33 @@ int dgvit_adam_step(float* p, const float* g, float* m, float* v, long long n, f
 int dgvit_soft_update(float* target, const float* source, long long n, float tau, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Gradient-norm clipping between the backward and Adam: torch.nn.utils.clip_grad_norm_(parameters, max_norm) with norm_type 2
+ * (attention_imitating.py:45-67) on the flat gradient buffers, with the norm and the coefficient left in device memory -- nothing
+ * synchronises, everything is graph-capturable.  Flat buffers as above: fp32, n a positive multiple of 4, 16-byte aligned.
+ *
+ * dgvit_grad_sqnorm_partials: a fixed grid of DGVIT_GRAD_NORM_PARTIALS workgroups; workgroup b sums g[i]^2 over its grid-stride share
+ *   in DOUBLE and stores the sum to partials[b] (accumulate == 0) or partials[b] + sum (accumulate != 0: the next buffer of the same
+ *   parameter set, in stream order).  `partials`: DGVIT_GRAD_NORM_PARTIALS doubles, 16-byte aligned.  Every slot is written by the
+ *   first (non-accumulating) call, so the scratch needs no memset; there are no atomics, and the result depends on the data and n only.
+ * dgvit_grad_clip_coef: one workgroup sums the partials in a fixed order in double and writes
+ *     out[0] = (float)sqrt(sum)                                        the total norm
+ *     out[1] = min(max_norm / (out[0] + 1e-6f), 1) in fp32             the coefficient, evaluated as torch does: the reciprocal of
+ *              (out[0] + 1e-6f) rounded to fp32, times max_norm, then clamp(max=1).  A NaN norm gives a NaN coefficient (torch.clamp
+ *              propagates NaN), an infinite norm gives 0.  max_norm must be finite and > 0.
+ * dgvit_adam_step_scaled: dgvit_adam_step on the gradient g[i] * *grad_scale_dev; the product is rounded to fp32 on its own before
+ *   weight decay is added, so the result is bit-identical to dgvit_adam_step on a buffer scaled beforehand -- without writing it.
+ *   grad_scale_dev (a DEVICE pointer, e.g. out + 1 of dgvit_grad_clip_coef) must not be NULL: the unscaled step is dgvit_adam_step.
+ * dgvit_scale_by_device_scalar: x[i] = *scale_dev * x[i] in place (the stand-alone clip of .grad buffers).
+ * -------------------------------------------------------------------------------------------- */
+#define DGVIT_GRAD_NORM_PARTIALS 512
+int dgvit_grad_sqnorm_partials(const float* g, long long n, double* partials, int accumulate, void* stream);
+int dgvit_grad_clip_coef(const double* partials, float max_norm, float* out /* 2 floats: total norm, coefficient */, void* stream);
+int dgvit_adam_step_scaled(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, long long step, const long long* step_dev,
+                           const float* grad_scale_dev, void* stream);
+int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * bf16 configuration (BASELINE.json config 5: 224x224 depth frames, 12-layer ViT-Base variant with goal token, bf16).
  * Same GoT.forward (GoalFormer.py:156-171) with bf16 STORAGE for every GEMM operand (LayerNorm outputs, qkv, attention
  * output, MLP hidden, the four weight matrices of each block and the patch weight) and fp32 everywhere else (residual
