@@ -101,6 +101,11 @@ SIGNATURES = {
     "dgvit_cnn_backward_v2": (_I, [_P, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_gather_rows": (_I, [_P, _P, _P, _LL, _LL, _LL, _P]),
     "dgvit_gather_shift_frames": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _I, _I, _ULL, _P, _P]),
+    "dgvit_per_tree_floats": (_LL, [_LL]),
+    "dgvit_per_init": (_I, [_P, _LL, _P]),
+    "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),
+    "dgvit_per_update": (_I, [_P, _LL, _LL, _P, _P, _LL, _F, _F, _P]),
+    "dgvit_per_sample": (_I, [_P, _LL, _P, _LL, _I, _F, _P, _P, _P]),
     "dgvit_depth_preprocess_scratch_floats": (_LL, [_I, _I, _I]),
     "dgvit_depth_to_state": (_I, [_P, _P, _F, _ULL, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
     "dgvit_depth_normalize_u8": (_I, [_P, _P, _P, _LL, _I, _I, _I, _P]),

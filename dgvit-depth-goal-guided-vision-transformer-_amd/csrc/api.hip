@@ -249,6 +249,20 @@ extern "C" int dgvit_gather_shift_frames(const float* src, const long long* idx,
                                          const unsigned long long* seed_dev, void* stream) {
   return gather_shift_frames(src, idx, out, shifts_out, nsel, H, W, row_floats, nrows, pad, stream_id, seed, seed_dev, (hipStream_t)stream);
 }
+// prioritized replay (replay.hip)
+extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }
+extern "C" int dgvit_per_init(float* tree, long long capacity, void* stream) { return per_init(tree, capacity, (hipStream_t)stream); }
+extern "C" int dgvit_per_set_range(float* tree, long long capacity, long long first, long long count, void* stream) {
+  return per_set_range(tree, capacity, first, count, (hipStream_t)stream);
+}
+extern "C" int dgvit_per_update(float* tree, long long capacity, long long stored, const long long* idx, const float* prio, long long n,
+                                float alpha, float eps, void* stream) {
+  return per_update(tree, capacity, stored, idx, prio, n, alpha, eps, (hipStream_t)stream);
+}
+extern "C" int dgvit_per_sample(const float* tree, long long capacity, const float* uniforms, long long n, int stratified, float beta,
+                                long long* idx_out, float* weights_out, void* stream) {
+  return per_sample(tree, capacity, uniforms, n, stratified, beta, idx_out, weights_out, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- SURVEY 8(f4)
 extern "C" long long dgvit_depth_preprocess_scratch_floats(int B, int H, int W) {

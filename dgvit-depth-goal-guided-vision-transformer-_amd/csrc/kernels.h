@@ -1,5 +1,5 @@
 // Internal prototypes of the launch functions implemented in the kernel translation units
-// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, gemm.hip, gemm_reduce.hip); the schedules in encoder.hip, encoder_bf16.hip
+// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, replay.hip, gemm.hip, gemm_reduce.hip); the schedules in encoder.hip, encoder_bf16.hip
 // and cnn_api.hip call these.
 #pragma once
 #include "common.h"
@@ -69,6 +69,14 @@ int gather_rows(const float*, const long long*, float*, long long, long long, lo
 int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
                         long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
                         const unsigned long long* seed_dev, hipStream_t stream);
+// replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
+long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
+int per_init(float* tree, long long capacity, hipStream_t stream);
+int per_set_range(float* tree, long long capacity, long long first, long long count, hipStream_t stream);
+int per_update(float* tree, long long capacity, long long stored, const long long* idx, const float* prio, long long n, float alpha, float eps,
+               hipStream_t stream);
+int per_sample(const float* tree, long long capacity, const float* uniforms, long long n, int stratified, float beta, long long* idx_out,
+               float* weights_out, hipStream_t stream);
 int mean_bwd(const float*, float*, int, int, int, hipStream_t);
 int depth_normalize_u8(const float*, float*, float*, int, int, int, hipStream_t);
 long long depth_normalize_scratch_floats(int);

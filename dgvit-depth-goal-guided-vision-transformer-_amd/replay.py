@@ -133,3 +133,148 @@ class DeviceReplayBuffer:
             out["obs_shift"], out["next_obs_shift"] = (torch.zeros(B, 2, dtype=torch.int32, device=self.device) for _ in range(2))
         out["indexes"] = idx
         return out
+
+
+PER_MAX_SIZE = 1 << 24      # include/dgvit_hip.h: the radix-64 tree has at most four levels
+
+
+def _unit(name: str, v) -> float:
+    """a real number in [0, 1] (bools and everything else: ValueError)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+def per_tree_layout(capacity: int):
+    """[(offset of the sums, padded length)] per level and the floats of the whole tree, as dgvit_per_tree_floats lays it out: a 64-float
+    header, then for each level pad64(n_l) sums and pad64(n_l) mins; n_0 = capacity, n_l = ceil(n_{l-1} / 64), last level n_l <= 64."""
+    if not 1 <= capacity <= PER_MAX_SIZE:
+        raise ValueError(f"size must be in [1, 2^24], got {capacity}")
+    levels, off, n = [], 64, int(capacity)
+    while True:
+        pad = (n + 63) // 64 * 64
+        levels.append((off, pad))
+        off += 2 * pad
+        if n <= 64:
+            return levels, off
+        n = (n + 63) // 64
+
+
+class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
+    """``DeviceReplayBuffer`` with proportional prioritization (Schaul et al. 2016) kept on the device: a radix-64 sum / min tree over the
+    ring's slots in one fp32 tensor (``self.tree``; layout and draw in include/dgvit_hip.h).  A stored transition gets the
+    largest priority seen so far, ``sample`` draws slot i with probability leaf_i / total, leaf_i = (|priority_i| + eps)^alpha, and adds
+    the importance weights (p_min / leaf_i)^beta -- cpprb's (N P(i))^-beta normalised by its maximum.  Nothing synchronises with the host,
+    so the draw, the gathers and the write-back are capturable in one graph.  What a SAC critic needs::
+
+        w = batch["weights"]
+        critic_loss = (w * (q - y) ** 2).mean()
+        buf.update_priorities(batch["indexes"], (q - y).abs().detach())
+
+    Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
+
+    def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",
+                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4):
+        self.alpha = _unit("alpha", alpha)
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0.0 <= float(eps) < float("inf"):
+            raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
+        self.eps = float(eps)
+        self._levels, floats = per_tree_layout(int(size))
+        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed)
+        lib = _lib.load()
+        if lib.dgvit_per_tree_floats(self.size) != floats:
+            raise _lib.DgvitError("dgvit_per_tree_floats disagrees with replay.per_tree_layout; rebuild the library")
+        self.tree = torch.empty(floats, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.dgvit_per_init(self._tree_ptr(), self.size, self._stream()), "dgvit_per_init")
+
+    def _tree_ptr(self):
+        return ctypes.c_void_p(self.tree.data_ptr())
+
+    @staticmethod
+    def _stream():
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def _store_rows(self, host) -> None:
+        """the base's copy, then the ring range just written takes the max priority (an overwritten slot forgets its old one)"""
+        n, i = min(host.shape[0], self.size), self.next_index
+        super()._store_rows(host)
+        first = min(n, self.size - i)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            for start, count in ((i, first), (0, n - first)):
+                if count > 0:
+                    _lib.check(lib.dgvit_per_set_range(self._tree_ptr(), self.size, start, count, self._stream()), "dgvit_per_set_range")
+
+    def draw(self, batch_size: int, beta: float = 0.4, stratified: bool = False,
+             uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The index draw alone: ((B,) int64 indices, (B, 1) fp32 importance weights).  ``uniforms`` ((B,) fp32 on the device, values in
+        [0, 1]) makes the draw reproducible; absent, it comes from ``self.gen``.  ``stratified`` draws sample j from the j-th of B equal
+        slices of the total priority."""
+        beta = _unit("beta", beta)
+        if self.stored == 0:
+            raise RuntimeError("cannot sample from an empty buffer")
+        B = int(batch_size)
+        if uniforms is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DgvitError("sample() inside a stream capture needs uniforms=: pass a persistent (B,) fp32 device tensor and refill "
+                                      "it inside the capture (tensor.uniform_() there uses torch's graph-safe default generator)")
+            uniforms = torch.rand(B, dtype=torch.float32, device=self.device, generator=self.gen)
+        elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or uniforms.device != self.store["obs"].device
+              or uniforms.numel() != B or not uniforms.is_contiguous()):
+            raise ValueError(f"uniforms must be a contiguous fp32 tensor of {B} values on {self.store['obs'].device}")
+        idx = torch.empty(B, dtype=torch.int64, device=self.device)
+        weights = torch.empty(B, 1, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _lib.load().dgvit_per_sample(self._tree_ptr(), self.size, ctypes.c_void_p(uniforms.data_ptr()), B, int(bool(stratified)), beta,
+                                              ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(weights.data_ptr()), self._stream())
+        _lib.check(rc, "dgvit_per_sample")
+        return idx, weights
+
+    def sample(self, batch_size: int, beta: float = 0.4, stratified: bool = False, uniforms: Optional[torch.Tensor] = None,
+               random_shift: int = 0, return_shifts: bool = False) -> Dict[str, torch.Tensor]:
+        """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift`` and
+        ``return_shifts`` as there).  The base's dict plus ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor."""
+        idx, weights = self.draw(batch_size, beta, stratified, uniforms)
+        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts)
+        out["weights"] = weights
+        return out
+
+    def update_priorities(self, indexes: torch.Tensor, priorities: torch.Tensor) -> None:
+        """leaf[indexes[j]] <- (|priorities[j]| + eps)^alpha: ``indexes`` any integer tensor of B entries, ``priorities`` (B,) or (B, 1)
+        fp32 on the device, typically ``|TD error|.detach()``.  Indices outside [0, stored) are ignored, a repeated index keeps the
+        largest of its new values, a non-finite priority takes the max priority."""
+        if not torch.is_tensor(indexes) or indexes.dtype.is_floating_point or indexes.dtype.is_complex or indexes.dtype == torch.bool:
+            raise ValueError("indexes must be an integer tensor")
+        if not torch.is_tensor(priorities) or priorities.dtype != torch.float32 or priorities.device != self.store["obs"].device:
+            raise ValueError(f"priorities must be an fp32 tensor on {self.store['obs'].device}")
+        idx = indexes.to(self.device, torch.int64).reshape(-1).contiguous()
+        prio = priorities.detach().reshape(-1).contiguous()
+        if prio.numel() != idx.numel() or priorities.dim() > 2 or (priorities.dim() == 2 and priorities.shape[1] != 1) or idx.numel() == 0:
+            raise ValueError(f"priorities must be (B,) or (B, 1) with B = {idx.numel()} >= 1 entries, got {tuple(priorities.shape)}")
+        with torch.cuda.device(self.device):
+            rc = _lib.load().dgvit_per_update(self._tree_ptr(), self.size, self.stored, ctypes.c_void_p(idx.data_ptr()),
+                                              ctypes.c_void_p(prio.data_ptr()), idx.numel(), self.alpha, self.eps, self._stream())
+        _lib.check(rc, "dgvit_per_update")
+
+    def priorities(self) -> torch.Tensor:
+        """the (stored,) fp32 leaf values (|priority| + eps)^alpha, a copy"""
+        off = self._levels[0][0]
+        return self.tree[off:off + self.stored].clone()
+
+    @property
+    def total_priority(self) -> torch.Tensor:
+        """the sum of all leaves (0-d device tensor): the top block's sums added up"""
+        off = self._levels[-1][0]
+        return self.tree[off:off + 64].sum()
+
+    @property
+    def min_priority(self) -> torch.Tensor:
+        """the smallest stored leaf (0-d device tensor; +inf while empty): the p_min of the importance weights"""
+        off, pad = self._levels[-1]
+        return self.tree[off + pad:off + pad + 64].min()
+
+    @property
+    def max_priority(self) -> torch.Tensor:
+        """the largest leaf ever written (0-d device tensor; 1 at first, never falls): what a newly stored transition gets"""
+        return self.tree[0].clone()

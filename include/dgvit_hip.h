@@ -383,6 +383,52 @@ int dgvit_gather_shift_frames(const float* src, const long long* idx /* may be N
                               unsigned long long seed, const unsigned long long* seed_dev, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
+ * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
+ *
+ * One caller-allocated fp32 buffer `tree` of dgvit_per_tree_floats(capacity) floats, 16-byte aligned, holds a radix-64 tree over the
+ * ring's `capacity` slots (1 .. 2^24) with a sum and a min for every node:
+ *   [0, 64)   header: word 0 = the running max leaf (1.0 after init, as cpprb), word 1 = its value when the last update began,
+ *             the rest reserved
+ *   level l = 0 .. L-1, one after the other: pad64(n_l) sums, then pad64(n_l) mins;  n_0 = capacity, n_l = ceil(n_{l-1} / 64), and
+ *             the last level is the first with n_l <= 64 (the top block; there is no separate root)
+ *   floats    = 64 + 2 * sum_l pad64(n_l)      (capacity 64: 192, 65: 448, 4096: 8384, 4097: 8768, 2^24: 34087104)
+ * Padding entries and slots never written hold sum 0 and min +inf.  A leaf is clamp((|priority| + eps)^alpha, 2^-64, 2^64).
+ * A parent is always recomputed from its 64 children in one fixed order, never updated by a delta: its bits are a function of its
+ * children alone, rebuilding twice is harmless, rounding does not accumulate over updates, and no float atomic is used.
+ *
+ * dgvit_per_tree_floats: host only; -1 when capacity is outside [1, 2^24].
+ * dgvit_per_init:       sums 0, mins +inf, max leaf 1.
+ * dgvit_per_set_range:  leaves [first, first + count) (inside the ring, count >= 1) take the current max leaf -- what a newly stored
+ *                       transition gets -- and their ancestors are rebuilt.
+ * dgvit_per_update:     leaf[idx[j]] from prio[j], j < n, 1 <= n < 2^24 (idx int64, prio fp32, both read when the kernels run).
+ *                       An index outside [0, stored) is ignored, not clamped.  The sign of a priority is ignored; a non-finite one
+ *                       takes the max leaf as it stood when the call began.  alpha == 1 takes no powf: the leaf is |p| + eps, clamped.
+ *                       An index that occurs more than once keeps the LARGEST of its new leaves, whatever its old one was (pass 1
+ *                       zeroes the addressed leaves, pass 2 is an integer max on the float bits).  The max leaf is raised the same way
+ *                       and never falls.  Then one wave per index and level rebuilds the ancestors.  0 <= alpha <= 1, eps >= 0.
+ * dgvit_per_sample:     idx_out[j] (int64) and weights_out[j] (fp32) from uniforms[j] in [0, 1] (clamped; read when the kernel runs),
+ *                       1 <= n < 2^24, one wave per sample.  total = the sum of the top block;
+ *                         mass = u_j * total                                  (stratified == 0)
+ *                         mass = ((float)j + u_j) / (float)n * total          (stratified == 1)
+ *                       At each level, from the top block down, lane c holds the sum of child c and the wave an inclusive prefix
+ *                       (Hillis-Steele, 6 steps); the chosen child is the first with child > 0 and prefix > mass, or, when none
+ *                       qualifies (u == 1, or rounding between a parent and the prefix of its children), the last child with a
+ *                       nonzero sum; mass <- max(mass - prefix of the children before it, 0) and the wave descends.  A slot with
+ *                       leaf 0 or an index >= capacity is never returned; an all-zero tree gives index 0 and weight 1.
+ *                         weights_out[j] = (p_min / leaf)^beta,  p_min = the min of the top block,  0 <= beta <= 1 (0: exactly 1)
+ *                       which is cpprb's (N P(i))^-beta / max_k w_k: N and total cancel.
+ * Every call is capturable in a HIP graph and none synchronises.
+ * -------------------------------------------------------------------------------------------- */
+long long dgvit_per_tree_floats(long long capacity);
+int dgvit_per_init(float* tree, long long capacity, void* stream);
+int dgvit_per_set_range(float* tree, long long capacity, long long first, long long count, void* stream);
+int dgvit_per_update(float* tree, long long capacity, long long stored, const long long* idx, const float* prio, long long n, float alpha,
+                     float eps, void* stream);
+int dgvit_per_sample(const float* tree, long long capacity, const float* uniforms, long long n, int stratified, float beta,
+                     long long* idx_out, float* weights_out, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * the depth-frame preprocessing in front of the path -- what env_lab.py does with OpenCV on the
  * host for every camera message (listener_callback :420-434: cv2.normalize MINMAX -> uint8, add_nose :78-89 (N(0, 50) noise,
  * clip, 5x5 Gaussian blur), blurring :69-76 (11x11 blur of the centre band)) and for every step (:295-299: cv2.resize to
