@@ -137,7 +137,7 @@ extern "C" int dgvit_gemm(int layout, int epilogue, const float* A, int lda, con
   if (pl.nsplit > 1 && scratch && scratch_floats >= al4(pl.tiles) + al4(pl.slab_floats)) {
     p.counters = reinterpret_cast<int*>(scratch); p.counter_capacity = pl.tiles;
     p.slabs = scratch + al4(pl.tiles); p.slab_capacity = scratch_floats - al4(pl.tiles);
-    HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(int) * pl.tiles, st));
+    TRY(zero_fill(scratch, (long long)sizeof(int) * pl.tiles, st));
   }
   return gemm_f32(layout, epilogue, p, 1, st);
 }

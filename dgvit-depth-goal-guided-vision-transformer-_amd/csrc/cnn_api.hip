@@ -80,7 +80,7 @@ extern "C" int dgvit_cnn_forward(const float* img, const float* const* params, f
     csk.ncounters = (int)csn.tiles;
     csk.slabs = wp[0] + conv_wp_floats(d) + al4(csn.tiles);
     csk.slab_cap = csn.slab;
-    HIP_TRY(hipMemsetAsync(csk.counters, 0, sizeof(int) * csn.tiles, st));
+    TRY(zero_fill(csk.counters, (long long)sizeof(int) * csn.tiles, st));
   }
   const float* in = img;
   for (int l = 0; l < 3; ++l) {

@@ -115,6 +115,12 @@ int reduce_slabs(const float* slabs, float* out, long long n, int nslab, long lo
 int reduce_slabs2(const float* slabs, float* out1, long long n1, float* out2, long long n, int nslab, long long slab_stride,
                   hipStream_t stream);
 
+// `bytes` (a multiple of 4, at a 4-byte aligned address) set to zero by a KERNEL.  Every zero fill of the library goes through here, not
+// through hipMemsetAsync: a memset recorded into a HIP graph does not reliably clear its range when the graph is replayed (measured:
+// after the second replay half the words of a freshly "cleared" range were nonzero; a captured learn() step then ran its in-launch
+// split-K GEMMs on dirty arrival counters and Adam consumed uninitialised gradients -- tests/test_gpu_sac_trajectory.py).
+int zero_fill(void* p, long long bytes, hipStream_t stream);
+
 // erf with |abs error| <= 1.5e-7 (Abramowitz & Stegun 7.1.26) on v_rcp_f32 / v_exp_f32: ~13 VALU instructions
 // instead of ~37 for ocml's erff (5.5e-7 once evaluated in fp32).  GELU(x) and GELU'(x) built on it stay within ~5e-7 of the exact-erf forms for
 // |x| <= 6 (checked against fp64 in tests/test_gpu_ops.py::test_gemm_epilogues), far inside the 1e-4 parity gate.

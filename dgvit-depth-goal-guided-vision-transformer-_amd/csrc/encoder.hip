@@ -259,7 +259,7 @@ int token_assembly(const Fwd& f, const float* img, const float* goal, float keep
   float* x = ws + w.x0;
   // arrival counters of the split GEMMs and of the small-batch blocks (adjacent): every user leaves them zero again
   if (!fused_first && (w.sk_slab_floats > 0 || w.bp_ncounters > 0))
-    HIP_TRY(hipMemsetAsync(ws + w.sk_counters, 0, sizeof(int) * (w.bp_counters - w.sk_counters + w.bp_ncounters), st));
+    TRY(zero_fill(ws + w.sk_counters, (long long)sizeof(int) * (w.bp_counters - w.sk_counters + w.bp_ncounters), st));
   if (!gather) TRY(patchify(img, patches, d.B, cfg->image_h, cfg->image_w, cfg->patch_h, cfg->patch_w, st));
   {
     GemmParams p = gp(patches, d.pd, f.params[P_PW], d.pd, x, d.D, d.B * d.P, d.D, d.pd);
@@ -581,7 +581,7 @@ int backward_layer(const Bwd& b, int i) {
     sk.attach(p);
     TRY(gemm_f32(GEMM_NN, EPI_STORE, p, 1, st));  // dln2 = dh1 W1
   }
-  if (last) HIP_TRY(hipMemsetAsync(dx2, 0, sizeof(float) * d.T * d.D, st));   // rows other than b*N get no gradient
+  if (last) TRY(zero_fill(dx2, (long long)sizeof(float) * d.T * d.D, st));   // rows other than b*N get no gradient
   TRY(layernorm_bwd(dln, lb + w.xmid, lb + w.mean2, lb + w.rstd2, lp[L_LN2W], dx, dx2, lg[L_LN2W], lg[L_LN2B], scratch + s.part_ln2, tok, d.D,
                     rs, st, gq));
   // ---- attention branch: xmid = to_out(attn(to_qkv(ln1))) + xin       (dx2 = d xmid)
@@ -718,7 +718,7 @@ extern "C" int dgvit_got_backward_v3_ev(const dgvit_config* cfg, const float* co
   if (s.sk_slab_floats > 0) {
     b.sk.counters = reinterpret_cast<int*>(scratch + s.sk_counters); b.sk.ncounters = (int)s.sk_ncounters;
     b.sk.slabs = scratch + s.sk_slabs; b.sk.slab_cap = s.sk_slab_floats;
-    HIP_TRY(hipMemsetAsync(b.sk.counters, 0, sizeof(int) * s.sk_ncounters, st));
+    TRY(zero_fill(b.sk.counters, (long long)sizeof(int) * s.sk_ncounters, st));
   }
   if (wgrad_overlap(cfg)) {
     TRY(side_init());

@@ -1,6 +1,8 @@
 // Deterministic fixed-order reductions of fp32 slabs: the split-K partials of the weight-gradient GEMMs and the per-workgroup column
 // partials of LayerNorm, the heads, the bf16 encoder and the CNN stack.  Several independent jobs share ONE launch (ReduceGroup,
 // common.h); every sum is taken in a fixed order, so results are bit-identical from run to run.
+#include <algorithm>
+
 #include "common.h"
 
 namespace {
@@ -64,7 +66,31 @@ __global__ void __launch_bounds__(256) reduce_slabs_scalar_kernel(const float* _
   else out2[i - n1] = s;
 }
 
+// n 32-bit words at p <- 0: 16-byte stores over the aligned body, word stores over the (at most three) words before and behind it
+__global__ void __launch_bounds__(256) zero_words_kernel(unsigned* __restrict__ p, long long n) {
+  const long long head = min(n, (long long)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2));
+  const long long n4 = (n - head) >> 2;
+  uint4* body = reinterpret_cast<uint4*>(p + head);
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) body[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (blockIdx.x == 0) {
+    const long long tail0 = head + 4 * n4;
+    if (threadIdx.x < head) p[threadIdx.x] = 0u;
+    if (tail0 + threadIdx.x < n) p[tail0 + threadIdx.x] = 0u;      // n - tail0 <= 3
+  }
+}
+
 }  // namespace
+
+int zero_fill(void* p, long long bytes, hipStream_t stream) {
+  if (bytes == 0) return DGVIT_OK;
+  DGVIT_CHECK_ARG(p && bytes > 0 && bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 3) == 0, "zero_fill: needs whole, aligned 32-bit words");
+  const long long n = bytes / 4, blocks = (n / 4 + 255) / 256;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(blocks, 1), 4096)), dim3(256), 0, stream,
+                     reinterpret_cast<unsigned*>(p), n);
+  DGVIT_CHECK_LAUNCH("zero_fill");
+  return DGVIT_OK;
+}
 
 // ---- grouped deterministic reductions ----------------------------------------------------------------------------------
 void reduce_group_init(ReduceGroup& g) { g.njobs = 0; g.first_block[0] = 0; }

@@ -185,7 +185,7 @@ inline int head_bwd(const Dims& d, const float* dfeat, const float* xl, const fl
     TRY(rmsnorm_bwd(dfeat, pooled, d.D, rms_g, dpool, d.D, drms_g, part, d.B, d.D, st));
     TRY(mean_bwd(dpool, dx, d.B, d.N, d.D, st));
   } else {
-    HIP_TRY(hipMemsetAsync(dx, 0, sizeof(float) * d.T * d.D, st));
+    TRY(zero_fill(dx, (long long)sizeof(float) * d.T * d.D, st));
     TRY(rmsnorm_bwd(dfeat, xl, (long long)d.N * d.D, rms_g, dx, (long long)d.N * d.D, drms_g, part, d.B, d.D, st));
   }
   if (events) TRY(mark_ready(events->head, st));
