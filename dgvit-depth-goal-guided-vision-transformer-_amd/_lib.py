@@ -118,6 +118,10 @@ SIGNATURES = {
     "dgvit_grad_clip_coef": (_I, [_P, _F, _P, _P]),
     "dgvit_adam_step_scaled": (_I, [_P, _P, _P, _P, _LL, _F, _F, _F, _F, _F, _LL, _P, _P, _P]),
     "dgvit_scale_by_device_scalar": (_I, [_P, _LL, _P, _P]),
+    # the SAC loss head (include/dgvit_hip.h: The SAC loss head)
+    "dgvit_sac_critic_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _I, _P]),
+    "dgvit_sac_actor_loss": (_I, [_P, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I, _I, _P]),
+    "dgvit_sac_scale_grads": (_I, [_P, _P, _LL, _P, _P]),
     "dgvit_got_bf16_weight_elems": (_LL, [_CFG]),
     "dgvit_got_pack_weights_bf16": (_I, [_CFG, _TABLE, _P, _LL, _I, _P]),
     "dgvit_got_bf16_workspace_bytes": (_LL, [_CFG, _I, _I]),

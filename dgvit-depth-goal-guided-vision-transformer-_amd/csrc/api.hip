@@ -239,6 +239,23 @@ extern "C" int dgvit_scale_by_device_scalar(float* x, long long n, const float* 
   return scale_by_device_scalar(x, n, scale_dev, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------------- SAC loss head (sac_loss.hip)
+extern "C" int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
+                                     const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
+                                     float gamma, float* target, float* td, float* loss, float* grads, int B, int A, void* stream) {
+  return sac_critic_loss(q1, q2, reward, done, weights, next_q1, next_q2, next_log_pi, log_alpha, alpha, gamma, target, td, loss, grads, B, A,
+                         (hipStream_t)stream);
+}
+extern "C" int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha,
+                                    int with_temperature, float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A,
+                                    void* stream) {
+  return sac_actor_loss(log_pi, q1_pi, q2_pi, log_alpha, alpha, with_temperature, target_entropy, losses, grads, dlog_alpha, B, A,
+                        (hipStream_t)stream);
+}
+extern "C" int dgvit_sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, void* stream) {
+  return sac_scale_grads(src, dst, n, scale_dev, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------- replay staging
 extern "C" int dgvit_gather_rows(const float* src, const long long* idx, float* out, long long nsel, long long row_floats,
                                  long long nrows, void* stream) {

@@ -57,6 +57,13 @@ int grad_clip_coef(const double* partials, float max_norm, float* out, hipStream
 int adam_step_scaled(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
                      const float* grad_scale_dev, hipStream_t);
 int scale_by_device_scalar(float* x, long long n, const float* scale_dev, hipStream_t);
+// the SAC loss head (sac_loss.hip): one launch per loss, alpha from device memory; done, weights, log_alpha, td and grads may be null
+int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* next_q1,
+                    const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma, float* target, float* td,
+                    float* loss, float* grads, int B, int A, hipStream_t);
+int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha, int with_temperature,
+                   float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A, hipStream_t);
+int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
 // the single-channel frame gradient from conv1's column gradient (rows of KP floats, 25 real taps): no ReLU mask

@@ -1,0 +1,188 @@
+// The SAC loss head: what SAC.learn computes between the network forwards and the backwards (DRL.py:384-425; SURVEY 3(A),
+// row a14), each loss with its gradient in ONE launch, the temperature read from device memory so that a captured step follows it.
+//   sac_critic_loss : y = r + (1 - done) gamma (min(q1n, q2n) - alpha logp_next);  loss = mean(w (q1 - y)^2) + mean(w (q2 - y)^2);
+//                     td[b] = mean_a |q1 - y|;  dq1 | dq2 for a unit upstream gradient
+//   sac_actor_loss  : policy_loss = mean(alpha logp - min(q1pi, q2pi)), alpha_loss = -log_alpha mean(logp + target_entropy), and
+//                     d logp | dq1pi | dq2pi and d log_alpha for unit upstream gradients
+//   sac_scale_grads : dst = *scale_dev * src, the backward of either loss for the 0-d upstream gradient autograd hands over
+// The two loss kernels are ONE workgroup of 256 threads: B * A is at most 2^20 elements of a few flops each, and one workgroup needs no
+// second launch, no atomics and no counters for its sums.  Every thread walks the elements i = tid, tid + 256, ... (row b = i / A), sums
+// in double, the wave folds with __shfl_down, the four waves meet in LDS and thread 0 writes the scalars: the same bits on every call.
+// Per element the arithmetic is in double from the fp32 inputs and rounded once where a value is stored; the stored fp32 target is the
+// one every later term uses, so td and the gradients are those of the returned tensor.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int SAC_MAX_ACTIONS = 16;          // as tanh_gaussian_*
+constexpr long long SAC_MAX_ELEMS = 1 << 20;
+
+__device__ __forceinline__ float sac_alpha(const float* __restrict__ log_alpha, float alpha) { return log_alpha ? expf(*log_alpha) : alpha; }
+
+__device__ __forceinline__ float sac_target(float r, float not_done, float gamma, float q1n, float q2n, float al, float nlp) {
+  return (float)((double)r + (double)not_done * (double)gamma * ((double)fminf(q1n, q2n) - (double)al * (double)nlp));
+}
+
+// the workgroup's sum of s in thread 0 (fixed order: lanes by __shfl_down, then wave 0 + 1, wave 2 + 3); wave_sum: 4 doubles of LDS
+__device__ __forceinline__ double block_sum(double s, double* wave_sum) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
+__global__ void __launch_bounds__(256) sac_critic_loss_kernel(const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ reward,
+                                                              const float* __restrict__ done, const float* __restrict__ weights,
+                                                              const float* __restrict__ q1n, const float* __restrict__ q2n,
+                                                              const float* __restrict__ nlogp, const float* __restrict__ log_alpha, float alpha,
+                                                              float gamma, float* __restrict__ y, float* __restrict__ td, float* __restrict__ loss,
+                                                              float* __restrict__ grads, int B, int A) {
+  __shared__ double wave_sum[4];
+  const float al = sac_alpha(log_alpha, alpha);
+  const int n = B * A;
+  const double inv_n = 1.0 / (double)n;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int b = i / A;
+    const float r = reward[b], nd = done ? 1.f - done[b] : 1.f, nlp = nlogp[b];
+    const double w = weights ? (double)weights[b] : 1.0;
+    const float yi = sac_target(r, nd, gamma, q1n[i], q2n[i], al, nlp);
+    const double e1 = (double)q1[i] - (double)yi, e2 = (double)q2[i] - (double)yi;
+    acc += w * (e1 * e1 + e2 * e2);
+    y[i] = yi;
+    if (grads) {
+      grads[i] = (float)(2.0 * w * e1 * inv_n);
+      grads[n + i] = (float)(2.0 * w * e2 * inv_n);
+    }
+    if (td && i == b * A) {     // the thread of a row's first element: the row's mean |q1 - y| in fp32
+      // In the order of torch's (q1 - y).abs().mean(1) on the device, so that the write-back is the number a caller would have computed
+      // from the returned target: P = the largest power of two <= A lanes, lane t sums elements t and t + P, the lanes fold pairwise
+      // (offsets 1, 2, 4, 8), times 1 / A.  Slots past P hold +0, which changes no sum of non-negative terms; the indices are
+      // compile-time constants after unrolling, so v[] stays in registers.
+      int P = 1;
+      while (2 * P <= A) P *= 2;
+      float v[SAC_MAX_ACTIONS];
+#pragma unroll
+      for (int t = 0; t < SAC_MAX_ACTIONS; ++t) {
+        v[t] = 0.f;
+        if (t < P) {
+          v[t] = t == 0 ? fabsf(q1[i] - yi) : fabsf(q1[i + t] - sac_target(r, nd, gamma, q1n[i + t], q2n[i + t], al, nlp));
+          if (t + P < A) v[t] += fabsf(q1[i + t + P] - sac_target(r, nd, gamma, q1n[i + t + P], q2n[i + t + P], al, nlp));
+        }
+      }
+#pragma unroll
+      for (int off = 1; off < SAC_MAX_ACTIONS; off <<= 1) {
+#pragma unroll
+        for (int t = 0; t < SAC_MAX_ACTIONS; t += 2 * off) v[t] += v[t + off];
+      }
+      td[b] = v[0] * (1.f / (float)A);
+    }
+  }
+  const double tot = block_sum(acc, wave_sum);
+  if (threadIdx.x == 0) loss[0] = (float)(tot * inv_n);
+}
+
+__global__ void __launch_bounds__(256) sac_actor_loss_kernel(const float* __restrict__ logp, const float* __restrict__ q1, const float* __restrict__ q2,
+                                                             const float* __restrict__ log_alpha, float alpha, int with_temperature,
+                                                             float target_entropy, float* __restrict__ losses, float* __restrict__ grads,
+                                                             float* __restrict__ dlog_alpha, int B, int A) {
+  __shared__ double wave_sum[2][4];
+  const float al = sac_alpha(log_alpha, alpha);
+  const int n = B * A;
+  const double inv_n = 1.0 / (double)n;
+  const float g_min = (float)(-inv_n), g_tie = (float)(-0.5 * inv_n), g_logp = (float)((double)al / (double)B);
+  double acc = 0.0, ent = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int b = i / A;
+    const float lp = logp[b], a1 = q1[i], a2 = q2[i];
+    acc += (double)al * (double)lp - (double)fminf(a1, a2);
+    if (i == b * A) {
+      ent += (double)lp + (double)target_entropy;
+      if (grads) grads[b] = g_logp;
+    }
+    if (grads) {                // torch.minimum's rule: the gradient goes to the smaller one, half to each at a tie
+      grads[B + i] = a1 < a2 ? g_min : (a1 == a2 ? g_tie : 0.f);
+      grads[B + n + i] = a2 < a1 ? g_min : (a1 == a2 ? g_tie : 0.f);
+    }
+  }
+  const double tot = block_sum(acc, wave_sum[0]);
+  const double etot = block_sum(ent, wave_sum[1]);
+  if (threadIdx.x == 0) {
+    losses[0] = (float)(tot * inv_n);
+    if (with_temperature) {
+      const double m = etot / (double)B;
+      losses[1] = (float)(-(double)*log_alpha * m);
+      if (dlog_alpha) dlog_alpha[0] = (float)(-m);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) sac_scale_grads_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n,
+                                                              const float* __restrict__ scale_dev) {
+  const float s = *scale_dev;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = s * src[i];
+}
+
+inline bool al4p(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+
+}  // namespace
+
+int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* next_q1,
+                    const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma, float* target, float* td,
+                    float* loss, float* grads, int B, int A, hipStream_t stream) {
+  DGVIT_CHECK_ARG(q1 && q2 && reward && next_q1 && next_q2 && next_log_pi, "sac_critic_loss: q1, q2, reward, next_q1, next_q2 and next_log_pi must not be null");
+  DGVIT_CHECK_ARG(target && loss, "sac_critic_loss: target and loss must not be null");
+  DGVIT_CHECK_ARG(B >= 1, "sac_critic_loss: B=%d must be at least 1", B);
+  DGVIT_CHECK_ARG(A >= 1 && A <= SAC_MAX_ACTIONS, "sac_critic_loss: A=%d must be in [1, %d]", A, SAC_MAX_ACTIONS);
+  DGVIT_CHECK_ARG((long long)B * A <= SAC_MAX_ELEMS, "sac_critic_loss: B*A=%lld must be at most %lld", (long long)B * A, SAC_MAX_ELEMS);
+  DGVIT_CHECK_ARG(log_alpha || std::isfinite(alpha), "sac_critic_loss: alpha=%g must be finite (or log_alpha given)", (double)alpha);
+  DGVIT_CHECK_ARG(std::isfinite(gamma), "sac_critic_loss: gamma=%g must be finite", (double)gamma);
+  DGVIT_CHECK_ARG(al4p(q1) && al4p(q2) && al4p(reward) && al4p(done) && al4p(weights) && al4p(next_q1) && al4p(next_q2) && al4p(next_log_pi) &&
+                      al4p(log_alpha) && al4p(target) && al4p(td) && al4p(loss) && al4p(grads),
+                  "sac_critic_loss: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(sac_critic_loss_kernel, dim3(1), dim3(256), 0, stream, q1, q2, reward, done, weights, next_q1, next_q2, next_log_pi, log_alpha,
+                       alpha, gamma, target, td, loss, grads, B, A);
+  }
+  DGVIT_CHECK_LAUNCH("sac_critic_loss");
+  return DGVIT_OK;
+}
+
+int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha, int with_temperature,
+                   float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A, hipStream_t stream) {
+  DGVIT_CHECK_ARG(log_pi && q1_pi && q2_pi && losses, "sac_actor_loss: log_pi, q1_pi, q2_pi and losses must not be null");
+  DGVIT_CHECK_ARG(B >= 1, "sac_actor_loss: B=%d must be at least 1", B);
+  DGVIT_CHECK_ARG(A >= 1 && A <= SAC_MAX_ACTIONS, "sac_actor_loss: A=%d must be in [1, %d]", A, SAC_MAX_ACTIONS);
+  DGVIT_CHECK_ARG((long long)B * A <= SAC_MAX_ELEMS, "sac_actor_loss: B*A=%lld must be at most %lld", (long long)B * A, SAC_MAX_ELEMS);
+  DGVIT_CHECK_ARG(with_temperature == 0 || with_temperature == 1, "sac_actor_loss: with_temperature=%d must be 0 or 1", with_temperature);
+  DGVIT_CHECK_ARG(log_alpha || std::isfinite(alpha), "sac_actor_loss: alpha=%g must be finite (or log_alpha given)", (double)alpha);
+  DGVIT_CHECK_ARG(!with_temperature || log_alpha, "sac_actor_loss: the temperature loss needs log_alpha (it is null)");
+  DGVIT_CHECK_ARG(!with_temperature || std::isfinite(target_entropy), "sac_actor_loss: target_entropy=%g must be finite", (double)target_entropy);
+  DGVIT_CHECK_ARG(al4p(log_pi) && al4p(q1_pi) && al4p(q2_pi) && al4p(log_alpha) && al4p(losses) && al4p(grads) && al4p(dlog_alpha),
+                  "sac_actor_loss: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(sac_actor_loss_kernel, dim3(1), dim3(256), 0, stream, log_pi, q1_pi, q2_pi, log_alpha, alpha, with_temperature, target_entropy,
+                       losses, grads, dlog_alpha, B, A);
+  }
+  DGVIT_CHECK_LAUNCH("sac_actor_loss");
+  return DGVIT_OK;
+}
+
+int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t stream) {
+  DGVIT_CHECK_ARG(src && dst && scale_dev, "sac_scale_grads: src, dst and scale_dev must not be null");
+  DGVIT_CHECK_ARG(n >= 1 && n <= 3 * SAC_MAX_ELEMS, "sac_scale_grads: n=%lld must be in [1, %lld]", n, 3 * SAC_MAX_ELEMS);
+  DGVIT_CHECK_ARG(al4p(src) && al4p(dst) && al4p(scale_dev), "sac_scale_grads: pointers must be 4-byte aligned");
+  long long blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(sac_scale_grads_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, dst, n, scale_dev);
+  }
+  DGVIT_CHECK_LAUNCH("sac_scale_grads");
+  return DGVIT_OK;
+}

@@ -171,6 +171,7 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         critic_loss = (w * (q - y) ** 2).mean()
         buf.update_priorities(batch["indexes"], (q - y).abs().detach())
 
+    ``sac_losses.critic_loss(weights=batch["weights"], done=batch["done"], ...)`` is that loss in one launch, and its ``.td`` the write-back.
     Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",

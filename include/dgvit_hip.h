@@ -485,6 +485,39 @@ int dgvit_adam_step_scaled(float* p, const float* g, float* m, float* v, long lo
 int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The SAC loss head: the arithmetic of SAC.learn between the network forwards and the backwards (DRL.py:384-425), one launch per
+ * loss with its gradient, nothing synchronises, graph-capturable.  fp32; q* are (B, A) row-major, reward / done / weights / log_pi /
+ * next_log_pi hold B values; 1 <= B, 1 <= A <= 16, B * A <= 2^20.  The temperature alpha is expf(log_alpha[0]) read on the DEVICE
+ * when the kernel runs (log_alpha != NULL: a replayed graph follows a learned temperature), otherwise the float `alpha`.
+ * Each kernel is one workgroup that sums in double in a fixed order: no atomics, the same bits on every call.
+ *
+ * dgvit_sac_critic_loss:
+ *     target[b,a] = reward[b] + (1 - done[b]) gamma (min(next_q1, next_q2)[b,a] - alpha next_log_pi[b])        done == NULL: 0
+ *     loss[0]     = (1/BA) sum w[b] (q1 - target)^2 + (1/BA) sum w[b] (q2 - target)^2                          weights == NULL: 1
+ *     td[b]       = (1/A) sum_a |q1[b,a] - target[b,a]|            (NULL: not wanted; what a prioritized replay takes back)
+ *     grads       = [dq1 | dq2], 2 B A floats, d loss / d q = 2 w (q - target) / (BA) for a unit upstream gradient (NULL: not wanted)
+ *   target is a constant (the reference's no_grad): nothing is produced for next_*, reward, done, weights or log_alpha.
+ * dgvit_sac_actor_loss:
+ *     losses[0] = (1/BA) sum (alpha log_pi[b] - min(q1_pi, q2_pi)[b,a])                                        the policy loss
+ *     grads     = [d log_pi (B) | dq1_pi (BA) | dq2_pi (BA)] (NULL: not wanted): d log_pi[b] = alpha / B; dq1_pi = -1/(BA) where
+ *                 q1_pi < q2_pi, -0.5/(BA) at a tie (torch.minimum's rule), 0 otherwise; dq2_pi the mirror image
+ *   and with with_temperature == 1 (needs log_alpha):
+ *     losses[1]     = -log_alpha[0] (1/B) sum_b (log_pi[b] + target_entropy)                                   the temperature loss
+ *     dlog_alpha[0] = -(1/B) sum_b (log_pi[b] + target_entropy)      (NULL: not wanted)
+ *   `losses` holds 2 floats; losses[1] and dlog_alpha are left alone when with_temperature == 0.  The temperature loss treats log_pi
+ *   as a constant and the policy loss treats log_alpha as one, so the two gradients above are all there are.
+ * dgvit_sac_scale_grads: dst[i] = *scale_dev * src[i], 1 <= n <= 3 * 2^20 -- the backward of either loss: a saved gradient buffer
+ *   times the 0-d upstream gradient, out of place (the saved buffer serves a second backward) and for any n and 4-byte alignment.
+ * -------------------------------------------------------------------------------------------- */
+int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
+                          const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
+                          float gamma, float* target, float* td, float* loss, float* grads, int B, int A, void* stream);
+int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha,
+                         int with_temperature, float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A,
+                         void* stream);
+int dgvit_sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * bf16 configuration (BASELINE.json config 5: 224x224 depth frames, 12-layer ViT-Base variant with goal token, bf16).
  * Same GoT.forward (GoalFormer.py:156-171) with bf16 STORAGE for every GEMM operand (LayerNorm outputs, qkv, attention
  * output, MLP hidden, the four weight matrices of each block and the patch weight) and fp32 everywhere else (residual
