@@ -101,6 +101,9 @@ SIGNATURES = {
     "dgvit_cnn_backward_v2": (_I, [_P, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_gather_rows": (_I, [_P, _P, _P, _LL, _LL, _LL, _P]),
     "dgvit_gather_shift_frames": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _I, _I, _ULL, _P, _P]),
+    "dgvit_quantize_rows_u8": (_I, [_P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_gather_rows_u8": (_I, [_P, _P, _P, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_gather_shift_frames_u8": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _LL, _I, _I, _ULL, _P, _P]),
     "dgvit_per_tree_floats": (_LL, [_LL]),
     "dgvit_per_init": (_I, [_P, _LL, _P]),
     "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),

@@ -266,6 +266,21 @@ extern "C" int dgvit_gather_shift_frames(const float* src, const long long* idx,
                                          const unsigned long long* seed_dev, void* stream) {
   return gather_shift_frames(src, idx, out, shifts_out, nsel, H, W, row_floats, nrows, pad, stream_id, seed, seed_dev, (hipStream_t)stream);
 }
+// the ring with uint8 frame storage (replay_u8.hip)
+extern "C" int dgvit_quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols,
+                                      long long row_bytes, long long nrows, long long start, void* stream) {
+  return quantize_rows_u8(src, src_ld, ring, n, cols, row_bytes, nrows, start, (hipStream_t)stream);
+}
+extern "C" int dgvit_gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, long long nsel, long long cols,
+                                    long long row_bytes, long long row_floats, long long nrows, void* stream) {
+  return gather_rows_u8(ring, idx, out, nsel, cols, row_bytes, row_floats, nrows, (hipStream_t)stream);
+}
+extern "C" int dgvit_gather_shift_frames_u8(const unsigned char* ring, const long long* idx, float* out, int* shifts_out, long long nsel, int H,
+                                            int W, long long row_bytes, long long row_floats, long long nrows, int pad, int stream_id,
+                                            unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  return gather_shift_frames_u8(ring, idx, out, shifts_out, nsel, H, W, row_bytes, row_floats, nrows, pad, stream_id, seed, seed_dev,
+                                (hipStream_t)stream);
+}
 // prioritized replay (replay.hip)
 extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }
 extern "C" int dgvit_per_init(float* tree, long long capacity, void* stream) { return per_init(tree, capacity, (hipStream_t)stream); }

@@ -76,6 +76,14 @@ int gather_rows(const float*, const long long*, float*, long long, long long, lo
 int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
                         long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
                         const unsigned long long* seed_dev, hipStream_t stream);
+// replay_u8.hip: the ring with uint8 frame storage (formulas: include/dgvit_hip.h)
+int quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols, long long row_bytes,
+                     long long nrows, long long start, hipStream_t stream);
+int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, long long nsel, long long cols, long long row_bytes,
+                   long long row_floats, long long nrows, hipStream_t stream);
+int gather_shift_frames_u8(const unsigned char* ring, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                           long long row_bytes, long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                           const unsigned long long* seed_dev, hipStream_t stream);
 // replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
 long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
 int per_init(float* tree, long long capacity, hipStream_t stream);

@@ -5,7 +5,9 @@ The reference keeps transitions in a host-side ``cpprb.PrioritizedReplayBuffer``
 tensors and copies it to the device synchronously from pageable memory (DRL.py:375-386): 2 x (B,128,160) fp32 =
 84 MB at B=512.  An MI355X has 288 GB of HBM: 100k transitions of two 128x160 fp32 frames are 16 GB, so the ring
 lives on the device, ``store_transition`` becomes one small H2D copy per environment step, and ``sample`` is an
-index draw plus one HBM-bound gather kernel per field -- the encoder never waits for PCIe.
+index draw plus one HBM-bound gather kernel per field -- the encoder never waits for PCIe.  The reference's frames are k / 255 with k in
+0..255 (env_lab.py:420-434, 348-349), so ``frame_dtype=torch.uint8`` stores them as bytes, a quarter of the ring, and the gather restores
+the fp32 frame.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -23,9 +25,38 @@ def _al4(n: int) -> int:
     return (n + 3) & ~3
 
 
+def _al16(n: int) -> int:
+    return (n + 15) & ~15
+
+
+FRAME_FIELDS = ("obs", "next_obs")
+
+
+def _frame_dtype(dtype):
+    """``frame_dtype`` after its check: host-only, runs before anything touches a device"""
+    if dtype is not torch.float32 and dtype is not torch.uint8:
+        raise ValueError(f"frame_dtype must be torch.float32 or torch.uint8, got {dtype!r}")
+    return dtype
+
+
+def _ptr(t):
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
 class DeviceReplayBuffer:
+    """The replay ring in HBM.  ``frame_dtype=torch.uint8`` (keyword-only; default ``torch.float32``) stores ``obs`` and ``next_obs`` as
+    one byte per pixel, a quarter of the fp32 ring: ``store["obs"]`` and ``store["next_obs"]`` are then
+    ``(size, al16(H*W))`` uint8 matrices, the other fields unchanged.  The stored value is code / 255: a frame given as floats is
+    quantised on the device, code = rint(clamp(255 x, 0, 255)) with halves to even, so inputs outside [0, 1] clamp (NaN stores 0); this
+    is exact for the reference's k / 255 frames and round-to-nearest otherwise (error at most 1/510 + 2^-23).  ``sample`` returns fp32
+    frames, bit-equal to numpy's and CPU torch's ``codes / 255`` in fp32.  With a uint8 ring ``add`` / ``add_batch`` take each frame
+    field, independently, as host floats (they travel in the one staged matrix and are quantised from it), as host uint8 (numpy or CPU
+    tensor: the codes themselves, staged as bytes) or as a device tensor, fp32 or uint8, which never visits the host.  Buffers have no
+    ``state_dict``."""
+
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2,
-                 device="cuda", seed: Optional[int] = None):
+                 device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32):
+        self.frame_dtype = _frame_dtype(frame_dtype)
         self.size, self.device = int(size), torch.device(device)
         if self.device.type != "cuda":
             raise _lib.DgvitError("DeviceReplayBuffer lives in HBM; pass a ROCm device")
@@ -35,7 +66,12 @@ class DeviceReplayBuffer:
                        "act": (act_dim,), "rew": (1,), "done": (1,)}
         # every field is a (size, row) fp32 matrix whose row length is padded to a multiple of 4 floats (float4 gather)
         self.rows = {k: _al4(n) for k, n in self.fields.items()}
-        self.store = {k: torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
+        if self.frame_dtype is torch.uint8:      # a frame's ring row is al16(H*W) bytes; the rows sample() returns stay al4(H*W) floats
+            self.row_bytes = _al16(self.fields["obs"])
+            self.store = {k: torch.zeros(self.size, self.row_bytes, dtype=torch.uint8, device=self.device) if k in FRAME_FIELDS
+                          else torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
+        else:
+            self.store = {k: torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
         self.next_index, self.stored = 0, 0
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
@@ -82,14 +118,112 @@ class DeviceReplayBuffer:
         self.next_index = (i + n) % self.size
         self.stored = min(self.stored + n, self.size)
 
+    def _on_store(self, start: int, n: int) -> None:
+        """hook: ring slots start .. start + n - 1 (mod size) have just been written"""
+
+    def _frame_source(self, k, v, n):
+        """How frame field k of n transitions travels into a uint8 ring: ("device", (n, H*W) fp32 or uint8 tensor on self.device),
+        ("bytes", (n, H*W) uint8 array: the codes themselves) or ("floats", (n, H*W) fp32 array)."""
+        if torch.is_tensor(v) and v.device.type != "cpu":
+            v = v.detach().to(self.device)
+            v = (v if v.dtype in (torch.uint8, torch.float32) else v.float()).reshape(n, -1).contiguous()
+            kind = "device"
+        else:
+            if torch.is_tensor(v):
+                v = v.detach()
+                v = (v if v.dtype == torch.uint8 else v.float()).numpy()
+            v = np.asarray(v)
+            kind = "bytes" if v.dtype == np.uint8 else "floats"
+            v = (v if kind == "bytes" else np.asarray(v, dtype=np.float32)).reshape(n, -1)
+        if v.shape[1] != self.fields[k]:
+            raise ValueError(f"{k}: expected {self.fields[k]} values per transition, got {v.shape[1]}")
+        return kind, v
+
+    def _ring_copy(self, k, rows, i, first) -> None:
+        """device rows (n, H*W) uint8 -> ring slots i .. of field k (ring wrap = two slices); the padding bytes stay zero"""
+        cnt, n = self.fields[k], rows.shape[0]
+        self.store[k][i:i + first, :cnt].copy_(rows[:first])
+        if first < n:
+            self.store[k][:n - first, :cnt].copy_(rows[first:])
+
+    def _store_u8(self, kw, n) -> None:
+        """add / add_batch of a uint8 ring.  The non-frame fields and the frame fields given as host floats travel side by side in ONE
+        staged fp32 matrix, as in ``_store_rows``; such a frame field is quantised straight from the staged matrix by one
+        dgvit_quantize_rows_u8 launch (the ring wrap inside it).  Frame fields given as host uint8 are staged as bytes (one byte matrix,
+        one copy) and copied into the ring; device tensors are quantised (fp32) or copied (uint8) where they are."""
+        for k in self.fields:
+            if k not in kw:
+                raise KeyError(f"missing field {k}")
+        frames = {k: self._frame_source(k, kw[k], n) for k in FRAME_FIELDS}
+        staged = [k for k in self.fields if k not in FRAME_FIELDS or frames[k][0] == "floats"]
+        off, row = {}, 0
+        for k in staged:
+            off[k] = row
+            row += self.rows[k]
+        host = np.zeros((n, row), dtype=np.float32)
+        for k in staged:
+            cnt = self.fields[k]
+            if k in FRAME_FIELDS:
+                v = frames[k][1]
+            else:
+                v = kw[k].detach().cpu().numpy() if torch.is_tensor(kw[k]) else np.asarray(kw[k], dtype=np.float32)
+                v = np.asarray(v, dtype=np.float32).reshape(n, -1)
+                if v.shape[1] != cnt:
+                    raise ValueError(f"{k}: expected {cnt} values per transition, got {v.shape[1]}")
+            host[:, off[k]:off[k] + cnt] = v
+        drop = max(n - self.size, 0)             # n > size: the last `size` transitions are the ones that stay
+        n -= drop
+        stage = torch.from_numpy(host[drop:]).pin_memory()
+        dev = stage.to(self.device, non_blocking=True)
+        keep = [stage, dev]
+        as_bytes = [k for k in FRAME_FIELDS if frames[k][0] == "bytes"]
+        if as_bytes:
+            cnt = self.fields["obs"]
+            bstage = torch.empty(n, len(as_bytes) * cnt, dtype=torch.uint8).pin_memory()
+            for j, k in enumerate(as_bytes):
+                bstage.numpy()[:, j * cnt:(j + 1) * cnt] = frames[k][1][drop:]
+            bdev = bstage.to(self.device, non_blocking=True)
+            keep += [bstage, bdev]
+        i = self.next_index
+        first = min(n, self.size - i)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for k in self.fields:
+                cnt = self.fields[k]
+                if k not in FRAME_FIELDS:
+                    o = off[k]
+                    self.store[k][i:i + first, :cnt].copy_(dev[:first, o:o + cnt])
+                    if first < n:
+                        self.store[k][:n - first, :cnt].copy_(dev[first:, o:o + cnt])
+                    continue
+                kind, v = frames[k]
+                if kind == "bytes":
+                    j = as_bytes.index(k)
+                    self._ring_copy(k, bdev[:, j * cnt:(j + 1) * cnt], i, first)
+                elif kind == "device" and v.dtype == torch.uint8:
+                    self._ring_copy(k, v[drop:], i, first)
+                else:
+                    src, ld = (dev[:, off[k]:], row) if kind == "floats" else (v[drop:], cnt)
+                    rc = lib.dgvit_quantize_rows_u8(_ptr(src), ld, _ptr(self.store[k]), n, cnt, self.row_bytes, self.size, i, st)
+                    _lib.check(rc, "dgvit_quantize_rows_u8")
+        self._last_stage = keep                  # keep the pinned buffers alive until the async copies have certainly been issued
+        self.next_index = (i + n) % self.size
+        self.stored = min(self.stored + n, self.size)
+        self._on_store(i, n)
+
     def add(self, **kw) -> None:
         """One transition (numpy arrays / scalars / tensors), same keywords as replay_buffer.add in DRL.py:439-448:
         one staged host->device copy for the whole transition."""
+        if self.frame_dtype is torch.uint8:
+            return self._store_u8(kw, 1)
         self._store_rows(self._host_rows(kw, 1))
 
     def add_batch(self, **kw) -> None:
         """Many transitions at once (first axis = transitions), e.g. the expert demonstrations of DRL.py:469-478: assembled on
         the host with numpy slicing, one host->device copy."""
+        if self.frame_dtype is torch.uint8:
+            return self._store_u8(kw, len(kw["obs"]))
         self._store_rows(self._host_rows(kw, len(kw["obs"])))
 
     def sample_indices(self, batch_size: int) -> torch.Tensor:
@@ -106,9 +240,11 @@ class DeviceReplayBuffer:
         padded by p pixels with its border and cropped back at its own random offset, the two fields drawing independently (streams
         0 and 1 of one seed per call; the seed comes from torch's CPU generator, or from the device inside a stream capture, and is
         kept in ``self.shift_seed``).  ``return_shifts=True`` adds ``obs_shift`` and ``next_obs_shift``, (B, 2) int32 (dy, dx).
-        With ``random_shift=0`` nothing is drawn and the launches are the plain gathers."""
+        With ``random_shift=0`` nothing is drawn and the launches are the plain gathers.  A uint8 ring (``frame_dtype``) takes the
+        ``_u8`` forms of the two frame launches and returns the same fp32 frames, code / 255."""
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
         lib = _lib.load()
+        u8 = self.frame_dtype is torch.uint8
         idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
         B = idx.numel()
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -119,11 +255,21 @@ class DeviceReplayBuffer:
             for k, n in self.fields.items():
                 r = self.rows[k]
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
-                if pad and k in ("obs", "next_obs"):
+                if pad and k in FRAME_FIELDS:
                     shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
-                    _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
+                    if u8:
+                        seed_dev = self.shift_seed if isinstance(self.shift_seed, torch.Tensor) else None
+                        rc = lib.dgvit_gather_shift_frames_u8(_ptr(self.store[k]), _ptr(idx), _ptr(buf), _ptr(shifts), B, *self.shapes[k],
+                                                              self.row_bytes, r, self.size, pad, int(k == "next_obs"),
+                                                              0 if seed_dev is not None else int(self.shift_seed), _ptr(seed_dev), st)
+                        _lib.check(rc, "dgvit_gather_shift_frames_u8")
+                    else:
+                        _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
                     if return_shifts:
                         out[k + "_shift"] = shifts
+                elif u8 and k in FRAME_FIELDS:
+                    rc = lib.dgvit_gather_rows_u8(_ptr(self.store[k]), _ptr(idx), _ptr(buf), B, n, self.row_bytes, r, self.size, st)
+                    _lib.check(rc, "dgvit_gather_rows_u8")
                 else:
                     rc = lib.dgvit_gather_rows(ctypes.c_void_p(self.store[k].data_ptr()), ctypes.c_void_p(idx.data_ptr()),
                                                ctypes.c_void_p(buf.data_ptr()), B, r, self.size, st)
@@ -175,13 +321,14 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",
-                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4):
+                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32):
+        _frame_dtype(frame_dtype)
         self.alpha = _unit("alpha", alpha)
         if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0.0 <= float(eps) < float("inf"):
             raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
         self.eps = float(eps)
         self._levels, floats = per_tree_layout(int(size))
-        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed)
+        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed, frame_dtype=frame_dtype)
         lib = _lib.load()
         if lib.dgvit_per_tree_floats(self.size) != floats:
             raise _lib.DgvitError("dgvit_per_tree_floats disagrees with replay.per_tree_layout; rebuild the library")
@@ -200,6 +347,10 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         """the base's copy, then the ring range just written takes the max priority (an overwritten slot forgets its old one)"""
         n, i = min(host.shape[0], self.size), self.next_index
         super()._store_rows(host)
+        self._on_store(i, n)
+
+    def _on_store(self, i: int, n: int) -> None:
+        """the max priority for ring slots i .. i + n - 1 (mod size): every add path of both ring kinds ends here"""
         first = min(n, self.size - i)
         lib = _lib.load()
         with torch.cuda.device(self.device):

@@ -383,6 +383,37 @@ int dgvit_gather_shift_frames(const float* src, const long long* idx /* may be N
                               unsigned long long seed, const unsigned long long* seed_dev, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The replay ring with uint8 frame storage (dgvit_amd.replay.DeviceReplayBuffer(frame_dtype=torch.uint8)).  The reference's
+ * frames are k / 255 with k in 0..255 (env_lab.py:420-434), so a ring row is row_bytes = al16(H*W) BYTES, a quarter of the fp32 ring, and
+ * the fp32 frame is restored inside the gather.  Stored value = code / 255; inputs outside [0, 1] clamp; exact for k / 255 frames and
+ * round-to-nearest (half to even) otherwise.  The three calls share these rules: row_bytes % 16 == 0 and row_bytes >= cols; an output row
+ * is row_floats floats, a multiple of 4 and >= cols; ring and out 16-byte aligned; columns at or beyond cols of every row WRITTEN (ring
+ * rows by the quantiser, output rows by the gathers) are zeros; all index arithmetic is 64-bit.
+ *
+ * dgvit_quantize_rows_u8:  ring[(start + i) % nrows][c] = q(src[i * src_ld + c])   for i < n, c < cols
+ *     q(x) = (uint8) rintf(fminf(fmaxf(x * 255.0f, 0), 255))      half to even; NaN, -0 and -inf store 0, +inf stores 255
+ *   The ring wrap happens inside the one launch.  src_ld >= cols is in floats (src 4-byte aligned), so src may be a column block of a
+ *   staged matrix or a frame tensor.  0 <= start < nrows, 1 <= n <= nrows, cols <= 2^25.
+ * dgvit_gather_rows_u8:    out[i][c] = (float)ring[clamp(idx[i], 0, nrows-1)][c] / 255.0f      for i < nsel, c < cols
+ *   The correctly rounded quotient, bit-equal to numpy's and CPU torch's uint8 -> float32 / 255.  A multiplication by 1.0f / 255.0f is
+ *   not (it differs in 126 of the 256 codes); the kernels form the quotient as that product plus one Newton correction in two fused
+ *   multiply-adds, equal to the division on every code.
+ * dgvit_gather_shift_frames_u8:  dgvit_gather_shift_frames over a byte ring, cols = H * W:
+ *     out[i][y][x] = (float)ring[clamp(idx[i], 0, nrows-1)][clamp(y + dy_i, 0, H-1) * W + clamp(x + dx_i, 0, W-1)] / 255.0f
+ *   with the same Philox draw and tag, stream_id, seed / seed_dev, shifts_out, idx == NULL identity and clamping, so one seed gives the same
+ *   shift table as the fp32 call.  pad == 0 gives the bytes of dgvit_gather_rows_u8.  0 <= pad < min(H, W); 1 <= nsel < 2^24;
+ *   row_floats <= 2^25.
+ * -------------------------------------------------------------------------------------------- */
+int dgvit_quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols, long long row_bytes,
+                           long long nrows, long long start, void* stream);
+int dgvit_gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, long long nsel, long long cols, long long row_bytes,
+                         long long row_floats, long long nrows, void* stream);
+int dgvit_gather_shift_frames_u8(const unsigned char* ring, const long long* idx /* may be NULL */, float* out,
+                                 int* shifts_out /* may be NULL */, long long nsel, int H, int W, long long row_bytes, long long row_floats,
+                                 long long nrows, int pad, int stream_id, unsigned long long seed, const unsigned long long* seed_dev,
+                                 void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
  * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
  *
