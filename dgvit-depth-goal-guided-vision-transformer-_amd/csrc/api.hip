@@ -266,7 +266,7 @@ extern "C" int dgvit_gather_shift_frames(const float* src, const long long* idx,
                                          const unsigned long long* seed_dev, void* stream) {
   return gather_shift_frames(src, idx, out, shifts_out, nsel, H, W, row_floats, nrows, pad, stream_id, seed, seed_dev, (hipStream_t)stream);
 }
-// the ring with uint8 frame storage (replay_u8.hip)
+// the ring with uint8 frame storage (replay_ring.hip)
 extern "C" int dgvit_quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols,
                                       long long row_bytes, long long nrows, long long start, void* stream) {
   return quantize_rows_u8(src, src_ld, ring, n, cols, row_bytes, nrows, start, (hipStream_t)stream);

@@ -204,7 +204,7 @@ __device__ __forceinline__ uint4 drop_bits(long long i4, unsigned long long seed
 // the factor one random word gives: 1/keep (kept) or 0 (dropped)
 __device__ __forceinline__ float drop_factor(uint32_t r, float keep, float inv) { return (r * 2.3283064365386963e-10f < keep) ? inv : 0.f; }
 
-// ---- random-shift augmentation of sampled frames (embed.hip gather_shift_frames_kernel): a third family of the same counter space.
+// ---- random-shift augmentation of sampled frames (replay_ring.hip gather_shift_frames_kernel): a third family of the same counter space.
 //   ctr.z                        | counter (ctr.x, ctr.y) | words used
 //   0                            | float4 group           | emb-dropout, all four
 //   0x44000000 | (l << 2) | s    | float4 group           | transformer dropout sites, all four (table above)

@@ -5,8 +5,6 @@
 //                   -- the same call with the same seed re-creates the mask in backward, nothing is stored
 //   drop_rows     : transformer-internal dropout of a row block (+ residual), sites 1-3 of the mask table in common.h
 //   relu_bwd      : dpre = dy * (y > 0)                    (head MLPs)
-//   gather_rows   : replay sampling, out[i] = src[idx[i]]
-//   gather_shift_frames : the same gather with the DrQ random shift (replicate-pad by `pad`, crop at a per-sample offset) folded in
 #include "common.h"
 #include "kernels.h"
 
@@ -82,91 +80,7 @@ __global__ void __launch_bounds__(256) add_rows_kernel(const float4* __restrict_
   out[r * ldo4 + c] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
 }
 
-// out[i][:] = src[idx[i]][:] for rows of `row4` float4 (device-resident replay sampling)
-__global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restrict__ src, const long long* __restrict__ idx,
-                                                          float* __restrict__ out, long long total4, int row4, long long nrows) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
-  const long long r = i / row4;
-  const int c = (int)(i % row4);
-  long long s = idx[r];
-  s = s < 0 ? 0 : (s >= nrows ? nrows - 1 : s);   // clamp instead of faulting on a bad index
-  reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(src)[s * row4 + c];
-}
-
-// out[i][y][x] = src[idx[i]][clamp(y + dy_i)][clamp(x + dx_i)]: the gather above with a per-sample integer shift in [-pad, pad]^2
-// (F.pad(mode="replicate", pad) then a crop at (pad + dy, pad + dx)); columns H*W .. row_floats of out are written as zeros.
-// blockIdx.x is the sample, so its index, seed and Philox draw are wave-uniform (scalar unit); blockIdx.y * 256 + threadIdx.x is the
-// float4 group of the output row.  A group may straddle image rows (W % 4 != 0): y and x advance per element.
-__global__ void __launch_bounds__(256) gather_shift_frames_kernel(const float* __restrict__ src, const long long* __restrict__ idx,
-                                                                  float* __restrict__ out, int* __restrict__ shifts_out, int row4,
-                                                                  long long nrows, int H, int W, int pad, uint32_t tag,
-                                                                  unsigned long long seed,
-                                                                  const unsigned long long* __restrict__ seed_dev) {
-  const int c = (int)blockIdx.y * 256 + (int)threadIdx.x;
-  if (c >= row4) return;
-  const long long r = blockIdx.x;
-  long long s = idx ? idx[r] : r;
-  s = s < 0 ? 0 : (s >= nrows ? nrows - 1 : s);   // as gather_rows_kernel
-  int dy = 0, dx = 0;
-  if (pad > 0) {
-    if (seed_dev) seed = *seed_dev;   // graph-capturable form, as dropout_kernel
-    const uint4 rb = drop_bits(r, seed, tag);
-    const uint32_t span = 2u * (uint32_t)pad + 1u;
-    dy = (int)__umulhi(rb.x, span) - pad;
-    dx = (int)__umulhi(rb.y, span) - pad;
-  }
-  if (shifts_out && c == 0) {
-    shifts_out[2 * r] = dy;
-    shifts_out[2 * r + 1] = dx;
-  }
-  const float* __restrict__ frame = src + s * (4ll * row4);
-  const unsigned p0 = 4u * (unsigned)c;
-  int y = (int)(p0 / (unsigned)W), x = (int)(p0 - (unsigned)y * (unsigned)W);
-  float v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int sy = min(max(y + dy, 0), H - 1), sx = min(max(x + dx, 0), W - 1);
-    const float t = frame[(long long)sy * W + sx];   // always in bounds (clamped): loaded unconditionally, no branch per element
-    v[e] = y < H ? t : 0.f;                          // y >= H: the padding columns behind the frame
-    if (++x == W) { x = 0; ++y; }
-  }
-  reinterpret_cast<float4*>(out)[r * row4 + c] = make_float4(v[0], v[1], v[2], v[3]);
-}
-
 }  // namespace
-
-int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
-                        long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
-                        const unsigned long long* seed_dev, hipStream_t stream) {
-  DGVIT_CHECK_ARG(src && out, "gather_shift_frames: src and out must not be null");
-  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 24) && nrows > 0, "gather_shift_frames: nsel=%lld must be in [1, 2^24) and nrows=%lld positive", nsel,
-                  nrows);   // one workgroup column per sample: 256 * nsel threads along x
-  DGVIT_CHECK_ARG(H > 0 && W > 0, "gather_shift_frames: frame H=%d W=%d must be positive", H, W);
-  DGVIT_CHECK_ARG(row_floats % 4 == 0 && row_floats >= (long long)H * W && row_floats <= (1ll << 25),
-                  "gather_shift_frames: row_floats=%lld must be a multiple of 4, at least H*W=%lld and at most 2^25", row_floats,
-                  (long long)H * W);
-  DGVIT_CHECK_ARG(pad >= 0 && pad < H && pad < W, "gather_shift_frames: pad=%d must be in [0, min(H, W)) = [0, %d)", pad, H < W ? H : W);
-  DGVIT_CHECK_ARG(stream_id >= 0 && stream_id < DGVIT_SHIFT_STREAMS, "gather_shift_frames: stream_id=%d must be in [0, %d)", stream_id,
-                  DGVIT_SHIFT_STREAMS);
-  DGVIT_CHECK_ARG(al16(src) && al16(out), "gather_shift_frames: src and out must be 16-byte aligned");
-  const int row4 = (int)(row_floats / 4);
-  hipLaunchKernelGGL(gather_shift_frames_kernel, dim3((unsigned)nsel, (unsigned)((row4 + 255) / 256)), dim3(256), 0, stream, src, idx, out,
-                     shifts_out, row4, nrows, H, W, pad, shift_tag(stream_id), seed, seed_dev);
-  DGVIT_CHECK_LAUNCH("gather_shift_frames");
-  return DGVIT_OK;
-}
-
-int gather_rows(const float* src, const long long* idx, float* out, long long nsel, long long row_floats, long long nrows,
-                hipStream_t stream) {
-  DGVIT_CHECK_ARG(src && idx && out && nsel > 0 && nrows > 0, "gather_rows: bad arguments");
-  DGVIT_CHECK_ARG(row_floats > 0 && row_floats % 4 == 0 && row_floats / 4 < (1ll << 31), "gather_rows: row length must be a multiple of 4 floats");
-  const long long total4 = nsel * (row_floats / 4);
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, src, idx, out, total4,
-                     (int)(row_floats / 4), nrows);
-  DGVIT_CHECK_LAUNCH("gather_rows");
-  return DGVIT_OK;
-}
 
 int add_rows(const float* a, long long lda, const float* b, long long ldb, float* out, long long ldo, long long rows, int cols, hipStream_t stream) {
   DGVIT_CHECK_ARG(a && b && out && rows > 0 && cols > 0, "add_rows: bad arguments");

@@ -1,5 +1,5 @@
 // Internal prototypes of the launch functions implemented in the kernel translation units
-// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, replay.hip, gemm.hip, gemm_reduce.hip); the schedules in encoder.hip, encoder_bf16.hip
+// (norm.hip, attention.hip, embed.hip, conv.hip, optim.hip, replay_ring.hip, replay.hip, gemm.hip, gemm_reduce.hip); the schedules in encoder.hip, encoder_bf16.hip
 // and cnn_api.hip call these.
 #pragma once
 #include "common.h"
@@ -71,12 +71,12 @@ int col2im_frame(const float*, float*, int, int, int, int, int, int, hipStream_t
 int weight_pack(const float*, float*, int, int, int, int, hipStream_t);
 int avgpool(const float*, float*, int, int, int, hipStream_t);
 int avgpool_bwd_relu(const float*, const float*, float*, int, int, int, hipStream_t);
+// replay_ring.hip: the replay ring's storage kernels, fp32 and uint8 frames (formulas: include/dgvit_hip.h)
 int gather_rows(const float*, const long long*, float*, long long, long long, long long, hipStream_t);
 // gather_rows with the random shift of a (H, W) frame folded in (idx / shifts_out may be null; draw: the shift table in common.h)
 int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
                         long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
                         const unsigned long long* seed_dev, hipStream_t stream);
-// replay_u8.hip: the ring with uint8 frame storage (formulas: include/dgvit_hip.h)
 int quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols, long long row_bytes,
                      long long nrows, long long start, hipStream_t stream);
 int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, long long nsel, long long cols, long long row_bytes,

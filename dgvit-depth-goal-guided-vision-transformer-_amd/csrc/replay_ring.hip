@@ -1,0 +1,247 @@
+// The replay ring's storage kernels (replay.DeviceReplayBuffer; the priority tree over the ring's slots is replay.hip).  A field is a
+// (nrows, row) matrix; a frame field is fp32 (row = al4(H*W) floats) or, DESIGN 3.30, uint8 (row = al16(H*W) BYTES: the reference's frames
+// are k/255 with k in 0..255, env_lab.py:420-434, and the fp32 frame is restored inside the gather).
+//   gather_rows             : out[i] = src[idx[i]]                                          (replay sampling)
+//   gather_rows_u8          : out[i][c] = (float)ring[idx[i]][c] / 255.0f
+//   quantize_rows_u8        : ring[(start + i) % nrows][c] = q(src[i][c]),  q(x) = (uint8) rintf(fminf(fmaxf(x * 255, 0), 255))
+//   gather_shift_frames     : the gather with the DrQ random shift (replicate-pad by `pad`, crop at a per-sample offset) folded in
+//   gather_shift_frames_u8  : the same kernel template over a byte ring: one draw, one set of clamps
+// The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
+// in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
+// the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
+// other side holds there.
+#include <math.h>
+
+#include <type_traits>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+// a sampled index as a ring row: clamp instead of faulting on a bad index
+__device__ __forceinline__ long long ring_row(long long s, long long nrows) { return s < 0 ? 0 : (s >= nrows ? nrows - 1 : s); }
+
+// fl(k / 255) for k in 0..255 without the division's v_rcp_f32 and ten-instruction expansion, four times per thread: q = fl(k * fl(1/255))
+// is within an ulp, r = k - 255 q is exact in one fma, and q + r * fl(1/255) rounds to the quotient -- the last step of the division's
+// own expansion.  Equal to (float)k / 255.0f on all 256 codes: tests/test_replay_u8_host.py restates the three operations in exact
+// rational arithmetic, tests/test_gpu_replay_u8.py compares every code on the device.
+__device__ __forceinline__ float dequant_u8(uint32_t k) {
+  constexpr float RINV = 0x1.010102p-8f;   // fl(1 / 255) = 0x3b808081
+  const float x = (float)k, q = x * RINV;
+  return fmaf(fmaf(-q, 255.0f, x), RINV, q);
+}
+
+// rintf rounds half to even; fmaxf(NaN, 0) = 0, so NaN stores 0; -0 and -inf store 0, +inf stores 255
+__device__ __forceinline__ uint32_t quant_u8(float x) { return (uint32_t)rintf(fminf(fmaxf(x * 255.0f, 0.0f), 255.0f)); }
+
+// out[i][:] = src[idx[i]][:] for rows of `row4` float4
+__global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restrict__ src, const long long* __restrict__ idx,
+                                                          float* __restrict__ out, long long total4, int row4, long long nrows) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long long r = i / row4;
+  const int c = (int)(i % row4);
+  const long long s = ring_row(idx[r], nrows);
+  reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(src)[s * row4 + c];
+}
+
+// thread = one float4 of an output row; the ring dword behind it exists whenever 4c < cols (row_bytes >= al4(cols))
+__global__ void __launch_bounds__(256) gather_rows_u8_kernel(const unsigned char* __restrict__ ring, const long long* __restrict__ idx,
+                                                             float* __restrict__ out, long long total4, int out4, int cols,
+                                                             long long row_bytes, long long nrows) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long long r = i / out4;
+  const int c = (int)(i - r * out4), p0 = 4 * c;
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (p0 < cols) {
+    const long long s = ring_row(idx[r], nrows);
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(ring + s * row_bytes + p0);
+    o.x = dequant_u8(w & 255u);
+    if (p0 + 1 < cols) o.y = dequant_u8((w >> 8) & 255u);
+    if (p0 + 2 < cols) o.z = dequant_u8((w >> 16) & 255u);
+    if (p0 + 3 < cols) o.w = dequant_u8(w >> 24);
+  }
+  reinterpret_cast<float4*>(out)[i] = o;
+}
+
+// thread = one dword of a ring row.  VEC: src rows are 16-byte aligned (src_ld % 4 == 0 and an aligned base), a whole group is one float4
+template <bool VEC>
+__global__ void __launch_bounds__(256) quantize_rows_u8_kernel(const float* __restrict__ src, long long src_ld, uint32_t* __restrict__ ring,
+                                                               long long total4, int row4, int cols, long long nrows, long long start) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long long r = i / row4;
+  const int c = (int)(i - r * row4), p0 = 4 * c;
+  long long d = start + r;      // start < nrows and r < n <= nrows: one subtraction wraps the ring
+  if (d >= nrows) d -= nrows;
+  const float* __restrict__ s = src + r * src_ld + p0;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (VEC && p0 + 4 <= cols) {
+    const float4 t = *reinterpret_cast<const float4*>(s);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (p0 + e < cols) v[e] = s[e];
+  }
+  ring[d * row4 + c] = quant_u8(v[0]) | (quant_u8(v[1]) << 8) | (quant_u8(v[2]) << 16) | (quant_u8(v[3]) << 24);   // q(0) = 0: the padding
+}
+
+// The row stride of the shifted gather's source, in elements: a byte ring's is an argument; the fp32 ring's is the output's, 4 * row4, and
+// an argument of its own would only grow that kernel's kernarg segment.
+struct row4_stride {};
+template <typename T>
+using src_stride = std::conditional_t<std::is_same_v<T, float>, row4_stride, long long>;
+
+// out[i][y][x] = fp32(src[idx[i]][clamp(y + dy_i)][clamp(x + dx_i)]): the gather with a per-sample integer shift in [-pad, pad]^2
+// (F.pad(mode="replicate", pad) then a crop at (pad + dy, pad + dx)); columns H*W .. 4 * row4 of out are written as zeros.  T = float or
+// unsigned char is the ring's element; the draw does not depend on it, so one seed gives both rings one shift table.
+// blockIdx.x is the sample, so its index, seed and Philox draw are wave-uniform (scalar unit); blockIdx.y * 256 + threadIdx.x is the
+// float4 group of the output row.  A group may straddle image rows (W % 4 != 0): y and x advance per element.
+template <typename T>
+__global__ void __launch_bounds__(256) gather_shift_frames_kernel(const T* __restrict__ src, const long long* __restrict__ idx,
+                                                                  float* __restrict__ out, int* __restrict__ shifts_out, int row4,
+                                                                  src_stride<T> ld, long long nrows, int H, int W, int pad, uint32_t tag,
+                                                                  unsigned long long seed,
+                                                                  const unsigned long long* __restrict__ seed_dev) {
+  const int c = (int)blockIdx.y * 256 + (int)threadIdx.x;
+  if (c >= row4) return;
+  const long long r = blockIdx.x;
+  const long long s = ring_row(idx ? idx[r] : r, nrows);
+  int dy = 0, dx = 0;
+  if (pad > 0) {
+    if (seed_dev) seed = *seed_dev;   // graph-capturable form, as dropout_kernel
+    const uint4 rb = drop_bits(r, seed, tag);
+    const uint32_t span = 2u * (uint32_t)pad + 1u;
+    dy = (int)__umulhi(rb.x, span) - pad;
+    dx = (int)__umulhi(rb.y, span) - pad;
+  }
+  if (shifts_out && c == 0) {
+    shifts_out[2 * r] = dy;
+    shifts_out[2 * r + 1] = dx;
+  }
+  const T* __restrict__ frame;
+  if constexpr (std::is_same_v<T, float>) frame = src + s * (4ll * row4);
+  else frame = src + s * ld;
+  const unsigned p0 = 4u * (unsigned)c;
+  int y = (int)(p0 / (unsigned)W), x = (int)(p0 - (unsigned)y * (unsigned)W);
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int sy = min(max(y + dy, 0), H - 1), sx = min(max(x + dx, 0), W - 1);
+    // the source pixel is always inside the frame (clamped; H * W <= 2^25): loaded unconditionally, no branch per element; y >= H are the
+    // padding columns behind the frame.  Each element type keeps its kernel's own line, conversion and index width: through a shared
+    // conversion helper the fp32 instantiation grows by 5 instructions
+    if constexpr (std::is_same_v<T, float>) {
+      const float t = frame[(long long)sy * W + sx];
+      v[e] = y < H ? t : 0.f;
+    } else {
+      const uint32_t t = frame[sy * W + sx];
+      v[e] = y < H ? dequant_u8(t) : 0.f;
+    }
+    if (++x == W) { x = 0; ++y; }
+  }
+  reinterpret_cast<float4*>(out)[r * row4 + c] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
+template <typename T>
+int launch_gather_shift(const char* name, const T* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                        long long ld, long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                        const unsigned long long* seed_dev, hipStream_t stream) {
+  constexpr bool BYTES = !std::is_same_v<T, float>;
+  const char* what = BYTES ? "ring" : "src";
+  DGVIT_CHECK_ARG(src && out, "%s: %s and out must not be null", name, what);
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 24) && nrows > 0, "%s: nsel=%lld must be in [1, 2^24) and nrows=%lld positive", name, nsel,
+                  nrows);   // one workgroup column per sample: 256 * nsel threads along x
+  DGVIT_CHECK_ARG(H > 0 && W > 0, "%s: frame H=%d W=%d must be positive", name, H, W);
+  const long long cols = (long long)H * W;
+  if constexpr (BYTES)
+    DGVIT_CHECK_ARG(ld % 16 == 0 && ld >= cols, "%s: row_bytes=%lld must be a multiple of 16 and at least H*W=%lld", name, ld, cols);
+  DGVIT_CHECK_ARG(row_floats % 4 == 0 && row_floats >= cols && row_floats <= (1ll << 25),
+                  "%s: row_floats=%lld must be a multiple of 4, at least H*W=%lld and at most 2^25", name, row_floats, cols);
+  DGVIT_CHECK_ARG(pad >= 0 && pad < H && pad < W, "%s: pad=%d must be in [0, min(H, W)) = [0, %d)", name, pad, H < W ? H : W);
+  DGVIT_CHECK_ARG(stream_id >= 0 && stream_id < DGVIT_SHIFT_STREAMS, "%s: stream_id=%d must be in [0, %d)", name, stream_id, DGVIT_SHIFT_STREAMS);
+  DGVIT_CHECK_ARG(al16(src) && al16(out), "%s: %s and out must be 16-byte aligned", name, what);
+  const int row4 = (int)(row_floats / 4);
+  src_stride<T> stride{};
+  if constexpr (BYTES) stride = ld;
+  hipLaunchKernelGGL(gather_shift_frames_kernel<T>, dim3((unsigned)nsel, (unsigned)((row4 + 255) / 256)), dim3(256), 0, stream, src, idx, out,
+                     shifts_out, row4, stride, nrows, H, W, pad, shift_tag(stream_id), seed, seed_dev);
+  DGVIT_CHECK_LAUNCH(name);
+  return DGVIT_OK;
+}
+
+inline bool al4p(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+
+}  // namespace
+
+int gather_rows(const float* src, const long long* idx, float* out, long long nsel, long long row_floats, long long nrows,
+                hipStream_t stream) {
+  DGVIT_CHECK_ARG(src && idx && out && nsel > 0 && nrows > 0, "gather_rows: bad arguments");
+  DGVIT_CHECK_ARG(row_floats > 0 && row_floats % 4 == 0 && row_floats / 4 < (1ll << 31), "gather_rows: row length must be a multiple of 4 floats");
+  const long long total4 = nsel * (row_floats / 4);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, src, idx, out, total4,
+                     (int)(row_floats / 4), nrows);
+  DGVIT_CHECK_LAUNCH("gather_rows");
+  return DGVIT_OK;
+}
+
+int gather_shift_frames(const float* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                        long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                        const unsigned long long* seed_dev, hipStream_t stream) {
+  return launch_gather_shift("gather_shift_frames", src, idx, out, shifts_out, nsel, H, W, row_floats, row_floats, nrows, pad, stream_id, seed,
+                             seed_dev, stream);
+}
+
+int gather_shift_frames_u8(const unsigned char* ring, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
+                           long long row_bytes, long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
+                           const unsigned long long* seed_dev, hipStream_t stream) {
+  return launch_gather_shift("gather_shift_frames_u8", ring, idx, out, shifts_out, nsel, H, W, row_bytes, row_floats, nrows, pad, stream_id,
+                             seed, seed_dev, stream);
+}
+
+int quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols, long long row_bytes,
+                     long long nrows, long long start, hipStream_t stream) {
+  DGVIT_CHECK_ARG(src && ring, "quantize_rows_u8: src and ring must not be null");
+  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows, "quantize_rows_u8: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "quantize_rows_u8: cols=%lld must be in [1, 2^25]", cols);
+  DGVIT_CHECK_ARG(row_bytes % 16 == 0 && row_bytes >= cols && row_bytes <= (1ll << 26),
+                  "quantize_rows_u8: row_bytes=%lld must be a multiple of 16, at least cols=%lld and at most 2^26", row_bytes, cols);
+  DGVIT_CHECK_ARG(src_ld >= cols, "quantize_rows_u8: src_ld=%lld must be at least cols=%lld", src_ld, cols);
+  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "quantize_rows_u8: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  DGVIT_CHECK_ARG(al4p(src) && al16(ring), "quantize_rows_u8: src must be 4-byte and ring 16-byte aligned");
+  const int row4 = (int)(row_bytes / 4);
+  const long long total4 = n * row4, blocks = (total4 + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "quantize_rows_u8: n=%lld rows of row_bytes=%lld are more than one launch covers", n, row_bytes);
+  uint32_t* ring4 = reinterpret_cast<uint32_t*>(ring);
+  if (src_ld % 4 == 0 && al16(src))
+    hipLaunchKernelGGL(quantize_rows_u8_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, src, src_ld, ring4, total4, row4, (int)cols,
+                       nrows, start);
+  else
+    hipLaunchKernelGGL(quantize_rows_u8_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, src, src_ld, ring4, total4, row4, (int)cols,
+                       nrows, start);
+  DGVIT_CHECK_LAUNCH("quantize_rows_u8");
+  return DGVIT_OK;
+}
+
+int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, long long nsel, long long cols, long long row_bytes,
+                   long long row_floats, long long nrows, hipStream_t stream) {
+  DGVIT_CHECK_ARG(ring && idx && out, "gather_rows_u8: ring, idx and out must not be null");
+  DGVIT_CHECK_ARG(nsel > 0 && nrows > 0, "gather_rows_u8: nsel=%lld and nrows=%lld must be positive", nsel, nrows);
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "gather_rows_u8: cols=%lld must be in [1, 2^25]", cols);
+  DGVIT_CHECK_ARG(row_bytes % 16 == 0 && row_bytes >= cols, "gather_rows_u8: row_bytes=%lld must be a multiple of 16 and at least cols=%lld",
+                  row_bytes, cols);
+  DGVIT_CHECK_ARG(row_floats % 4 == 0 && row_floats >= cols && row_floats <= (1ll << 26),
+                  "gather_rows_u8: row_floats=%lld must be a multiple of 4, at least cols=%lld and at most 2^26", row_floats, cols);
+  DGVIT_CHECK_ARG(al16(ring) && al16(out), "gather_rows_u8: ring and out must be 16-byte aligned");
+  const int out4 = (int)(row_floats / 4);
+  const long long total4 = nsel * out4, blocks = (total4 + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "gather_rows_u8: nsel=%lld rows of row_floats=%lld are more than one launch covers", nsel, row_floats);
+  hipLaunchKernelGGL(gather_rows_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ring, idx, out, total4, out4, (int)cols, row_bytes,
+                     nrows);
+  DGVIT_CHECK_LAUNCH("gather_rows_u8");
+  return DGVIT_OK;
+}

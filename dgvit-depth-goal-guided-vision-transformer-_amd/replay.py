@@ -11,13 +11,13 @@ the fp32 frame.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
-import ctypes
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from .functional import _ptr, _stream
 from .preprocess import _gather_shift, _shift_pad, _shift_seed
 
 
@@ -37,10 +37,6 @@ def _frame_dtype(dtype):
     if dtype is not torch.float32 and dtype is not torch.uint8:
         raise ValueError(f"frame_dtype must be torch.float32 or torch.uint8, got {dtype!r}")
     return dtype
-
-
-def _ptr(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
 class DeviceReplayBuffer:
@@ -80,132 +76,85 @@ class DeviceReplayBuffer:
     def get_stored_size(self) -> int:
         return self.stored
 
-    def _host_rows(self, kw, n):
-        """(n, row) fp32 host matrix holding the fields of n transitions side by side (offsets in self._off)."""
-        if not hasattr(self, "_off"):
-            self._off, o = {}, 0
-            for k, r in self.rows.items():
-                self._off[k] = o
-                o += r
-            self._row = o
-        host = np.zeros((n, self._row), dtype=np.float32)
-        for k, cnt in self.fields.items():
-            if k not in kw:
-                raise KeyError(f"missing field {k}")
-            v = kw[k].detach().cpu().numpy() if torch.is_tensor(kw[k]) else np.asarray(kw[k], dtype=np.float32)
-            v = np.asarray(v, dtype=np.float32).reshape(n, -1)
-            if v.shape[1] != cnt:
-                raise ValueError(f"{k}: expected {cnt} values per transition, got {v.shape[1]}")
-            host[:, self._off[k]:self._off[k] + cnt] = v
-        return host
-
-    def _store_rows(self, host) -> None:
-        """ONE host->device copy of the assembled rows (pinned staging), then device-side copies into the field matrices
-        (ring wrap = two slices).  The reference converts and copies every field of every sampled batch instead (DRL.py:379-386)."""
-        n = host.shape[0]
-        if n > self.size:
-            host, n = host[-self.size:], self.size
-        stage = torch.from_numpy(host).pin_memory()
-        dev = stage.to(self.device, non_blocking=True)
-        i = self.next_index
-        first = min(n, self.size - i)
-        for k, cnt in self.fields.items():
-            o = self._off[k]
-            self.store[k][i:i + first, :cnt].copy_(dev[:first, o:o + cnt])
-            if first < n:
-                self.store[k][:n - first, :cnt].copy_(dev[first:, o:o + cnt])
-        self._last_stage = (stage, dev)          # keep the pinned buffer alive until the async copy has certainly been issued
-        self.next_index = (i + n) % self.size
-        self.stored = min(self.stored + n, self.size)
-
     def _on_store(self, start: int, n: int) -> None:
         """hook: ring slots start .. start + n - 1 (mod size) have just been written"""
 
-    def _frame_source(self, k, v, n):
-        """How frame field k of n transitions travels into a uint8 ring: ("device", (n, H*W) fp32 or uint8 tensor on self.device),
-        ("bytes", (n, H*W) uint8 array: the codes themselves) or ("floats", (n, H*W) fp32 array)."""
-        if torch.is_tensor(v) and v.device.type != "cpu":
+    def _travel(self, k, v, n):
+        """How field k of n transitions travels into the ring: ("floats", (n, cnt) fp32 array), in the one staged matrix -- every field of
+        an fp32 ring, device tensors included, and every non-frame field --, or, for a frame field of a uint8 ring, also ("bytes", (n, H*W)
+        uint8 array: the codes themselves) or ("device", (n, H*W) fp32 or uint8 tensor on self.device)."""
+        frame_u8 = self.frame_dtype is torch.uint8 and k in FRAME_FIELDS
+        if frame_u8 and torch.is_tensor(v) and v.device.type != "cpu":
             v = v.detach().to(self.device)
             v = (v if v.dtype in (torch.uint8, torch.float32) else v.float()).reshape(n, -1).contiguous()
             kind = "device"
         else:
             if torch.is_tensor(v):
-                v = v.detach()
+                v = v.detach().cpu()
                 v = (v if v.dtype == torch.uint8 else v.float()).numpy()
-            v = np.asarray(v)
-            kind = "bytes" if v.dtype == np.uint8 else "floats"
-            v = (v if kind == "bytes" else np.asarray(v, dtype=np.float32)).reshape(n, -1)
+            elif frame_u8:
+                v = np.asarray(v)
+            kind = "bytes" if frame_u8 and v.dtype == np.uint8 else "floats"
+            v = np.asarray(v, dtype=np.uint8 if kind == "bytes" else np.float32).reshape(n, -1)
         if v.shape[1] != self.fields[k]:
             raise ValueError(f"{k}: expected {self.fields[k]} values per transition, got {v.shape[1]}")
         return kind, v
 
     def _ring_copy(self, k, rows, i, first) -> None:
-        """device rows (n, H*W) uint8 -> ring slots i .. of field k (ring wrap = two slices); the padding bytes stay zero"""
+        """device rows (n, cnt) -> ring slots i .. of field k (ring wrap = two slices); the padding columns stay zero"""
         cnt, n = self.fields[k], rows.shape[0]
         self.store[k][i:i + first, :cnt].copy_(rows[:first])
         if first < n:
             self.store[k][:n - first, :cnt].copy_(rows[first:])
 
-    def _store_u8(self, kw, n) -> None:
-        """add / add_batch of a uint8 ring.  The non-frame fields and the frame fields given as host floats travel side by side in ONE
-        staged fp32 matrix, as in ``_store_rows``; such a frame field is quantised straight from the staged matrix by one
-        dgvit_quantize_rows_u8 launch (the ring wrap inside it).  Frame fields given as host uint8 are staged as bytes (one byte matrix,
-        one copy) and copied into the ring; device tensors are quantised (fp32) or copied (uint8) where they are."""
+    def _store(self, kw, n) -> None:
+        """add / add_batch of both ring kinds.  Every field that travels as host floats (``_travel``) lies side by side in ONE staged fp32
+        matrix: one host->device copy from pinned memory, then device-side copies into the field matrices -- the reference converts and
+        copies every field of every sampled batch instead (DRL.py:379-386).  A uint8 ring differs only in its frame fields: host floats
+        are quantised straight from the staged matrix by one dgvit_quantize_rows_u8 launch (the ring wrap inside it), host uint8 is
+        staged as bytes (one byte matrix, one copy) and copied into the ring, device tensors are quantised (fp32) or copied (uint8)
+        where they are.  Which frame fields the matrix holds is the call's, so its column offsets are too: fixed ones would stage
+        2 H W unused floats per transition whenever the frames come as bytes or from the device."""
         for k in self.fields:
             if k not in kw:
                 raise KeyError(f"missing field {k}")
-        frames = {k: self._frame_source(k, kw[k], n) for k in FRAME_FIELDS}
-        staged = [k for k in self.fields if k not in FRAME_FIELDS or frames[k][0] == "floats"]
+        rows = {k: self._travel(k, kw[k], n) for k in self.fields}
         off, row = {}, 0
-        for k in staged:
-            off[k] = row
-            row += self.rows[k]
+        for k in self.fields:
+            if rows[k][0] == "floats":
+                off[k] = row
+                row += self.rows[k]
         host = np.zeros((n, row), dtype=np.float32)
-        for k in staged:
-            cnt = self.fields[k]
-            if k in FRAME_FIELDS:
-                v = frames[k][1]
-            else:
-                v = kw[k].detach().cpu().numpy() if torch.is_tensor(kw[k]) else np.asarray(kw[k], dtype=np.float32)
-                v = np.asarray(v, dtype=np.float32).reshape(n, -1)
-                if v.shape[1] != cnt:
-                    raise ValueError(f"{k}: expected {cnt} values per transition, got {v.shape[1]}")
-            host[:, off[k]:off[k] + cnt] = v
+        for k, o in off.items():
+            host[:, o:o + self.fields[k]] = rows[k][1]
         drop = max(n - self.size, 0)             # n > size: the last `size` transitions are the ones that stay
         n -= drop
         stage = torch.from_numpy(host[drop:]).pin_memory()
         dev = stage.to(self.device, non_blocking=True)
         keep = [stage, dev]
-        as_bytes = [k for k in FRAME_FIELDS if frames[k][0] == "bytes"]
+        as_bytes = [k for k in FRAME_FIELDS if rows[k][0] == "bytes"]
         if as_bytes:
             cnt = self.fields["obs"]
             bstage = torch.empty(n, len(as_bytes) * cnt, dtype=torch.uint8).pin_memory()
             for j, k in enumerate(as_bytes):
-                bstage.numpy()[:, j * cnt:(j + 1) * cnt] = frames[k][1][drop:]
+                bstage.numpy()[:, j * cnt:(j + 1) * cnt] = rows[k][1][drop:]
             bdev = bstage.to(self.device, non_blocking=True)
             keep += [bstage, bdev]
         i = self.next_index
         first = min(n, self.size - i)
-        lib = _lib.load()
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for k in self.fields:
-                cnt = self.fields[k]
-                if k not in FRAME_FIELDS:
-                    o = off[k]
-                    self.store[k][i:i + first, :cnt].copy_(dev[:first, o:o + cnt])
-                    if first < n:
-                        self.store[k][:n - first, :cnt].copy_(dev[first:, o:o + cnt])
-                    continue
-                kind, v = frames[k]
+            for k, cnt in self.fields.items():
+                kind, v = rows[k]
                 if kind == "bytes":
                     j = as_bytes.index(k)
                     self._ring_copy(k, bdev[:, j * cnt:(j + 1) * cnt], i, first)
                 elif kind == "device" and v.dtype == torch.uint8:
                     self._ring_copy(k, v[drop:], i, first)
-                else:
+                elif self.store[k].dtype == torch.float32:
+                    self._ring_copy(k, dev[:, off[k]:off[k] + cnt], i, first)
+                else:                            # fp32 rows, staged or on the device, into a byte ring
                     src, ld = (dev[:, off[k]:], row) if kind == "floats" else (v[drop:], cnt)
-                    rc = lib.dgvit_quantize_rows_u8(_ptr(src), ld, _ptr(self.store[k]), n, cnt, self.row_bytes, self.size, i, st)
+                    rc = _lib.load().dgvit_quantize_rows_u8(_ptr(src), ld, _ptr(self.store[k]), n, cnt, self.row_bytes, self.size, i, _stream())
                     _lib.check(rc, "dgvit_quantize_rows_u8")
         self._last_stage = keep                  # keep the pinned buffers alive until the async copies have certainly been issued
         self.next_index = (i + n) % self.size
@@ -215,16 +164,12 @@ class DeviceReplayBuffer:
     def add(self, **kw) -> None:
         """One transition (numpy arrays / scalars / tensors), same keywords as replay_buffer.add in DRL.py:439-448:
         one staged host->device copy for the whole transition."""
-        if self.frame_dtype is torch.uint8:
-            return self._store_u8(kw, 1)
-        self._store_rows(self._host_rows(kw, 1))
+        self._store(kw, 1)
 
     def add_batch(self, **kw) -> None:
         """Many transitions at once (first axis = transitions), e.g. the expert demonstrations of DRL.py:469-478: assembled on
         the host with numpy slicing, one host->device copy."""
-        if self.frame_dtype is torch.uint8:
-            return self._store_u8(kw, len(kw["obs"]))
-        self._store_rows(self._host_rows(kw, len(kw["obs"])))
+        self._store(kw, len(kw["obs"]))
 
     def sample_indices(self, batch_size: int) -> torch.Tensor:
         if self.stored == 0:
@@ -247,7 +192,7 @@ class DeviceReplayBuffer:
         u8 = self.frame_dtype is torch.uint8
         idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
         B = idx.numel()
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _stream()
         out = {}
         if pad:
             self.shift_seed = _shift_seed(self.device)
@@ -257,22 +202,14 @@ class DeviceReplayBuffer:
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
                 if pad and k in FRAME_FIELDS:
                     shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
-                    if u8:
-                        seed_dev = self.shift_seed if isinstance(self.shift_seed, torch.Tensor) else None
-                        rc = lib.dgvit_gather_shift_frames_u8(_ptr(self.store[k]), _ptr(idx), _ptr(buf), _ptr(shifts), B, *self.shapes[k],
-                                                              self.row_bytes, r, self.size, pad, int(k == "next_obs"),
-                                                              0 if seed_dev is not None else int(self.shift_seed), _ptr(seed_dev), st)
-                        _lib.check(rc, "dgvit_gather_shift_frames_u8")
-                    else:
-                        _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
+                    _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
                     if return_shifts:
                         out[k + "_shift"] = shifts
                 elif u8 and k in FRAME_FIELDS:
                     rc = lib.dgvit_gather_rows_u8(_ptr(self.store[k]), _ptr(idx), _ptr(buf), B, n, self.row_bytes, r, self.size, st)
                     _lib.check(rc, "dgvit_gather_rows_u8")
                 else:
-                    rc = lib.dgvit_gather_rows(ctypes.c_void_p(self.store[k].data_ptr()), ctypes.c_void_p(idx.data_ptr()),
-                                               ctypes.c_void_p(buf.data_ptr()), B, r, self.size, st)
+                    rc = lib.dgvit_gather_rows(_ptr(self.store[k]), _ptr(idx), _ptr(buf), B, r, self.size, st)
                     _lib.check(rc, "dgvit_gather_rows")
                 out[k] = buf[:, :n].reshape(B, *self.shapes[k])
         if return_shifts and not pad:
@@ -334,29 +271,17 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             raise _lib.DgvitError("dgvit_per_tree_floats disagrees with replay.per_tree_layout; rebuild the library")
         self.tree = torch.empty(floats, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(lib.dgvit_per_init(self._tree_ptr(), self.size, self._stream()), "dgvit_per_init")
-
-    def _tree_ptr(self):
-        return ctypes.c_void_p(self.tree.data_ptr())
-
-    @staticmethod
-    def _stream():
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _store_rows(self, host) -> None:
-        """the base's copy, then the ring range just written takes the max priority (an overwritten slot forgets its old one)"""
-        n, i = min(host.shape[0], self.size), self.next_index
-        super()._store_rows(host)
-        self._on_store(i, n)
+            _lib.check(lib.dgvit_per_init(_ptr(self.tree), self.size, _stream()), "dgvit_per_init")
 
     def _on_store(self, i: int, n: int) -> None:
-        """the max priority for ring slots i .. i + n - 1 (mod size): every add path of both ring kinds ends here"""
+        """the max priority for ring slots i .. i + n - 1 (mod size), an overwritten slot forgetting its old one: the base's one store
+        path ends here"""
         first = min(n, self.size - i)
         lib = _lib.load()
         with torch.cuda.device(self.device):
             for start, count in ((i, first), (0, n - first)):
                 if count > 0:
-                    _lib.check(lib.dgvit_per_set_range(self._tree_ptr(), self.size, start, count, self._stream()), "dgvit_per_set_range")
+                    _lib.check(lib.dgvit_per_set_range(_ptr(self.tree), self.size, start, count, _stream()), "dgvit_per_set_range")
 
     def draw(self, batch_size: int, beta: float = 0.4, stratified: bool = False,
              uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -378,8 +303,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         idx = torch.empty(B, dtype=torch.int64, device=self.device)
         weights = torch.empty(B, 1, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = _lib.load().dgvit_per_sample(self._tree_ptr(), self.size, ctypes.c_void_p(uniforms.data_ptr()), B, int(bool(stratified)), beta,
-                                              ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(weights.data_ptr()), self._stream())
+            rc = _lib.load().dgvit_per_sample(_ptr(self.tree), self.size, _ptr(uniforms), B, int(bool(stratified)), beta, _ptr(idx),
+                                              _ptr(weights), _stream())
         _lib.check(rc, "dgvit_per_sample")
         return idx, weights
 
@@ -405,8 +330,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         if prio.numel() != idx.numel() or priorities.dim() > 2 or (priorities.dim() == 2 and priorities.shape[1] != 1) or idx.numel() == 0:
             raise ValueError(f"priorities must be (B,) or (B, 1) with B = {idx.numel()} >= 1 entries, got {tuple(priorities.shape)}")
         with torch.cuda.device(self.device):
-            rc = _lib.load().dgvit_per_update(self._tree_ptr(), self.size, self.stored, ctypes.c_void_p(idx.data_ptr()),
-                                              ctypes.c_void_p(prio.data_ptr()), idx.numel(), self.alpha, self.eps, self._stream())
+            rc = _lib.load().dgvit_per_update(_ptr(self.tree), self.size, self.stored, _ptr(idx), _ptr(prio), idx.numel(), self.alpha,
+                                              self.eps, _stream())
         _lib.check(rc, "dgvit_per_update")
 
     def priorities(self) -> torch.Tensor:

@@ -3,7 +3,7 @@ the formulas in include/dgvit_hip.h, independent of the kernels.
 
 * ``quantize``:   code = rint(clip(fl(x * 255), 0, 255)) in fp32, halves to even (np.rint), NaN -> 0.
 * ``dequantize``: fl(k / 255) in fp32, a correctly rounded division -- what ``uint8_tensor.float() / 255`` computes.
-* ``newton_dequantize``: the three fp32 operations the kernels use in place of the division (csrc/replay_u8.hip: dequant_u8), each
+* ``newton_dequantize``: the three fp32 operations the kernels use in place of the division (csrc/replay_ring.hip: dequant_u8), each
   evaluated in exact rational arithmetic and rounded once, as a hardware multiply and fused multiply-add round.
 * ``tie_inputs``: fp32 inputs whose product with 255 rounds to exactly m + 0.5, where half-to-even and half-away-from-zero part.
 * ``pattern``:    frames of codes for offset tests.  Bytes cannot carry a distinct value per pixel; a prime modulus (251) with

@@ -461,3 +461,61 @@ def test_prioritized_sample_and_update_in_one_captured_graph(amd):
         np.testing.assert_array_equal(buf.priorities().cpu().numpy(), leaves)
         drawn.append(torch.cat([idx, static["obs_shift"].reshape(-1).long()]))
     assert not torch.equal(drawn[0], drawn[1])
+
+
+def test_both_rings_hold_the_same_transitions_after_the_same_adds(amd):
+    """An fp32 and a uint8 ring, and a prioritized twin of each, fed the same k / 255 transitions through the one store path: 5 single
+    adds, an add_batch of 16 that wraps, an add_batch of 21 > size.  The frame fields rotate through the four forms a uint8 ring takes
+    (the fp32 ring gets the same frames as floats, on the host or on the device).  After every step the two rings agree in next_index,
+    stored, every non-frame field and every field of sample(indices = all slots), bit for bit; the slots just written hold the frames
+    given and, in the prioritized twins, the max priority.  (12, 10) frames: W % 4 != 0, and row_bytes = al16(120) = 128 leaves 8 padding
+    bytes per ring row (the fp32 row is al4(120) = 120 floats)."""
+    from dgvit_amd.replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+    S, h, w = 16, 12, 10
+    pairs = [tuple(cls(S, obs_shape=(h, w), seed=0, frame_dtype=dt, **kw) for dt in (torch.float32, torch.uint8))
+             for cls, kw in ((DeviceReplayBuffer, {}), (PrioritizedDeviceReplayBuffer, dict(alpha=1.0, eps=0.0)))]
+    g = np.random.default_rng(21)
+    every = torch.arange(S, device="cuda")
+    frames = ("obs", "next_obs")
+    forms = ("host_float", "host_u8", "device_float", "device_u8")
+    f = lambda *s: g.standard_normal(s).astype(np.float32)      # noqa: E731
+    pos = total = 0
+    for step, n in enumerate([1, 1, 1, 1, 1, 16, 21]):
+        codes = {k: g.integers(0, 256, (n, h, w), dtype=np.uint8) for k in frames}
+        exact = {k: R.dequantize(codes[k]) for k in frames}
+        t = dict(pobs=f(n, 2), next_pobs=f(n, 2), act=f(n, 2), rew=f(n, 1), done=(g.random((n, 1)) < 0.5).astype(np.float32))
+        form = {k: forms[(step + j) % 4] for j, k in enumerate(frames)}
+        to_u8 = {k: {"host_float": exact[k], "host_u8": codes[k], "device_float": torch.from_numpy(exact[k]).cuda(),
+                     "device_u8": torch.from_numpy(codes[k]).cuda()}[form[k]] for k in frames}
+        to_f32 = {k: torch.from_numpy(exact[k]).cuda() if form[k].startswith("device") else exact[k] for k in frames}
+        kept = min(n, S)
+        slots = torch.from_numpy((pos + np.arange(kept)) % S)
+        for f32, u8 in pairs:
+            for buf, fr in ((f32, to_f32), (u8, to_u8)):
+                if hasattr(buf, "tree") and buf.stored:
+                    buf.update_priorities(every, torch.full((S,), 0.25, device="cuda"))
+                if n == 1:
+                    buf.add(**{k: v[0] for k, v in {**t, **fr}.items()})
+                else:
+                    buf.add_batch(**t, **fr)
+            assert f32.next_index == u8.next_index == (pos + kept) % S, (step, form)
+            assert f32.stored == u8.stored == min(total + n, S), (step, form)
+            for k in SMALL:
+                assert torch.equal(f32.store[k], u8.store[k]), (step, k)
+            a, b = (DeviceReplayBuffer.sample(buf, S, indices=every) for buf in (f32, u8))
+            assert list(a) == list(b)
+            for k in a:
+                assert torch.equal(a[k], b[k]), (step, form, k)
+            for k in frames:
+                assert torch.equal(b[k].cpu()[slots], torch.from_numpy(exact[k][-kept:])), (step, form, k)
+                assert u8.store[k].shape[1] == 128 and not u8.store[k][:, h * w:].any(), (step, form, k)
+                assert not f32.store[k][:, h * w:].any(), (step, form, k)
+            for k in SMALL:
+                assert torch.equal(b[k].cpu()[slots], torch.from_numpy(t[k][-kept:])), (step, k)
+            if hasattr(f32, "tree"):
+                assert torch.equal(f32.priorities(), u8.priorities()), (step, form)
+                assert float(f32.max_priority) == float(u8.max_priority) == 1.0
+                assert torch.equal(u8.priorities().cpu()[slots], torch.ones(kept)), (step, form)
+                if total and kept < S:
+                    assert float(u8.min_priority) == 0.25, "slots not written keep the priority they had"
+        pos, total = (pos + kept) % S, total + n

@@ -171,10 +171,10 @@ def test_dequantize_is_torch_and_numpy_division_bit_for_bit():
 
 
 def test_the_kernels_newton_step_is_the_division_on_every_code():
-    """csrc/replay_u8.hip forms k / 255 as a product with fl(1/255) and one correction in two fused multiply-adds: restated with exact
+    """csrc/replay_ring.hip forms k / 255 as a product with fl(1/255) and one correction in two fused multiply-adds: restated with exact
     rational arithmetic and one rounding per operation, it is the correctly rounded quotient for all 256 codes"""
     assert np.float32(float.fromhex("0x1.010102p-8")) == np.float32(1) / np.float32(255)
-    with open(os.path.join(os.path.dirname(__file__), os.pardir, "dgvit-depth-goal-guided-vision-transformer-_amd", "csrc", "replay_u8.hip")) as f:
+    with open(os.path.join(os.path.dirname(__file__), os.pardir, "dgvit-depth-goal-guided-vision-transformer-_amd", "csrc", "replay_ring.hip")) as f:
         assert "0x1.010102p-8f" in f.read()
     got = np.array([R.newton_dequantize(k) for k in range(256)], dtype=np.float32)
     assert np.array_equal(got.view(np.uint32), R.dequantize(np.arange(256, dtype=np.uint8)).view(np.uint32))
