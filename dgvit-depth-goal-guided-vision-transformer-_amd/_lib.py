@@ -43,7 +43,7 @@ NUM_GLOBAL_PARAMS = 4
 PARAMS_PER_LAYER = 11
 ABI_VERSION = 7
 
-_P, _I, _LL, _F, _ULL = c_void_p, c_int, c_longlong, c_float, c_ulonglong
+_P, _I, _LL, _F, _ULL, _D = c_void_p, c_int, c_longlong, c_float, c_ulonglong, ctypes.c_double
 _CFG = POINTER(dgvit_config)
 _TABLE = POINTER(c_void_p)
 
@@ -104,6 +104,8 @@ SIGNATURES = {
     "dgvit_quantize_rows_u8": (_I, [_P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_gather_rows_u8": (_I, [_P, _P, _P, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_gather_shift_frames_u8": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _LL, _I, _I, _ULL, _P, _P]),
+    "dgvit_ring_mark": (_I, [_P, _LL, _LL, _LL, _P]),
+    "dgvit_nstep_walk": (_I, [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _LL, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "dgvit_per_tree_floats": (_LL, [_LL]),
     "dgvit_per_init": (_I, [_P, _LL, _P]),
     "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),
@@ -123,6 +125,7 @@ SIGNATURES = {
     "dgvit_scale_by_device_scalar": (_I, [_P, _LL, _P, _P]),
     # the SAC loss head (include/dgvit_hip.h: The SAC loss head)
     "dgvit_sac_critic_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _I, _P]),
+    "dgvit_sac_critic_loss_v2": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _I, _P]),
     "dgvit_sac_actor_loss": (_I, [_P, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I, _I, _P]),
     "dgvit_sac_scale_grads": (_I, [_P, _P, _LL, _P, _P]),
     "dgvit_got_bf16_weight_elems": (_LL, [_CFG]),

@@ -243,8 +243,15 @@ extern "C" int dgvit_scale_by_device_scalar(float* x, long long n, const float* 
 extern "C" int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
                                      const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
                                      float gamma, float* target, float* td, float* loss, float* grads, int B, int A, void* stream) {
-  return sac_critic_loss(q1, q2, reward, done, weights, next_q1, next_q2, next_log_pi, log_alpha, alpha, gamma, target, td, loss, grads, B, A,
-                         (hipStream_t)stream);
+  return sac_critic_loss(q1, q2, reward, done, weights, nullptr, next_q1, next_q2, next_log_pi, log_alpha, alpha, gamma, target, td, loss, grads,
+                         B, A, (hipStream_t)stream);
+}
+extern "C" int dgvit_sac_critic_loss_v2(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
+                                        const float* discount, const float* next_q1, const float* next_q2, const float* next_log_pi,
+                                        const float* log_alpha, float alpha, float gamma, float* target, float* td, float* loss, float* grads,
+                                        int B, int A, void* stream) {
+  return sac_critic_loss(q1, q2, reward, done, weights, discount, next_q1, next_q2, next_log_pi, log_alpha, alpha, gamma, target, td, loss,
+                         grads, B, A, (hipStream_t)stream);
 }
 extern "C" int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha,
                                     int with_temperature, float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A,
@@ -280,6 +287,17 @@ extern "C" int dgvit_gather_shift_frames_u8(const unsigned char* ring, const lon
                                             unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
   return gather_shift_frames_u8(ring, idx, out, shifts_out, nsel, H, W, row_bytes, row_floats, nrows, pad, stream_id, seed, seed_dev,
                                 (hipStream_t)stream);
+}
+// episode flags and the n-step walk (replay_ring.hip)
+extern "C" int dgvit_ring_mark(unsigned char* flags, long long nrows, long long start, long long n, void* stream) {
+  return ring_mark(flags, nrows, start, n, (hipStream_t)stream);
+}
+extern "C" int dgvit_nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                                const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, int n,
+                                double gamma, float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out,
+                                long long* tail_out, void* stream) {
+  return nstep_walk(rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, n, gamma, ret_out, done_out, discount_out,
+                    next_small_out, steps_out, tail_out, (hipStream_t)stream);
 }
 // prioritized replay (replay.hip)
 extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }

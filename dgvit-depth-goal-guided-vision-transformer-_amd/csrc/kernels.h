@@ -57,10 +57,11 @@ int grad_clip_coef(const double* partials, float max_norm, float* out, hipStream
 int adam_step_scaled(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
                      const float* grad_scale_dev, hipStream_t);
 int scale_by_device_scalar(float* x, long long n, const float* scale_dev, hipStream_t);
-// the SAC loss head (sac_loss.hip): one launch per loss, alpha from device memory; done, weights, log_alpha, td and grads may be null
-int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* next_q1,
-                    const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma, float* target, float* td,
-                    float* loss, float* grads, int B, int A, hipStream_t);
+// the SAC loss head (sac_loss.hip): one launch per loss, alpha from device memory; done, weights, discount, log_alpha, td and
+// grads may be null; discount (B values) takes the place of gamma sample by sample
+int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* discount,
+                    const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma,
+                    float* target, float* td, float* loss, float* grads, int B, int A, hipStream_t);
 int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha, int with_temperature,
                    float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A, hipStream_t);
 int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t);
@@ -84,6 +85,11 @@ int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, 
 int gather_shift_frames_u8(const unsigned char* ring, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
                            long long row_bytes, long long row_floats, long long nrows, int pad, int stream_id, unsigned long long seed,
                            const unsigned long long* seed_dev, hipStream_t stream);
+// episode flags of the ring's slots and the n-step walk along them (include/dgvit_hip.h: n-step returns)
+int ring_mark(unsigned char* flags, long long nrows, long long start, long long n, hipStream_t stream);
+int nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags, const float* next_small,
+               long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma, float* ret_out, float* done_out,
+               float* discount_out, float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream);
 // replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
 long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
 int per_init(float* tree, long long capacity, hipStream_t stream);

@@ -6,6 +6,9 @@
 //   quantize_rows_u8        : ring[(start + i) % nrows][c] = q(src[i][c]),  q(x) = (uint8) rintf(fminf(fmaxf(x * 255, 0), 255))
 //   gather_shift_frames     : the gather with the DrQ random shift (replicate-pad by `pad`, crop at a per-sample offset) folded in
 //   gather_shift_frames_u8  : the same kernel template over a byte ring: one draw, one set of clamps
+//   ring_mark               : the per-slot episode flags after a store: the written slots forget their marks, the newest one is the HEAD
+//   nstep_walk              : the n-step return of each sampled slot: a walk along the ring that stops at done, at a flag or after n slots,
+//                             one wave per sample, the rewards summed in double in ascending order
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
 // the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
@@ -146,6 +149,68 @@ __global__ void __launch_bounds__(256) gather_shift_frames_kernel(const T* __res
   reinterpret_cast<float4*>(out)[r * row4 + c] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// Episode flags, one byte per slot.  END: the slot's transition is the last of its episode; HEAD: the slot is the newest one
+// written, its ring successor is the oldest slot or an unwritten one.  A walk stops behind any slot whose byte is not zero.
+constexpr unsigned char RING_END = 1, RING_HEAD = 2;
+constexpr int NSTEP_MAX = 64;   // one lane per visited slot
+
+// thread j < n: slot (start + j) % nrows forgets its marks, the last one becomes the HEAD; thread n: the slot before `start` is no longer
+// the newest and keeps only its END -- unless the store covered the whole ring, in which case that slot has just been written
+__global__ void __launch_bounds__(256) ring_mark_kernel(unsigned char* __restrict__ flags, long long nrows, long long start, long long n) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) {
+    long long d = start + j;    // start < nrows and j < n <= nrows: one subtraction wraps the ring
+    if (d >= nrows) d -= nrows;
+    flags[d] = j == n - 1 ? RING_HEAD : 0;
+  } else if (j == n && n < nrows) {
+    const long long p = start > 0 ? start - 1 : nrows - 1;
+    flags[p] &= RING_END;
+  }
+}
+
+// One wave per sample (4 per workgroup), as per_sample_kernel.  Lane k < n loads rew, done and flags of slot s_k = (i + k) mod nrows, so
+// the walk is one memory round trip; the ballot of the stop predicate gives m, the slots visited; the sum runs over lanes < m in ascending
+// order in double, every lane the same arithmetic; then the lanes copy the next_small row of the last slot.  Every slot index is reduced
+// mod nrows and i is clamped: nothing here can address outside the ring.  No atomics: the result is a function of the ring and idx[b].
+__global__ void __launch_bounds__(256) nstep_walk_kernel(const float* __restrict__ rew, long long rew_ld, const float* __restrict__ done,
+                                                         long long done_ld, const unsigned char* __restrict__ flags,
+                                                         const float4* __restrict__ next_small, int small4, const long long* __restrict__ idx,
+                                                         long long nsel, long long nrows, int n, double gamma, float* __restrict__ ret_out,
+                                                         float* __restrict__ done_out, float* __restrict__ discount_out,
+                                                         float4* __restrict__ next_small_out, int* __restrict__ steps_out,
+                                                         long long* __restrict__ tail_out) {
+  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (w >= nsel) return;       // wave-uniform
+  long long s = ring_row(idx[w], nrows) + lane;
+  if (nrows >= NSTEP_MAX) {    // s < 2 nrows: one subtraction wraps the ring
+    if (s >= nrows) s -= nrows;
+  } else {
+    s = (long long)((unsigned)s % (unsigned)nrows);   // a ring shorter than the walk: s < 128
+  }
+  const bool active = lane < n;
+  const float r = active ? rew[s * rew_ld] : 0.f;
+  const float d = active ? done[s * done_ld] : 0.f;
+  const unsigned f = active ? (unsigned)flags[s] : 0u;
+  const unsigned long long stop = __ballot(active && (d != 0.f || f != 0u || lane == n - 1));   // lane n - 1 always stops: never empty
+  const int m = __ffsll((long long)stop);
+  double acc = 0.0, g = 1.0;
+  for (int k = 0; k < m; ++k) {     // m is wave-uniform
+    acc += g * (double)__shfl(r, k, 64);
+    g *= gamma;
+  }
+  const long long tail = __shfl(s, m - 1, 64);
+  const float dm = __shfl(d, m - 1, 64);
+  if (lane == 0) {
+    ret_out[w] = (float)acc;
+    done_out[w] = dm;
+    discount_out[w] = (float)g;
+    steps_out[w] = m;
+    tail_out[w] = tail;
+  }
+  for (int c = lane; c < small4; c += 64) next_small_out[w * small4 + c] = next_small[tail * small4 + c];
+}
+
 // both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
 template <typename T>
 int launch_gather_shift(const char* name, const T* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
@@ -243,5 +308,39 @@ int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, 
   hipLaunchKernelGGL(gather_rows_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ring, idx, out, total4, out4, (int)cols, row_bytes,
                      nrows);
   DGVIT_CHECK_LAUNCH("gather_rows_u8");
+  return DGVIT_OK;
+}
+
+int ring_mark(unsigned char* flags, long long nrows, long long start, long long n, hipStream_t stream) {
+  DGVIT_CHECK_ARG(flags, "ring_mark: flags must not be null");
+  DGVIT_CHECK_ARG(nrows > 0 && n > 0 && n <= nrows, "ring_mark: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_mark: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  const long long blocks = (n + 1 + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_mark: n=%lld slots are more than one launch covers", n);
+  hipLaunchKernelGGL(ring_mark_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, flags, nrows, start, n);
+  DGVIT_CHECK_LAUNCH("ring_mark");
+  return DGVIT_OK;
+}
+
+int nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags, const float* next_small,
+               long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma, float* ret_out, float* done_out,
+               float* discount_out, float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream) {
+  DGVIT_CHECK_ARG(rew && done && flags && next_small && idx, "nstep_walk: rew, done, flags, next_small and idx must not be null");
+  DGVIT_CHECK_ARG(ret_out && done_out && discount_out && next_small_out && steps_out && tail_out,
+                  "nstep_walk: ret_out, done_out, discount_out, next_small_out, steps_out and tail_out must not be null");
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0, "nstep_walk: nsel=%lld must be in [1, 2^31) and nrows=%lld positive", nsel, nrows);
+  DGVIT_CHECK_ARG(n >= 1 && n <= NSTEP_MAX, "nstep_walk: n=%d must be in [1, %d]", n, NSTEP_MAX);
+  DGVIT_CHECK_ARG(gamma >= 0.0 && gamma <= 1.0, "nstep_walk: gamma=%g must be in [0, 1]", gamma);   // a NaN fails both comparisons
+  DGVIT_CHECK_ARG(rew_ld > 0 && done_ld > 0, "nstep_walk: rew_ld=%lld and done_ld=%lld must be positive", rew_ld, done_ld);
+  DGVIT_CHECK_ARG(small_ld > 0 && small_ld % 4 == 0 && small_ld <= (1ll << 20),
+                  "nstep_walk: small_ld=%lld must be a positive multiple of 4, at most 2^20", small_ld);
+  DGVIT_CHECK_ARG(al16(next_small) && al16(next_small_out), "nstep_walk: next_small and next_small_out must be 16-byte aligned");
+  DGVIT_CHECK_ARG(al4p(rew) && al4p(done) && al4p(ret_out) && al4p(done_out) && al4p(discount_out) && al4p(steps_out) &&
+                      (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (reinterpret_cast<uintptr_t>(tail_out) & 7) == 0,
+                  "nstep_walk: float and int32 pointers must be 4-byte aligned, idx and tail_out 8-byte aligned");
+  hipLaunchKernelGGL(nstep_walk_kernel, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags,
+                     reinterpret_cast<const float4*>(next_small), (int)(small_ld / 4), idx, nsel, nrows, n, gamma, ret_out, done_out,
+                     discount_out, reinterpret_cast<float4*>(next_small_out), steps_out, tail_out);
+  DGVIT_CHECK_LAUNCH("nstep_walk");
   return DGVIT_OK;
 }

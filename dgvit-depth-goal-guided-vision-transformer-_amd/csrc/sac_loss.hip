@@ -1,7 +1,8 @@
 // The SAC loss head: what SAC.learn computes between the network forwards and the backwards (DRL.py:384-425; SURVEY 3(A),
 // row a14), each loss with its gradient in ONE launch, the temperature read from device memory so that a captured step follows it.
 //   sac_critic_loss : y = r + (1 - done) gamma (min(q1n, q2n) - alpha logp_next);  loss = mean(w (q1 - y)^2) + mean(w (q2 - y)^2);
-//                     td[b] = mean_a |q1 - y|;  dq1 | dq2 for a unit upstream gradient
+//                     td[b] = mean_a |q1 - y|;  dq1 | dq2 for a unit upstream gradient.  discount[b], when given, stands where gamma
+//                     does: the gamma^m of an n-step batch
 //   sac_actor_loss  : policy_loss = mean(alpha logp - min(q1pi, q2pi)), alpha_loss = -log_alpha mean(logp + target_entropy), and
 //                     d logp | dq1pi | dq2pi and d log_alpha for unit upstream gradients
 //   sac_scale_grads : dst = *scale_dev * src, the backward of either loss for the 0-d upstream gradient autograd hands over
@@ -35,9 +36,9 @@ __device__ __forceinline__ double block_sum(double s, double* wave_sum) {
 
 __global__ void __launch_bounds__(256) sac_critic_loss_kernel(const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ reward,
                                                               const float* __restrict__ done, const float* __restrict__ weights,
-                                                              const float* __restrict__ q1n, const float* __restrict__ q2n,
+                                                              const float* __restrict__ discount, const float* __restrict__ q1n, const float* __restrict__ q2n,
                                                               const float* __restrict__ nlogp, const float* __restrict__ log_alpha, float alpha,
-                                                              float gamma, float* __restrict__ y, float* __restrict__ td, float* __restrict__ loss,
+                                                              float gamma_all, float* __restrict__ y, float* __restrict__ td, float* __restrict__ loss,
                                                               float* __restrict__ grads, int B, int A) {
   __shared__ double wave_sum[4];
   const float al = sac_alpha(log_alpha, alpha);
@@ -48,6 +49,7 @@ __global__ void __launch_bounds__(256) sac_critic_loss_kernel(const float* __res
     const int b = i / A;
     const float r = reward[b], nd = done ? 1.f - done[b] : 1.f, nlp = nlogp[b];
     const double w = weights ? (double)weights[b] : 1.0;
+    const float gamma = discount ? discount[b] : gamma_all;
     const float yi = sac_target(r, nd, gamma, q1n[i], q2n[i], al, nlp);
     const double e1 = (double)q1[i] - (double)yi, e2 = (double)q2[i] - (double)yi;
     acc += w * (e1 * e1 + e2 * e2);
@@ -130,23 +132,23 @@ inline bool al4p(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) ==
 
 }  // namespace
 
-int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* next_q1,
-                    const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma, float* target, float* td,
-                    float* loss, float* grads, int B, int A, hipStream_t stream) {
+int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* discount,
+                    const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha, float gamma,
+                    float* target, float* td, float* loss, float* grads, int B, int A, hipStream_t stream) {
   DGVIT_CHECK_ARG(q1 && q2 && reward && next_q1 && next_q2 && next_log_pi, "sac_critic_loss: q1, q2, reward, next_q1, next_q2 and next_log_pi must not be null");
   DGVIT_CHECK_ARG(target && loss, "sac_critic_loss: target and loss must not be null");
   DGVIT_CHECK_ARG(B >= 1, "sac_critic_loss: B=%d must be at least 1", B);
   DGVIT_CHECK_ARG(A >= 1 && A <= SAC_MAX_ACTIONS, "sac_critic_loss: A=%d must be in [1, %d]", A, SAC_MAX_ACTIONS);
   DGVIT_CHECK_ARG((long long)B * A <= SAC_MAX_ELEMS, "sac_critic_loss: B*A=%lld must be at most %lld", (long long)B * A, SAC_MAX_ELEMS);
   DGVIT_CHECK_ARG(log_alpha || std::isfinite(alpha), "sac_critic_loss: alpha=%g must be finite (or log_alpha given)", (double)alpha);
-  DGVIT_CHECK_ARG(std::isfinite(gamma), "sac_critic_loss: gamma=%g must be finite", (double)gamma);
-  DGVIT_CHECK_ARG(al4p(q1) && al4p(q2) && al4p(reward) && al4p(done) && al4p(weights) && al4p(next_q1) && al4p(next_q2) && al4p(next_log_pi) &&
+  DGVIT_CHECK_ARG(discount || std::isfinite(gamma), "sac_critic_loss: gamma=%g must be finite (or discount given)", (double)gamma);
+  DGVIT_CHECK_ARG(al4p(q1) && al4p(q2) && al4p(reward) && al4p(done) && al4p(weights) && al4p(discount) && al4p(next_q1) && al4p(next_q2) && al4p(next_log_pi) &&
                       al4p(log_alpha) && al4p(target) && al4p(td) && al4p(loss) && al4p(grads),
                   "sac_critic_loss: pointers must be 4-byte aligned");
   {
     ProfileScope t(PROF_OTHER, 0.0, stream);
-    hipLaunchKernelGGL(sac_critic_loss_kernel, dim3(1), dim3(256), 0, stream, q1, q2, reward, done, weights, next_q1, next_q2, next_log_pi, log_alpha,
-                       alpha, gamma, target, td, loss, grads, B, A);
+    hipLaunchKernelGGL(sac_critic_loss_kernel, dim3(1), dim3(256), 0, stream, q1, q2, reward, done, weights, discount, next_q1, next_q2, next_log_pi,
+                       log_alpha, alpha, gamma, target, td, loss, grads, B, A);
   }
   DGVIT_CHECK_LAUNCH("sac_critic_loss");
   return DGVIT_OK;

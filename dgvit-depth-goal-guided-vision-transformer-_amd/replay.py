@@ -9,6 +9,10 @@ index draw plus one HBM-bound gather kernel per field -- the encoder never waits
 0..255 (env_lab.py:420-434, 348-349), so ``frame_dtype=torch.uint8`` stores them as bytes, a quarter of the ring, and the gather restores
 the fp32 frame.
 
+Consecutive ring slots are consecutive environment steps, so ``sample(..., n_step=n, gamma=g)`` returns multi-step transitions -- cpprb's
+``Nstep`` option -- by a walk along the ring at sample time: nothing extra is stored and n and gamma may change from call
+to call.  What a walk may not cross is kept in ``episode_flags``, one byte per slot on the device.
+
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
 from typing import Dict, Optional, Tuple
@@ -30,6 +34,8 @@ def _al16(n: int) -> int:
 
 
 FRAME_FIELDS = ("obs", "next_obs")
+FLAG_END, FLAG_HEAD = 1, 2  # include/dgvit_hip.h: DGVIT_RING_END, DGVIT_RING_HEAD (bits of episode_flags)
+NSTEP_MAX = 64              # one lane of a wave per visited slot
 
 
 def _frame_dtype(dtype):
@@ -37,6 +43,15 @@ def _frame_dtype(dtype):
     if dtype is not torch.float32 and dtype is not torch.uint8:
         raise ValueError(f"frame_dtype must be torch.float32 or torch.uint8, got {dtype!r}")
     return dtype
+
+
+def _n_step(n):
+    """``n_step`` after its check (None: one-step sampling): host-only, runs before anything touches a device"""
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= NSTEP_MAX:
+        raise ValueError(f"n_step must be None or an int in [1, {NSTEP_MAX}], got {n!r}")
+    return int(n)
 
 
 class DeviceReplayBuffer:
@@ -48,7 +63,15 @@ class DeviceReplayBuffer:
     frames, bit-equal to numpy's and CPU torch's ``codes / 255`` in fp32.  With a uint8 ring ``add`` / ``add_batch`` take each frame
     field, independently, as host floats (they travel in the one staged matrix and are quantised from it), as host uint8 (numpy or CPU
     tensor: the codes themselves, staged as bytes) or as a device tensor, fp32 or uint8, which never visits the host.  Buffers have no
-    ``state_dict``."""
+    ``state_dict``.
+
+    Episodes.  ``episode_flags`` is None until ``track_episodes()``, ``on_episode_end()`` or ``sample(n_step=...)`` is first
+    used; from then on it is a (size,) uint8 device tensor that the store path keeps current with one more launch per ``add`` /
+    ``add_batch``: bit 0 (END) marks the last transition of an episode, whatever its ``done`` says (time limits, truncations -- the
+    reference fetches ``done`` and never applies it, so ``done`` alone cannot mark episodes), bit 1 (HEAD) the newest slot written.  A
+    buffer that never uses them allocates nothing and launches nothing more than before.  Episode ends before tracking started are
+    unknown, apart from ``done``: call ``track_episodes()`` before the first ``add`` if n-step sampling is meant.  ``add_batch`` writes
+    consecutive slots, so demonstrations go in one episode per call, each followed by ``on_episode_end()`` -- or rely on their ``done``."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2,
                  device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32):
@@ -69,6 +92,7 @@ class DeviceReplayBuffer:
         else:
             self.store = {k: torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
         self.next_index, self.stored = 0, 0
+        self.episode_flags = None                # (size,) uint8 once episodes are tracked
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
             self.gen.manual_seed(int(seed))
@@ -78,6 +102,28 @@ class DeviceReplayBuffer:
 
     def _on_store(self, start: int, n: int) -> None:
         """hook: ring slots start .. start + n - 1 (mod size) have just been written"""
+
+    def track_episodes(self) -> None:
+        """Start keeping ``episode_flags`` (idempotent).  On allocation the flags are zeros with HEAD on the newest slot, if anything
+        is stored: episode ends from before are unknown, apart from ``done``.  The allocation cannot happen inside a stream capture."""
+        if self.episode_flags is not None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DgvitError("track_episodes() allocates the episode flags, which a stream capture cannot: call it (or on_episode_end(), "
+                                  "or an eager sample(n_step=...)) before capturing")
+        flags = torch.zeros(self.size, dtype=torch.uint8, device=self.device)
+        if self.stored:
+            flags[(self.next_index - 1) % self.size] = FLAG_HEAD
+        self.episode_flags = flags
+
+    def on_episode_end(self) -> None:
+        """The newest transition is the last of its episode, whatever its ``done`` says (cpprb's name): ORs END into its flags on the
+        device, without a host synchronisation."""
+        if self.stored == 0:
+            raise RuntimeError("on_episode_end() on an empty buffer: there is no newest transition")
+        self.track_episodes()
+        newest = (self.next_index - 1) % self.size
+        self.episode_flags[newest:newest + 1].bitwise_or_(FLAG_END)
 
     def _travel(self, k, v, n):
         """How field k of n transitions travels into the ring: ("floats", (n, cnt) fp32 array), in the one staged matrix -- every field of
@@ -156,6 +202,8 @@ class DeviceReplayBuffer:
                     src, ld = (dev[:, off[k]:], row) if kind == "floats" else (v[drop:], cnt)
                     rc = _lib.load().dgvit_quantize_rows_u8(_ptr(src), ld, _ptr(self.store[k]), n, cnt, self.row_bytes, self.size, i, _stream())
                     _lib.check(rc, "dgvit_quantize_rows_u8")
+            if self.episode_flags is not None:   # one launch: the written slots forget their marks, the last of them is the HEAD
+                _lib.check(_lib.load().dgvit_ring_mark(_ptr(self.episode_flags), self.size, i, n, _stream()), "dgvit_ring_mark")
         self._last_stage = keep                  # keep the pinned buffers alive until the async copies have certainly been issued
         self.next_index = (i + n) % self.size
         self.stored = min(self.stored + n, self.size)
@@ -177,7 +225,7 @@ class DeviceReplayBuffer:
         return torch.randint(0, self.stored, (batch_size,), device=self.device, dtype=torch.int64, generator=self.gen)
 
     def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None, random_shift: int = 0,
-               return_shifts: bool = False) -> Dict[str, torch.Tensor]:
+               return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99) -> Dict[str, torch.Tensor]:
         """Uniform sample with replacement -> dict of DEVICE tensors shaped like the reference's batch
         (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip.
 
@@ -186,8 +234,21 @@ class DeviceReplayBuffer:
         0 and 1 of one seed per call; the seed comes from torch's CPU generator, or from the device inside a stream capture, and is
         kept in ``self.shift_seed``).  ``return_shifts=True`` adds ``obs_shift`` and ``next_obs_shift``, (B, 2) int32 (dy, dx).
         With ``random_shift=0`` nothing is drawn and the launches are the plain gathers.  A uint8 ring (``frame_dtype``) takes the
-        ``_u8`` forms of the two frame launches and returns the same fp32 frames, code / 255."""
+        ``_u8`` forms of the two frame launches and returns the same fp32 frames, code / 255.
+
+        ``n_step=n`` (an int in [1, 64]; ``gamma`` in [0, 1]) returns n-step transitions, cpprb's ``Nstep``: from the sampled slot the
+        walk follows the ring for m <= n slots and stops behind the first one with ``done != 0`` or an episode flag (END or HEAD).
+        ``rew`` is then sum_{k<m} gamma^k rew_k (summed in double, rounded once), ``next_obs``, ``next_pobs`` and ``done`` are those of
+        the walk's last slot, and the dict gains ``discount`` (B, 1) fp32 = gamma^m -- what ``sac_losses.critic_loss(discount=...)``
+        takes in the place of gamma -- and ``steps`` (B,) int32 = m.  ``indexes`` stays the start slot, which is what
+        ``update_priorities`` must get.  Five launches instead of seven: the ``obs``, ``pobs`` and ``act`` gathers, the walk (which
+        produces ``rew``, ``done`` and ``next_pobs`` itself) and the ``next_obs`` gather at the walk's last slot.  Outside a capture
+        the call starts ``track_episodes()`` if nothing has; inside one the flags must exist already, and a replayed graph follows
+        the ring as later ``add()``s move it.  ``n_step=None`` is the one-step path above, launch for launch."""
+        n_step, gamma = _n_step(n_step), _unit("gamma", gamma)
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
+        if n_step is not None:
+            self.track_episodes()
         lib = _lib.load()
         u8 = self.frame_dtype is torch.uint8
         idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
@@ -197,25 +258,48 @@ class DeviceReplayBuffer:
         if pad:
             self.shift_seed = _shift_seed(self.device)
         with torch.cuda.device(self.device):
+            at = idx                             # the slots a field is gathered at: the walk's last ones for next_obs of an n-step call
             for k, n in self.fields.items():
                 r = self.rows[k]
+                if n_step is not None and k in ("rew", "next_pobs", "done"):
+                    if k == "rew":               # (fields are in the reference's order: obs, pobs and act are out, next_obs is to come)
+                        walk = self._walk(idx, n_step, gamma)
+                        at = walk.pop("tail")
+                    out[k] = walk.pop(k)
+                    continue
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
                 if pad and k in FRAME_FIELDS:
                     shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
-                    _gather_shift(self.store[k], idx, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
+                    _gather_shift(self.store[k], at, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
                     if return_shifts:
                         out[k + "_shift"] = shifts
                 elif u8 and k in FRAME_FIELDS:
-                    rc = lib.dgvit_gather_rows_u8(_ptr(self.store[k]), _ptr(idx), _ptr(buf), B, n, self.row_bytes, r, self.size, st)
+                    rc = lib.dgvit_gather_rows_u8(_ptr(self.store[k]), _ptr(at), _ptr(buf), B, n, self.row_bytes, r, self.size, st)
                     _lib.check(rc, "dgvit_gather_rows_u8")
                 else:
-                    rc = lib.dgvit_gather_rows(_ptr(self.store[k]), _ptr(idx), _ptr(buf), B, r, self.size, st)
+                    rc = lib.dgvit_gather_rows(_ptr(self.store[k]), _ptr(at), _ptr(buf), B, r, self.size, st)
                     _lib.check(rc, "dgvit_gather_rows")
                 out[k] = buf[:, :n].reshape(B, *self.shapes[k])
         if return_shifts and not pad:
             out["obs_shift"], out["next_obs_shift"] = (torch.zeros(B, 2, dtype=torch.int32, device=self.device) for _ in range(2))
+        if n_step is not None:
+            out.update(walk)                     # discount, steps
         out["indexes"] = idx
         return out
+
+    def _walk(self, idx, n_step, gamma):
+        """the one dgvit_nstep_walk launch of an n-step sample: rew, done, next_pobs, discount, steps and the tail slots"""
+        B, dev = idx.numel(), self.device
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+        ret, done, disc, small = f32(B), f32(B), f32(B), f32(B, self.rows["next_pobs"])
+        steps, tail = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+        rc = _lib.load().dgvit_nstep_walk(_ptr(self.store["rew"]), self.rows["rew"], _ptr(self.store["done"]), self.rows["done"],
+                                          _ptr(self.episode_flags), _ptr(self.store["next_pobs"]), self.rows["next_pobs"], _ptr(idx), B,
+                                          self.size, n_step, gamma, _ptr(ret), _ptr(done), _ptr(disc), _ptr(small), _ptr(steps), _ptr(tail),
+                                          _stream())
+        _lib.check(rc, "dgvit_nstep_walk")
+        return {"rew": ret.view(B, 1), "done": done.view(B, 1), "next_pobs": small[:, :self.fields["next_pobs"]], "discount": disc.view(B, 1),
+                "steps": steps, "tail": tail}
 
 
 PER_MAX_SIZE = 1 << 24      # include/dgvit_hip.h: the radix-64 tree has at most four levels
@@ -309,11 +393,13 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         return idx, weights
 
     def sample(self, batch_size: int, beta: float = 0.4, stratified: bool = False, uniforms: Optional[torch.Tensor] = None,
-               random_shift: int = 0, return_shifts: bool = False) -> Dict[str, torch.Tensor]:
-        """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift`` and
-        ``return_shifts`` as there).  The base's dict plus ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor."""
+               random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99) -> Dict[str, torch.Tensor]:
+        """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift``,
+        ``return_shifts``, ``n_step`` and ``gamma`` as there; the draw and the weights do not depend on them).  The base's dict plus
+        ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor, the start slots of an n-step sample."""
+        _n_step(n_step), _unit("gamma", gamma)
         idx, weights = self.draw(batch_size, beta, stratified, uniforms)
-        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts)
+        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma)
         out["weights"] = weights
         return out
 

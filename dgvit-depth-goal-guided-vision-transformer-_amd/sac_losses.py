@@ -87,7 +87,8 @@ class _Precomputed(torch.autograd.Function):
         return (None, None, *res)
 
 
-def critic_loss(q1, q2, reward, next_q1, next_q2, next_log_pi, *, alpha=None, log_alpha=None, gamma=0.99, done=None, weights=None):
+def critic_loss(q1, q2, reward, next_q1, next_q2, next_log_pi, *, alpha=None, log_alpha=None, gamma=0.99, done=None, weights=None,
+                discount=None):
     """``CriticLoss(loss, td, target)`` of the twin critics, one launch:
 
         target = reward + (1 - done) gamma (min(next_q1, next_q2) - alpha next_log_pi)           (B, A), detached: the no_grad target
@@ -95,27 +96,39 @@ def critic_loss(q1, q2, reward, next_q1, next_q2, next_log_pi, *, alpha=None, lo
         td     = |q1 - target|.mean(1)                                                           (B,), detached: update_priorities takes it
 
     ``done=None`` is 0 (the reference fetches ``dones`` and never applies them), ``weights=None`` is 1.  Nothing flows to ``next_*``,
-    ``reward``, ``weights`` or ``log_alpha``.  ``loss.backward()`` is one further launch."""
+    ``reward``, ``weights`` or ``log_alpha``.  ``loss.backward()`` is one further launch.
+
+    ``discount=`` ((B,) or (B, 1) fp32 on the device) takes the place of ``gamma`` sample by sample,
+
+        target = reward + (1 - done) discount_b (min(next_q1, next_q2) - alpha next_log_pi)
+
+    which is the n-step target when ``reward``, ``done`` and ``discount`` are ``rew``, ``done`` and ``discount`` = gamma^m of
+    ``DeviceReplayBuffer.sample(..., n_step=n)``.  With ``discount=`` the float ``gamma`` is not read."""
     what = "critic_loss"
     alpha_f, la = _temperature(alpha, log_alpha, what)
-    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma):
+    if discount is None and (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)):
         raise ValueError(f"{what}: gamma must be a finite float, got {gamma!r}")
     B, A = _matrix(q1, "q1", what)
     for name, t in (("q2", q2), ("next_q1", next_q1), ("next_q2", next_q2)):
         _matrix(t, name, what, (B, A))
-    for name, t in (("reward", reward), ("next_log_pi", next_log_pi), ("done", done), ("weights", weights)):
+    for name, t in (("reward", reward), ("next_log_pi", next_log_pi), ("done", done), ("weights", weights), ("discount", discount)):
         if t is not None or name in ("reward", "next_log_pi"):
             _column(t, name, what, B)
-    q1c, q2c, r, n1, n2, nlp, d, w, la = _on_device([("q1", q1), ("q2", q2), ("reward", reward), ("next_q1", next_q1), ("next_q2", next_q2),
-                                                     ("next_log_pi", next_log_pi), ("done", done), ("weights", weights), ("log_alpha", la)])
+    q1c, q2c, r, n1, n2, nlp, d, w, g, la = _on_device([("q1", q1), ("q2", q2), ("reward", reward), ("next_q1", next_q1), ("next_q2", next_q2),
+                                                        ("next_log_pi", next_log_pi), ("done", done), ("weights", weights),
+                                                        ("discount", discount), ("log_alpha", la)])
     need = torch.is_grad_enabled() and (q1.requires_grad or q2.requires_grad)
     dev = q1c.device
     target, td = torch.empty(B, A, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     grads = torch.empty(2 * B * A, dtype=torch.float32, device=dev) if need else None
     with torch.cuda.device(dev):
-        rc = _lib.load().dgvit_sac_critic_loss(_ptr(q1c), _ptr(q2c), _ptr(r), _ptr(d), _ptr(w), _ptr(n1), _ptr(n2), _ptr(nlp), _ptr(la),
-                                               alpha_f, float(gamma), _ptr(target), _ptr(td), _ptr(loss), _ptr(grads), B, A, _stream())
+        if g is None:
+            rc = _lib.load().dgvit_sac_critic_loss(_ptr(q1c), _ptr(q2c), _ptr(r), _ptr(d), _ptr(w), _ptr(n1), _ptr(n2), _ptr(nlp), _ptr(la),
+                                                   alpha_f, float(gamma), _ptr(target), _ptr(td), _ptr(loss), _ptr(grads), B, A, _stream())
+        else:
+            rc = _lib.load().dgvit_sac_critic_loss_v2(_ptr(q1c), _ptr(q2c), _ptr(r), _ptr(d), _ptr(w), _ptr(g), _ptr(n1), _ptr(n2), _ptr(nlp),
+                                                      _ptr(la), alpha_f, 0.0, _ptr(target), _ptr(td), _ptr(loss), _ptr(grads), B, A, _stream())
     _lib.check(rc, "dgvit_sac_critic_loss")
     value = loss.view(())
     if need:

@@ -414,6 +414,37 @@ int dgvit_gather_shift_frames_u8(const unsigned char* ring, const long long* idx
                                  void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * n-step returns at sample time (dgvit_amd.replay: sample(..., n_step=, gamma=)).  Consecutive ring slots are consecutive
+ * environment steps, so the multi-step target of cpprb's Nstep option is a walk along the ring.  What the walk may not cross is kept in
+ * one byte per slot, `flags` (nrows bytes on the device):
+ *   bit 0, END  (1): the slot's transition is the last of its episode, whatever its `done` says (time limits, truncations)
+ *   bit 1, HEAD (2): the slot is the newest one written; its ring successor is the oldest slot or an unwritten one
+ *
+ * dgvit_ring_mark:  after a store of n slots at `start`:  flags[(start + j) % nrows] = (j == n - 1 ? HEAD : 0)  for j < n, and the slot
+ *   before `start` loses HEAD and keeps END unless it was itself just written (n == nrows).  An overwritten slot forgets its marks; exactly
+ *   one slot carries HEAD.  One launch.  0 <= start < nrows, 1 <= n <= nrows.
+ * dgvit_nstep_walk: for each b < nsel, one wave:
+ *     i    = clamp(idx[b], 0, nrows-1),  s_k = (i + k) mod nrows
+ *     m    = the number of slots visited: the walk stops behind the first k with done[s_k] != 0 or flags[s_k] != 0, or after n slots
+ *     ret_out[b]      = (float) sum_{k<m} gamma^k rew[s_k]      summed in DOUBLE in ascending k, gamma^k the left-to-right product of k
+ *                                                               factors in double, rounded to fp32 once
+ *     discount_out[b] = (float) gamma^m
+ *     done_out[b]     = done[s_{m-1}],   tail_out[b] = s_{m-1} (int64),   steps_out[b] = m (int32)
+ *     next_small_out[b][:] = next_small[tail_out[b]][:]         rows of small_ld floats, a multiple of 4, copied as float4
+ *   rew and done are read at rew[s * rew_ld] and done[s * done_ld] (the first column of a (nrows, ld) matrix).  1 <= n <= 64,
+ *   0 <= gamma <= 1 (a double), 1 <= nsel < 2^31, small_ld <= 2^20; next_small and next_small_out 16-byte aligned.  Every slot index is
+ *   taken mod nrows, so no index can fault; no atomics: the result depends on the ring and idx[b] alone, not on b or nsel.  tail_out is an
+ *   index tensor for the frame gathers above (next_obs of the n-step transition).  Both calls are capturable and neither synchronises.
+ * -------------------------------------------------------------------------------------------- */
+#define DGVIT_RING_END 1
+#define DGVIT_RING_HEAD 2
+int dgvit_ring_mark(unsigned char* flags, long long nrows, long long start, long long n, void* stream);
+int dgvit_nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                     const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma,
+                     float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out, long long* tail_out,
+                     void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
  * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
  *
@@ -528,6 +559,9 @@ int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, 
  *     td[b]       = (1/A) sum_a |q1[b,a] - target[b,a]|            (NULL: not wanted; what a prioritized replay takes back)
  *     grads       = [dq1 | dq2], 2 B A floats, d loss / d q = 2 w (q - target) / (BA) for a unit upstream gradient (NULL: not wanted)
  *   target is a constant (the reference's no_grad): nothing is produced for next_*, reward, done, weights or log_alpha.
+ * dgvit_sac_critic_loss_v2: the same launch with a per-sample discount (B values, e.g. discount_out of dgvit_nstep_walk) in the place
+ *   of gamma:  target[b,a] = reward[b] + (1 - done[b]) discount[b] (min(next_q1, next_q2)[b,a] - alpha next_log_pi[b]).  With
+ *   discount != NULL the float gamma is not read; with discount == NULL the call IS dgvit_sac_critic_loss, bit for bit.
  * dgvit_sac_actor_loss:
  *     losses[0] = (1/BA) sum (alpha log_pi[b] - min(q1_pi, q2_pi)[b,a])                                        the policy loss
  *     grads     = [d log_pi (B) | dq1_pi (BA) | dq2_pi (BA)] (NULL: not wanted): d log_pi[b] = alpha / B; dq1_pi = -1/(BA) where
@@ -543,6 +577,10 @@ int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, 
 int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
                           const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
                           float gamma, float* target, float* td, float* loss, float* grads, int B, int A, void* stream);
+int dgvit_sac_critic_loss_v2(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
+                             const float* discount /* may be NULL */, const float* next_q1, const float* next_q2, const float* next_log_pi,
+                             const float* log_alpha, float alpha, float gamma, float* target, float* td, float* loss, float* grads, int B,
+                             int A, void* stream);
 int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha,
                          int with_temperature, float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A,
                          void* stream);
