@@ -152,6 +152,15 @@ SIGNATURES = {
     "dgvit_attention_backward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dgvit_attention_forward_bf16_tiled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_bf16_tiled": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    # transformer-internal dropout in the bf16 configuration (layer_keep after dropout_keep; the ops take keep, seed, seed_dev, layer)
+    "dgvit_got_forward_bf16_v2": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _P, _LL, _I, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_forward_maps_bf16_v2": (_I, [_CFG, _TABLE, _P, _P, _P, _P, _P, _I, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_bf16_v3": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P]),
+    "dgvit_got_backward_bf16_v3_ev": (_I, [_CFG, _TABLE, _P, _TABLE, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _F, _F, _ULL, _P, _P,
+                                           POINTER(dgvit_grad_events)]),
+    "dgvit_attention_forward_bf16_tiled_drop": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
+    "dgvit_attention_backward_bf16_tiled_drop": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
+    "dgvit_drop_rows_bf16": (_I, [_P, _LL, _P, _LL, _LL, _I, _I, _F, _ULL, _P, _I, _I, _P]),
     "dgvit_profile_start": (_I, [_I]),
     "dgvit_profile_stop": (_I, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_longlong)]),
     "dgvit_profile_sampling": (_I, [_I]),

@@ -25,7 +25,7 @@ LIB_DIAG = os.path.join(HERE, "libdgvit_hip_diag.so")   # the same sources with 
 SOURCES = ["gemm.hip", "gemm_reduce.hip", "norm.hip", "attention.hip", "attention_long.hip", "embed.hip", "conv.hip", "optim.hip", "sac_loss.hip", "replay.hip", "replay_ring.hip", "profile.hip", "preprocess.hip", "gemm_bf16.hip",
            "gemm_bf16_stream.hip", "attention_bf16.hip", "attention_bf16_long.hip", "attention_maps.hip", "last_block.hip", "misc_bf16.hip", "heads.hip", "block.hip", "api.hip", "encoder.hip", "encoder_bf16.hip", "cnn_api.hip"]
 DIAG_ONLY_SOURCES = ["frame.hip", "diag_api.hip"]    # experiments and the knob entry points: not part of the product library
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_tiles.h"), os.path.join(CSRC, "attention_bf16_tiles.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "bf16.h"), os.path.join(CSRC, "small_mma.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_tiles.h"), os.path.join(CSRC, "attention_bf16_tiles.h"), os.path.join(CSRC, "attention_bf16_dq_body.h"), os.path.join(CSRC, "attention_bf16_dkv_body.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "bf16.h"), os.path.join(CSRC, "small_mma.h"),
            os.path.join(CSRC, "knobs.h"), os.path.join(CSRC, "launch.h"), os.path.join(CSRC, "schedule.h"), os.path.join(CSRC, "gemm_tile.h"), os.path.join(CSRC, "gemm_pipe.h"), os.path.join(INCLUDE, "dgvit_hip.h"), os.path.join(INCLUDE, "dgvit_hip_diag.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-fvisibility=hidden", "-I", INCLUDE, "-Rpass-analysis=kernel-resource-usage"]

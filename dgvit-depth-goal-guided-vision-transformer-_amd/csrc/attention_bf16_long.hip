@@ -52,9 +52,11 @@ struct TileRegs {
 
 // ------------------------------------------------------------------------------------ forward
 // grid: (B * H) * ceil(nq / (32 NW)) workgroups, block index = item * nqb + query block
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                                      float* __restrict__ lse, int N, int H, float scale, int nq) {
+// DROP: the attention-dropout mask on the probabilities that feed P V (attn_key_tiles); l, m and the stored lse stay undropped.  The
+// mask row is the absolute query row, so nq = 1 draws the bits of the dense call's row 0.
+template <int NW, bool DROP>
+__device__ __forceinline__ void attn_fwd_bf16_tiled_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse, int N,
+                                                         int H, float scale, int nq, const LayerDrop& drop) {
   constexpr int DH = 64, LQ = 32 * NW, STAGE = 2 * TILE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -74,6 +76,9 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_kernel(const bf16
 
   bf16x8 qf[4];
   load_frags(qf, base + (long long)(q < nq ? q : 0) * ld, h);
+  RowDrop rd = {};
+  if constexpr (DROP)
+    rd = RowDrop{(((long long)b * H + hd) * N + (q < nq ? q : 0)) * ((N + 3) / 4), drop_seed(drop), drop.tag, drop.keep, 1.0f / drop.keep};
   TileRegs kr, vr;
   if (fetcher) {
     kr.fetch(base + I, ld, 0, N, tid);
@@ -100,8 +105,8 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_kernel(const bf16
     const unsigned char* Vs = Ks + TILE;
     if (active) {
       const int kt = 2 * t;
-      if (kt + 2 <= nkt) attn_key_tiles<2>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw, t * LK);
-      else attn_key_tiles<1>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw, t * LK);
+      if (kt + 2 <= nkt) attn_key_tiles<2, DROP>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw, t * LK, &rd);
+      else attn_key_tiles<1, DROP>(Ks, Vs, qf, m, l, o, sc, kt, nkt, N, li, h, lane, fsw, t * LK, &rd);
     }
     if (fetcher && t + 1 < ntile) {
       unsigned char* nxt = smem + ((t + 1) & 1) * STAGE;   // last read in trip t - 1, before the barrier that ended it
@@ -115,212 +120,59 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_kernel(const bf16
     if (lse && h == 0) lse[((long long)b * H + hd) * N + q] = m + __builtin_amdgcn_logf(l);   // base-2 log-sum-exp
   }
 }
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                                      float* __restrict__ lse, int N, int H, float scale, int nq) {
+  attn_fwd_bf16_tiled_body<NW, false>(qkv, out, lse, N, H, scale, nq, LayerDrop{});
+}
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_fwd_bf16_tiled_drop_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                                           float* __restrict__ lse, int N, int H, float scale, int nq,
+                                                                           const LayerDrop drop) {
+  attn_fwd_bf16_tiled_body<NW, true>(qkv, out, lse, N, H, scale, nq, drop);
+}
 
 // ------------------------------------------------------------------------------------ backward (1): dQ, delta
 // grid: (B * H) * ceil(N / (32 NW)) workgroups; the arithmetic per (query tile, key tile) is attn_bwd_dq_bf16_kernel's
+// DROP: dS = P o (mask / keep o dP - delta) scale; the register layout is the forward's (one Philox block per four registers), and
+// delta = rowsum(dO o O) needs no mask: O is the dropped output.
 template <int NW>
 __global__ void __launch_bounds__(64 * NW) attn_bwd_dq_bf16_tiled_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o_fwd,
                                                                          const bf16_t* __restrict__ d_out, const float* __restrict__ lse,
                                                                          bf16_t* __restrict__ dqkv, float* __restrict__ delta, int N,
                                                                          int H, float scale) {
-  constexpr int DH = 64, LQ = 32 * NW, STAGE = 2 * TILE + TILE_T;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int nqb = (N + LQ - 1) / LQ;
-  const int item = blockIdx.x / nqb, qb = blockIdx.x % nqb;
-  const int b = item / H, hd = item % H;
-  const int I = H * DH;
-  const long long ld = 3ll * I;
-  const bf16_t* base = qkv + (long long)b * N * ld + hd * DH;
-  const float sc = scale * DGVIT_LOG2E;
-  const int q = qb * LQ + wave * 32 + li, qc = q < N ? q : 0;
-  const bool active = qb * LQ + wave * 32 < N;
-  const bool fetcher = tid < FETCHERS;
-  const int nkt = (N + 31) / 32, ntile = (N + LK - 1) / LK;
-
-  bf16x8 qf[4], dof[4];
-  float dl = 0.f;
-  {
-    bf16x8 of[4];
-    load_frags(qf, base + qc * ld, h);
-    load_frags(dof, d_out + ((long long)b * N + qc) * I + hd * DH, h);
-    load_frags(of, o_fwd + ((long long)b * N + qc) * I + hd * DH, h);
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dl += (float)dof[s][j] * (float)of[s][j];
-    dl += __shfl_xor(dl, 32, 64);
-  }
-  const float lq = lse[((long long)b * H + hd) * N + qc];
-  if (active && q < N && h == 0) delta[((long long)b * H + hd) * N + q] = dl;
-
-  TileRegs kr, vr;
-  auto fetch = [&](int t) {
-    kr.fetch(base + I, ld, t * LK, N, tid);
-    vr.fetch(base + 2 * I, ld, t * LK, N, tid);
-  };
-  auto stash = [&](int t) {
-    unsigned char* st = smem + (t & 1) * STAGE;
-    kr.stash_rows<false>(st, tid);
-    vr.stash_rows<false>(st + TILE, tid);
-    kr.stash_transposed(reinterpret_cast<bf16_t*>(st + 2 * TILE), tid);
-  };
-  if (fetcher) {
-    fetch(0);
-    stash(0);
-  }
-  __syncthreads();
-
-  f32x16 dq[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    dq[0][r] = 0.f;
-    dq[1][r] = 0.f;
-  }
-#pragma unroll 1
-  for (int t = 0; t < ntile; ++t) {
-    if (fetcher && t + 1 < ntile) fetch(t + 1);
-    const unsigned char* Ks = smem + (t & 1) * STAGE;
-    const unsigned char* Vs = Ks + TILE;
-    const bf16_t* Kt = reinterpret_cast<const bf16_t*>(Ks + 2 * TILE);
-    if (active) {
-#pragma unroll 1
-      for (int sub = 0; sub < 2; ++sub) {
-        const int kt = 2 * t + sub;
-        if (kt >= nkt) break;   // wave-uniform: an odd last tile
-        f32x16 s0, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] = 0.f;
-          dp[r] = 0.f;
-        }
-        mfma_rows(s0, Ks, sub * 32, li, h, qf);
-        mfma_rows(dp, Vs, sub * 32, li, h, dof);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kt * 32 + acc_row(r, h);
-          const float pr = key < N ? __builtin_amdgcn_exp2f(s0[r] * sc - lq) : 0.f;
-          s0[r] = pr * (dp[r] - dl) * scale;   // dS^T
-        }
-        mfma_transposed(dq, Kt, VS, sub * 32, li, h, s0);
-      }
-    }
-    if (fetcher && t + 1 < ntile) stash(t + 1);
-    __syncthreads();
-  }
-  if (active && q < N) store_T_bf16(dq, dqkv + ((long long)b * N + q) * ld + hd * DH, h, 1.f);
+  constexpr bool DROP = false;
+  const LayerDrop drop = {};
+#include "attention_bf16_dq_body.h"
+}
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) attn_bwd_dq_bf16_tiled_drop_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o_fwd,
+                                                                              const bf16_t* __restrict__ d_out, const float* __restrict__ lse,
+                                                                              bf16_t* __restrict__ dqkv, float* __restrict__ delta, int N,
+                                                                              int H, float scale, const LayerDrop drop) {
+  constexpr bool DROP = true;
+#include "attention_bf16_dq_body.h"
 }
 
 // ------------------------------------------------------------------------------------ backward (2): dK, dV
 // grid: (B * H) * ceil(N / (32 NW)) workgroups; the arithmetic per (key tile, query tile) is attn_bwd_dkv_bf16_kernel's
+// DROP: dV += dO^T (P o mask / keep), dS as in the dQ kernel.  Here the key sits on the lane and the queries in the registers, so every
+// register is another mask row; the four lanes of a quad (keys 4j .. 4j+3) share the Philox blocks of four queries between them.
 template <int NW>
 __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bwd_dkv_bf16_tiled_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_out,
                                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                                           bf16_t* __restrict__ dqkv, int N, int H, float scale) {
-  constexpr int DH = 64, LQ = 32 * NW, STAGE = 2 * TILE + 2 * TILE_T + 2 * LK * 4;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int nkb = (N + LQ - 1) / LQ;
-  const int item = blockIdx.x / nkb, kb = blockIdx.x % nkb;
-  const int b = item / H, hd = item % H;
-  const int I = H * DH;
-  const long long ld = 3ll * I;
-  const bf16_t* base = qkv + (long long)b * N * ld + hd * DH;
-  const bf16_t* dob = d_out + (long long)b * N * I + hd * DH;
-  const float* lbase = lse + ((long long)b * H + hd) * N;
-  const float* dbase = delta + ((long long)b * H + hd) * N;
-  const float sc = scale * DGVIT_LOG2E;
-  const int key = kb * LQ + wave * 32 + li, kc = key < N ? key : 0;
-  const bool kvalid = key < N;
-  const bool active = kb * LQ + wave * 32 < N;   // wave-uniform: this wave's key tile holds a real key
-  const bool fetcher = tid < FETCHERS;
-  const int nqt = (N + 31) / 32, ntile = (N + LK - 1) / LK;
-
-  bf16x8 kf[4], vf[4];
-  load_frags(kf, base + I + kc * ld, h);
-  load_frags(vf, base + 2 * I + kc * ld, h);
-  // the row statistics of a query tile travel with its Q / dO rows: the first 64 threads load one each
-  TileRegs qr, dor;
-  float ls = 0.f, ds = 0.f;
-  auto fetch = [&](int t) {
-    qr.fetch(base, ld, t * LK, N, tid);
-    dor.fetch(dob, (long long)I, t * LK, N, tid);
-    if (tid < LK) {
-      const int r = t * LK + tid;
-      ls = r < N ? lbase[r] : 0.f;
-      ds = r < N ? dbase[r] : 0.f;
-    }
-  };
-  auto stash = [&](int t) {
-    unsigned char* st = smem + (t & 1) * STAGE;
-    qr.stash_rows<false>(st, tid);
-    dor.stash_rows<false>(st + TILE, tid);
-    qr.stash_transposed(reinterpret_cast<bf16_t*>(st + 2 * TILE), tid);
-    dor.stash_transposed(reinterpret_cast<bf16_t*>(st + 2 * TILE + TILE_T), tid);
-    if (tid < LK) {
-      float* stat = reinterpret_cast<float*>(st + 2 * TILE + 2 * TILE_T);
-      stat[tid] = ls;
-      stat[LK + tid] = ds;
-    }
-  };
-  if (fetcher) {
-    fetch(0);
-    stash(0);
-  }
-  __syncthreads();
-
-  f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f;
-  }
-#pragma unroll 1
-  for (int t = 0; t < ntile; ++t) {
-    if (fetcher && t + 1 < ntile) fetch(t + 1);
-    const unsigned char* Qs = smem + (t & 1) * STAGE;
-    const unsigned char* Os = Qs + TILE;                                     // dO rows
-    const bf16_t* Qt = reinterpret_cast<const bf16_t*>(Qs + 2 * TILE);
-    const bf16_t* Ot = reinterpret_cast<const bf16_t*>(Qs + 2 * TILE + TILE_T);   // dO transposed
-    const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * TILE + 2 * TILE_T);
-    const float* del_s = lse_s + LK;
-    if (active) {
-#pragma unroll 1
-      for (int sub = 0; sub < 2; ++sub) {
-        const int qt = 2 * t + sub;
-        if (qt >= nqt) break;   // wave-uniform: an odd last tile
-        f32x16 s0, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] = 0.f;
-          dp[r] = 0.f;
-        }
-        mfma_rows(s0, Qs, sub * 32, li, h, kf);     // S[query][key]: queries in the registers, key on the lane
-        mfma_rows(dp, Os, sub * 32, li, h, vf);     // dP = dO V^T
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int ql = sub * 32 + 8 * g + 4 * h, q0 = t * LK + ql;   // registers 4g .. 4g+3 hold queries q0 .. q0+3
-          const fx4 l4 = *reinterpret_cast<const fx4*>(lse_s + ql), d4 = *reinterpret_cast<const fx4*>(del_s + ql);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = 4 * g + i;
-            const float pr = (kvalid && q0 + i < N) ? __builtin_amdgcn_exp2f(s0[r] * sc - l4[i]) : 0.f;
-            s0[r] = pr;                                // P
-            dp[r] = pr * (dp[r] - d4[i]) * scale;      // dS
-          }
-        }
-        mfma_transposed(dv, Ot, VS, sub * 32, li, h, s0);   // dV^T += dO^T P
-        mfma_transposed(dk, Qt, VS, sub * 32, li, h, dp);   // dK^T += Q^T dS
-      }
-    }
-    if (fetcher && t + 1 < ntile) stash(t + 1);
-    __syncthreads();
-  }
-  if (active && kvalid) {
-    store_T_bf16(dk, dqkv + ((long long)b * N + key) * ld + I + hd * DH, h, 1.f);
-    store_T_bf16(dv, dqkv + ((long long)b * N + key) * ld + 2 * I + hd * DH, h, 1.f);
-  }
+  constexpr bool DROP = false;
+  const LayerDrop drop = {};
+#include "attention_bf16_dkv_body.h"
+}
+template <int NW>
+__global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) attn_bwd_dkv_bf16_tiled_drop_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_out,
+                                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                               bf16_t* __restrict__ dqkv, int N, int H, float scale,
+                                                                               const LayerDrop drop) {
+  constexpr bool DROP = true;
+#include "attention_bf16_dkv_body.h"
 }
 
 constexpr int LDS_FWD = 2 * (2 * TILE);                             // 32 KB
@@ -335,13 +187,16 @@ int tiled_grid(const char* what, int B, int H, int rows, int block, long long& g
 }
 
 template <int NW>
-int launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
+int launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, const LayerDrop* drop, hipStream_t st) {
   long long grid;
   TRY(tiled_grid("attention_fwd_bf16_tiled", B, H, nq, 32 * NW, grid));
   const float scale = 1.0f / sqrtf((float)dh);
   {
     ProfileScope t(PROF_ATTN_FWD, 4.0 * (double)nq * N * dh * H * B, st);
-    hipLaunchKernelGGL((attn_fwd_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_FWD, st, qkv, out, lse, N, H, scale, nq);
+    if (drop)
+      hipLaunchKernelGGL((attn_fwd_bf16_tiled_drop_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_FWD, st, qkv, out, lse, N, H, scale, nq, *drop);
+    else
+      hipLaunchKernelGGL((attn_fwd_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_FWD, st, qkv, out, lse, N, H, scale, nq);
   }
   DGVIT_CHECK_LAUNCH("attention_fwd_bf16_tiled");
   return DGVIT_OK;
@@ -349,11 +204,23 @@ int launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, 
 
 template <int NW>
 int launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B, int N, int H,
-               int dh, hipStream_t st) {
+               int dh, const LayerDrop* drop, hipStream_t st) {
   long long grid;
   TRY(tiled_grid("attention_bwd_bf16_tiled", B, H, N, 32 * NW, grid));
-  TRY(allow_dynamic_lds<attn_bwd_dkv_bf16_tiled_kernel<NW>>(LDS_DKV, "attention_bwd_bf16_tiled"));
   const float scale = 1.0f / sqrtf((float)dh);
+  if (drop) {
+    TRY(allow_dynamic_lds<attn_bwd_dkv_bf16_tiled_drop_kernel<NW>>(LDS_DKV, "attention_bwd_bf16_tiled_drop"));
+    {
+      ProfileScope t(PROF_ATTN_BWD, 10.0 * (double)N * N * dh * H * B, st);
+      hipLaunchKernelGGL((attn_bwd_dq_bf16_tiled_drop_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DQ, st, qkv, out, dout, lse, dqkv, delta,
+                         N, H, scale, *drop);
+      hipLaunchKernelGGL((attn_bwd_dkv_bf16_tiled_drop_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DKV, st, qkv, dout, lse,
+                         (const float*)delta, dqkv, N, H, scale, *drop);
+    }
+    DGVIT_CHECK_LAUNCH("attention_bwd_bf16_tiled_drop");
+    return DGVIT_OK;
+  }
+  TRY(allow_dynamic_lds<attn_bwd_dkv_bf16_tiled_kernel<NW>>(LDS_DKV, "attention_bwd_bf16_tiled"));
   {
     ProfileScope t(PROF_ATTN_BWD, 10.0 * (double)N * N * dh * H * B, st);   // 2.5 x forward
     hipLaunchKernelGGL((attn_bwd_dq_bf16_tiled_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), LDS_DQ, st, qkv, out, dout, lse, dqkv, delta, N, H,
@@ -367,23 +234,39 @@ int launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const f
 
 }  // namespace
 
-int attention_fwd_bf16_tiled(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
+namespace {
+int fwd_tiled(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, const LayerDrop* drop, hipStream_t st) {
   DGVIT_CHECK_ARG(N >= 1, "attention_fwd_bf16_tiled: tokens N=%d must be at least 1", N);
   DGVIT_CHECK_ARG(dh == 64, "attention_fwd_bf16_tiled: dim_head=%d unsupported (64)", dh);
   DGVIT_CHECK_ARG(nq >= 1 && nq <= N, "attention_fwd_bf16_tiled: query rows nq=%d outside [1, %d]", nq, N);
   DGVIT_CHECK_ARG(qkv && out, "attention_fwd_bf16_tiled: null pointer (qkv=%p, out=%p)", (const void*)qkv, (const void*)out);
   DGVIT_CHECK_ARG(B > 0 && H > 0, "attention_fwd_bf16_tiled: batch B=%d and heads H=%d must be positive", B, H);
 #ifdef DGVIT_DIAG
-  if (g_attn_bf16_tiled_waves == 8) return launch_fwd<8>(qkv, out, lse, B, N, H, dh, nq, st);
-  return launch_fwd<4>(qkv, out, lse, B, N, H, dh, nq, st);
+  if (g_attn_bf16_tiled_waves == 8) return launch_fwd<8>(qkv, out, lse, B, N, H, dh, nq, drop, st);
+  return launch_fwd<4>(qkv, out, lse, B, N, H, dh, nq, drop, st);
 #else
-  return launch_fwd<g_attn_bf16_tiled_waves>(qkv, out, lse, B, N, H, dh, nq, st);
+  return launch_fwd<g_attn_bf16_tiled_waves>(qkv, out, lse, B, N, H, dh, nq, drop, st);
 #endif
+}
+int check_drop(const char* what, const LayerDrop& drop) {
+  DGVIT_CHECK_ARG(drop.keep > 0.f && drop.keep <= 1.f, "%s: keep=%g must be in (0, 1]", what, (double)drop.keep);
+  return DGVIT_OK;
+}
+}  // namespace
+
+int attention_fwd_bf16_tiled(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st) {
+  return fwd_tiled(qkv, out, lse, B, N, H, dh, nq, nullptr, st);
+}
+int attention_fwd_bf16_tiled_drop(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, const LayerDrop& drop,
+                                  hipStream_t st) {
+  TRY(check_drop("attention_fwd_bf16_tiled_drop", drop));
+  return fwd_tiled(qkv, out, lse, B, N, H, dh, nq, drop.keep < 1.f ? &drop : nullptr, st);
 }
 
 // dqkv (B, N, 3I) bf16 = gradient of the attention core; delta: B*H*N floats of scratch (written in full: rowsum(dO o O) of every row)
-int attention_bwd_bf16_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,
-                             int N, int H, int dh, hipStream_t st) {
+namespace {
+int bwd_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B, int N, int H, int dh,
+              const LayerDrop* drop, hipStream_t st) {
   DGVIT_CHECK_ARG(N >= 1, "attention_bwd_bf16_tiled: tokens N=%d must be at least 1", N);
   DGVIT_CHECK_ARG(dh == 64, "attention_bwd_bf16_tiled: dim_head=%d unsupported (64)", dh);
   DGVIT_CHECK_ARG(qkv && out && dout && lse && dqkv && delta,
@@ -391,9 +274,20 @@ int attention_bwd_bf16_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t*
                   (const void*)out, (const void*)dout, (const void*)lse, (const void*)dqkv, (const void*)delta);
   DGVIT_CHECK_ARG(B > 0 && H > 0, "attention_bwd_bf16_tiled: batch B=%d and heads H=%d must be positive", B, H);
 #ifdef DGVIT_DIAG
-  if (g_attn_bf16_tiled_waves == 8) return launch_bwd<8>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, st);
-  return launch_bwd<4>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, st);
+  if (g_attn_bf16_tiled_waves == 8) return launch_bwd<8>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, drop, st);
+  return launch_bwd<4>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, drop, st);
 #else
-  return launch_bwd<g_attn_bf16_tiled_waves>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, st);
+  return launch_bwd<g_attn_bf16_tiled_waves>(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, drop, st);
 #endif
+}
+}  // namespace
+
+int attention_bwd_bf16_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,
+                             int N, int H, int dh, hipStream_t st) {
+  return bwd_tiled(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, nullptr, st);
+}
+int attention_bwd_bf16_tiled_drop(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta,
+                                  int B, int N, int H, int dh, const LayerDrop& drop, hipStream_t st) {
+  TRY(check_drop("attention_bwd_bf16_tiled_drop", drop));
+  return bwd_tiled(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, drop.keep < 1.f ? &drop : nullptr, st);
 }

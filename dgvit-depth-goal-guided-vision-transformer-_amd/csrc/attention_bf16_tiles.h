@@ -77,11 +77,28 @@ __device__ __forceinline__ void softmax_step(f32x16 (&s0)[NT], float& m, float& 
   l = l * alpha + ts;
 }
 
+// The attention-dropout mask (site 0 of the table in common.h) of one row of the (b, h, q, k) probabilities, as the K / V-tiled kernels
+// apply it: g0 = the float4 group of the row's key 0, ((b*H + h)*N + q) * ceil(N/4); group g0 + k/4 gives the keys k .. k+3.
+struct RowDrop {
+  long long g0;
+  unsigned long long seed;
+  uint32_t tag;
+  float keep, inv;
+  // the four factors (1/keep or 0) of keys 4 k4 .. 4 k4 + 3
+  __device__ __forceinline__ void factors(int k4, float (&f)[4]) const {
+    const uint4 r = drop_bits(g0 + k4, seed, tag);
+    f[0] = drop_factor(r.x, keep, inv); f[1] = drop_factor(r.y, keep, inv); f[2] = drop_factor(r.z, keep, inv); f[3] = drop_factor(r.w, keep, inv);
+  }
+};
+
 // NT (1 or 2) key tiles of one query tile: S^T = K Q^T (independent accumulator chains), the softmax step over all of them, O^T += V^T P^T.
 // The images start at key row0 (a multiple of 32; 0: the whole head is in LDS): key tile kt is at image row kt * 32 - row0.
-template <int NT>
+// DROP: the un-normalised probabilities are multiplied by mask / keep before they are rounded to bf16 (l and m stay undropped); registers
+// 4g .. 4g+3 hold four consecutive keys aligned to 4 (acc_row), so one Philox block covers them.  Straight-line code: EXEC stays all ones.
+template <int NT, bool DROP = false>
 __device__ __forceinline__ void attn_key_tiles(const unsigned char* Ks, const unsigned char* Vs, const bf16x8 (&qf)[4], float& m, float& l, f32x16 (&o)[2],
-                                               float sc, int kt, int nkt, int N, int li, int h, int lane, unsigned fsw, int row0 = 0) {
+                                               float sc, int kt, int nkt, int N, int li, int h, int lane, unsigned fsw, int row0 = 0,
+                                               const RowDrop* rd = nullptr) {
   f32x16 s0[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -95,6 +112,17 @@ __device__ __forceinline__ void attn_key_tiles(const unsigned char* Ks, const un
       s0[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[s], s0[t], 0, 0, 0);
     }
   softmax_step<NT>(s0, m, l, o, sc, kt, nkt, N, h);
+  if constexpr (DROP) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float f[4];
+        rd->factors((kt + t) * 8 + 2 * g + h, f);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s0[t][4 * g + i] *= f[i];
+      }
+  }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     bf16x8 pf[2];

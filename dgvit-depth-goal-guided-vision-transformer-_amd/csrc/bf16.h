@@ -124,4 +124,13 @@ int attention_bwd_bf16(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout,
 int attention_fwd_bf16_tiled(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, hipStream_t st);
 int attention_bwd_bf16_tiled(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B,
                              int N, int H, int dh, hipStream_t st);
+// ... with the site-0 mask of the table in common.h on the probabilities (drop.tag = drop_tag(layer, DROP_ATTN)); drop.keep == 1
+// launches the kernels above.  lse and delta are those of the undropped softmax and of the dropped output.
+int attention_fwd_bf16_tiled_drop(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, int H, int dh, int nq, const LayerDrop& drop,
+                                  hipStream_t st);
+int attention_bwd_bf16_tiled_drop(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta,
+                                  int B, int N, int H, int dh, const LayerDrop& drop, hipStream_t st);
+// misc_bf16.hip: sites 1 - 3 on a bf16 row block, dst = src o mask / keep (dst may be src); buffer row r is absolute token row r * rs
+int drop_rows_bf16(const bf16_t* src, long long lds, bf16_t* dst, long long ldd, long long rows, int width, int rs, const LayerDrop& drop,
+                   hipStream_t st);
 

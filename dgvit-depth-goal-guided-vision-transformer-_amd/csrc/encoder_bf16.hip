@@ -232,6 +232,12 @@ struct FwdB {
   hipStream_t st;
   float* maps = nullptr;   // attention maps (dgvit_got_forward_maps_bf16); null in every other call
   int maps_rows = DGVIT_MAPS_GOAL;
+  // transformer-internal dropout (the mask table of common.h): lkeep < 1 applies the four sites of every block
+  float lkeep = 1.f;
+  unsigned long long seed = 0;
+  const unsigned long long* seed_dev = nullptr;
+  bool ldrop() const { return lkeep < 1.f; }
+  LayerDrop site(int layer, int s) const { return LayerDrop{lkeep, drop_tag(layer, s), seed, seed_dev}; }
   float* f32(unsigned char* base, long long off) const { return save ? (float*)(base + off) : (float*)nullptr; }
 };
 
@@ -294,7 +300,9 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
     TRY(gemm_bf16(BEPI_BF16, q, st));
   }
   float* lse = f.maps ? (float*)(lb + w.lse) : f.f32(lb, w.lse);   // (the no-grad layout has the slot too)
-  if (d.tiled) TRY(attention_fwd_bf16_tiled(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
+  // with dropout every attention call takes the K / V-tiled kernels (any N): they carry the mask, the fused ones do not
+  if (f.ldrop()) TRY(attention_fwd_bf16_tiled_drop(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, f.site(i, DROP_ATTN), st));
+  else if (d.tiled) TRY(attention_fwd_bf16_tiled(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
   else TRY(attention_fwd_bf16(qkv, ao, lse, d.B, d.N, d.H, d.dh, last ? 1 : d.N, st));
   if (f.maps) {   // before the shared qkv / lse are overwritten by the next layer
     const long long per_head = f.maps_rows == DGVIT_MAPS_ALL ? (long long)d.N * d.N : d.N;
@@ -306,6 +314,7 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
     p.bias = lp[L_OUTB];
     TRY(gemm_bf16(BEPI_BF16, p, st));
   }
+  if (f.ldrop()) TRY(drop_rows_bf16(delta, (long long)rs * d.D, delta, (long long)rs * d.D, tok, d.D, rs, f.site(i, DROP_OUT), st));
   // xmid = x + to_out(..);  ln2 = LN2(xmid).  No-grad passes do not store xmid in the blocks that have a successor: the feed-forward
   // output goes to the (free again) attention-output buffer and both branch outputs join the stream in ONE pass below,
   // (x + d_attn) + d_ff in the order of the two-step schedule: identical results, 22 instead of 24 bytes per element and block
@@ -324,10 +333,13 @@ int layer_fwd_bf16(const FwdB& f, int i, float*& x) {
       TRY(gemm_bf16(BEPI_GELU_BF16, p, st));
     }
   }
+  if (f.ldrop()) TRY(drop_rows_bf16(a1, d.M, a1, d.M, tok, d.M, rs, f.site(i, DROP_HIDDEN), st));   // (the pre-activation h1 stays as it is)
   {
-    GemmBf16Params p = gpb(a1, d.M, lw + wp.fc2, d.M, joint ? ao : delta, rs * d.D, tok, d.D, d.M);
+    bf16_t* ff = joint ? ao : delta;
+    GemmBf16Params p = gpb(a1, d.M, lw + wp.fc2, d.M, ff, rs * d.D, tok, d.D, d.M);
     p.bias = lp[L_FC2B];
     TRY(gemm_bf16(BEPI_BF16, p, st));
+    if (f.ldrop()) TRY(drop_rows_bf16(ff, (long long)rs * d.D, ff, (long long)rs * d.D, tok, d.D, rs, f.site(i, DROP_FF), st));
   }
   // xo = xmid + ff(..), and the next block's LN1 of it
   if (joint) {
@@ -359,6 +371,8 @@ int got_forward_bf16(FwdB& f, const float* img, const float* goal, float* feat, 
   TRY(check_bf16_dims(d));
   DGVIT_CHECK_ARG(params && wpack && img && goal && feat && workspace, "dgvit_got_forward_bf16: null pointer");
   DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dropout_keep must be in (0, 1]");
+  DGVIT_CHECK_ARG(f.lkeep > 0.f && f.lkeep <= 1.f, "layer_keep=%g must be in (0, 1]", (double)f.lkeep);
+  f.seed = seed; f.seed_dev = seed_dev;
   f.w = make_wsb(d, save);
   f.wp = make_wp(d);
   if (ws_bytes < f.w.total) return dgvit_set_error(DGVIT_ERR_WORKSPACE, "bf16 forward workspace %lld < %lld bytes", ws_bytes, f.w.total);
@@ -371,18 +385,35 @@ int got_forward_bf16(FwdB& f, const float* img, const float* goal, float* feat, 
 }
 }  // namespace
 
+extern "C" int dgvit_got_forward_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                         const float* img, const float* goal, float* feat, void* workspace, long long ws_bytes,
+                                         int batch, int save, float keep, float layer_keep, unsigned long long seed,
+                                         const unsigned long long* seed_dev, void* stream) {
+  FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, save, (hipStream_t)stream};
+  f.lkeep = layer_keep;
+  return got_forward_bf16(f, img, goal, feat, workspace, ws_bytes, batch, keep, seed, seed_dev);
+}
+
 extern "C" int dgvit_got_forward_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
                                       const float* img, const float* goal, float* feat, void* workspace, long long ws_bytes,
                                       int batch, int save, float keep, unsigned long long seed,
                                       const unsigned long long* seed_dev, void* stream) {
-  FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, save, (hipStream_t)stream};
-  return got_forward_bf16(f, img, goal, feat, workspace, ws_bytes, batch, keep, seed, seed_dev);
+  return dgvit_got_forward_bf16_v2(cfg, params, wpack, img, goal, feat, workspace, ws_bytes, batch, save, keep, 1.f, seed, seed_dev, stream);
 }
 
 // the no-grad bf16 forward with each layer's attention probabilities (include/dgvit_hip.h: Attention maps)
 extern "C" int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
                                            const float* goal, float* feat, float* maps, int rows, void* workspace, long long ws_bytes, int batch,
                                            float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+  return dgvit_got_forward_maps_bf16_v2(cfg, params, wpack, img, goal, feat, maps, rows, workspace, ws_bytes, batch, keep, 1.f, seed, seed_dev,
+                                        stream);
+}
+
+// ... with the transformer-internal dropout: the maps are read from q, k and the undropped lse, so they are the probabilities before the mask
+extern "C" int dgvit_got_forward_maps_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
+                                              const float* goal, float* feat, float* maps, int rows, void* workspace, long long ws_bytes,
+                                              int batch, float keep, float layer_keep, unsigned long long seed,
+                                              const unsigned long long* seed_dev, void* stream) {
   Dims d;
   TRY(make_dims(cfg, batch, d));
   TRY(check_bf16_dims(d));
@@ -391,6 +422,7 @@ extern "C" int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float*
   FwdB f = {cfg, {}, {}, {}, params, wpack, (unsigned char*)workspace, 0, (hipStream_t)stream};
   f.maps = maps;
   f.maps_rows = rows;
+  f.lkeep = layer_keep;
   return got_forward_bf16(f, img, goal, feat, workspace, ws_bytes, batch, keep, seed, seed_dev);
 }
 
@@ -423,6 +455,24 @@ extern "C" int dgvit_got_backward_bf16_v2(const dgvit_config* cfg, const float* 
                                        keep, seed, seed_dev, stream, nullptr);
 }
 
+extern "C" int dgvit_got_backward_bf16_v2_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                             float* const* grads, const float* dfeat, float* dgoal, float* dimg, const float* img,
+                                             const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
+                                             float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream,
+                                             const dgvit_grad_events* events) {
+  return dgvit_got_backward_bf16_v3_ev(cfg, params, wpack, grads, dfeat, dgoal, dimg, img, workspace, ws_bytes, scratch, scratch_bytes, batch,
+                                       keep, 1.f, seed, seed_dev, stream, events);
+}
+
+extern "C" int dgvit_got_backward_bf16_v3(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+                                          float* const* grads, const float* dfeat, float* dgoal, float* dimg, const float* img,
+                                          const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
+                                          float keep, float layer_keep, unsigned long long seed, const unsigned long long* seed_dev,
+                                          void* stream) {
+  return dgvit_got_backward_bf16_v3_ev(cfg, params, wpack, grads, dfeat, dgoal, dimg, img, workspace, ws_bytes, scratch, scratch_bytes, batch,
+                                       keep, layer_keep, seed, seed_dev, stream, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------- backward
 namespace {
 
@@ -439,6 +489,12 @@ struct BwdB {
   unsigned char* sc;
   hipStream_t st;
   const dgvit_grad_events* events;
+  // transformer-internal dropout: the forward's keep and seed (nothing is stored: every mask is regenerated)
+  float lkeep;
+  unsigned long long seed;
+  const unsigned long long* seed_dev;
+  bool ldrop() const { return lkeep < 1.f; }
+  LayerDrop site(int layer, int s) const { return LayerDrop{lkeep, drop_tag(layer, s), seed, seed_dev}; }
   // dW (no x ni) and optionally db (no) from dY (T x no, row stride ldy) and X (T x ni, row stride ldx)
   int wgrad(const bf16_t* dY, int ldy, const bf16_t* X, int ldx, float* dW, float* db, int no, int ni) const {
     if (db) TRY(colsum_bf16(dY, ldy, db, (float*)(sc + s.part), (int)d.T, no, st));
@@ -477,13 +533,23 @@ int layer_bwd_bf16(const BwdB& b, int i) {
   const bf16_t* h1 = (const bf16_t*)(lb + w.h1);
   const bf16_t* a1 = (const bf16_t*)(lb + w.a1);
   const float* xmid = (const float*)(lb + w.xmid);
+  // With dropout the gradient of a branch OUTPUT (fc2, to_out) is dxh o mask / keep: a masked bf16 copy feeds the branch's weight- and
+  // data-gradient GEMMs, the residual path keeps dx.  The copy lives in dln, which is free at both points (it is written next by the
+  // data-gradient GEMM that follows the copy's last reader); everything runs on the one stream `st`, in order.
+  const bool ldrop = b.ldrop();
   // ---- feed-forward branch: xout = xmid + fc2(gelu(fc1(ln2)))        (dx / dxh = d xout)
-  TRY(b.wgrad(dxh, d.D, a1, d.M, lg[L_FC2W], lg[L_FC2B], d.D, d.M));
+  const bf16_t* dff = dxh;
+  if (ldrop) {
+    TRY(drop_rows_bf16(dxh, d.D, dln, d.D, T, d.D, 1, b.site(i, DROP_FF), st));
+    dff = dln;
+  }
+  TRY(b.wgrad(dff, d.D, a1, d.M, lg[L_FC2W], lg[L_FC2B], d.D, d.M));   // (a1 is the masked hidden: the forward dropped it in place)
   {
-    GemmBf16Params p = gpb(dxh, d.D, lw + wp.fc2T, d.D, dh1, d.M, T, d.M, d.D);   // dh1 = (dx W2) * gelu'(h1)
+    GemmBf16Params p = gpb(dff, d.D, lw + wp.fc2T, d.D, dh1, d.M, T, d.M, d.D);   // dh1 = (dx W2) * gelu'(h1)
     p.aux = h1; p.ldaux = d.M;
     TRY(gemm_bf16(BEPI_DGELU_BF16, p, st));
   }
+  if (ldrop) TRY(drop_rows_bf16(dh1, d.M, dh1, d.M, T, d.M, 1, b.site(i, DROP_HIDDEN), st));
   TRY(b.wgrad(dh1, d.M, ln2, d.D, lg[L_FC1W], lg[L_FC1B], d.M, d.D));
   {
     GemmBf16Params p = gpb(dh1, d.M, lw + wp.fc1T, d.M, dln, d.D, T, d.D, d.M);     // dln2 = dh1 W1
@@ -492,12 +558,20 @@ int layer_bwd_bf16(const BwdB& b, int i) {
   TRY(layernorm_bwd_bf16(dln, xmid, (const float*)(lb + w.mean2), (const float*)(lb + w.rstd2), lp[L_LN2W], dx, dx2, dxh, lg[L_LN2W],
                          lg[L_LN2B], part, T, d.D, 1, st));
   // ---- attention branch: xmid = xin + to_out(attn(to_qkv(ln1)))      (dx2 / dxh = d xmid)
-  TRY(b.wgrad(dxh, d.D, ao, d.I, lg[L_OUTW], lg[L_OUTB], d.D, d.I));
+  const bf16_t* dat = dxh;
+  if (ldrop) {
+    TRY(drop_rows_bf16(dxh, d.D, dln, d.D, T, d.D, 1, b.site(i, DROP_OUT), st));
+    dat = dln;
+  }
+  TRY(b.wgrad(dat, d.D, ao, d.I, lg[L_OUTW], lg[L_OUTB], d.D, d.I));
   {
-    GemmBf16Params p = gpb(dxh, d.D, lw + wp.outT, d.D, dao, d.I, T, d.I, d.D);     // dao = dxmid Wo
+    GemmBf16Params p = gpb(dat, d.D, lw + wp.outT, d.D, dao, d.I, T, d.I, d.D);     // dao = dxmid Wo
     TRY(gemm_bf16(BEPI_BF16, p, st));
   }
-  if (d.tiled) TRY(attention_bwd_bf16_tiled(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
+  if (ldrop)
+    TRY(attention_bwd_bf16_tiled_drop(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh,
+                                      b.site(i, DROP_ATTN), st));
+  else if (d.tiled) TRY(attention_bwd_bf16_tiled(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
   else TRY(attention_bwd_bf16(qkv, ao, dao, (const float*)(lb + w.lse), dqkv, (float*)(sc + s.delta), d.B, d.N, d.H, d.dh, st));
   TRY(b.wgrad(dqkv, 3 * d.I, ln1, d.D, lg[L_QKV], nullptr, 3 * d.I, d.D));
   {
@@ -513,13 +587,14 @@ int layer_bwd_bf16(const BwdB& b, int i) {
 }  // namespace
 
 
-extern "C" int dgvit_got_backward_bf16_v2_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
+extern "C" int dgvit_got_backward_bf16_v3_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack,
                                              float* const* grads, const float* dfeat, float* dgoal, float* dimg, const float* img,
                                              const void* workspace, long long ws_bytes, void* scratch, long long scratch_bytes, int batch,
-                                             float keep, unsigned long long seed, const unsigned long long* seed_dev, void* stream,
-                                             const dgvit_grad_events* events) {
+                                             float keep, float layer_keep, unsigned long long seed, const unsigned long long* seed_dev,
+                                             void* stream, const dgvit_grad_events* events) {
   hipStream_t st = (hipStream_t)stream;
-  BwdB b = {{}, {}, {}, {}, params, wpack, grads, (const unsigned char*)workspace, (unsigned char*)scratch, st, events};
+  BwdB b = {{}, {}, {}, {}, params, wpack, grads, (const unsigned char*)workspace, (unsigned char*)scratch, st, events, layer_keep, seed, seed_dev};
+  DGVIT_CHECK_ARG(layer_keep > 0.f && layer_keep <= 1.f, "layer_keep=%g must be in (0, 1]", (double)layer_keep);
   const Dims& d = b.d;
   TRY(make_dims(cfg, batch, b.d));
   TRY(check_bf16_dims(d));
@@ -600,4 +675,32 @@ extern "C" int dgvit_attention_backward_bf16_tiled(const unsigned short* qkv, co
                                                    const float* lse, unsigned short* dqkv, float* delta, int B, int N, int H, int dh,
                                                    void* stream) {
   return attention_bwd_bf16_tiled(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, (hipStream_t)stream);
+}
+namespace {
+int check_layer_site(const char* what, int layer, int site_lo, int site) {
+  DGVIT_CHECK_ARG(layer >= 0 && layer < (1 << 22), "%s: layer=%d outside [0, 2^22)", what, layer);
+  DGVIT_CHECK_ARG(site >= site_lo && site <= DROP_FF, "%s: site=%d outside [%d, 3]", what, site, site_lo);
+  return DGVIT_OK;
+}
+}  // namespace
+extern "C" int dgvit_attention_forward_bf16_tiled_drop(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh,
+                                                       int nq, float keep, unsigned long long seed, const unsigned long long* seed_dev,
+                                                       int layer, void* stream) {
+  TRY(check_layer_site("dgvit_attention_forward_bf16_tiled_drop", layer, DROP_ATTN, DROP_ATTN));
+  return attention_fwd_bf16_tiled_drop(qkv, out, lse, B, N, H, dh, nq, LayerDrop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev},
+                                       (hipStream_t)stream);
+}
+extern "C" int dgvit_attention_backward_bf16_tiled_drop(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout,
+                                                        const float* lse, unsigned short* dqkv, float* delta, int B, int N, int H, int dh,
+                                                        float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer,
+                                                        void* stream) {
+  TRY(check_layer_site("dgvit_attention_backward_bf16_tiled_drop", layer, DROP_ATTN, DROP_ATTN));
+  return attention_bwd_bf16_tiled_drop(qkv, out, dout, lse, dqkv, delta, B, N, H, dh, LayerDrop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev},
+                                       (hipStream_t)stream);
+}
+extern "C" int dgvit_drop_rows_bf16(const unsigned short* src, long long lds, unsigned short* dst, long long ldd, long long rows, int width,
+                                    int rs, float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer, int site,
+                                    void* stream) {
+  TRY(check_layer_site("dgvit_drop_rows_bf16", layer, DROP_OUT, site));
+  return drop_rows_bf16(src, lds, dst, ldd, rows, width, rs, LayerDrop{keep, drop_tag(layer, site), seed, seed_dev}, (hipStream_t)stream);
 }

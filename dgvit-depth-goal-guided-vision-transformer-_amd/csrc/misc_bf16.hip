@@ -201,7 +201,47 @@ __global__ void __launch_bounds__(256) residual_add_bf16_kernel(const float* __r
       *reinterpret_cast<const fx4*>(x + off) + __builtin_convertvector(*reinterpret_cast<const bf16x4*>(delta + off), fx4);
 }
 
+// transformer-internal dropout of a bf16 row block (sites 1 - 3 of the mask table in common.h): a thread takes one 16-byte access = eight
+// elements = two Philox groups; the factor is applied in fp32 before the rounding to bf16.  Buffer row r is absolute token row r * rs
+// (the token-0 rows of the pruned last block draw the bits of the dense block's rows b*N).  dst may be src.
+__global__ void __launch_bounds__(256) drop_rows_bf16_kernel(const bf16_t* src, long long lds, bf16_t* dst, long long ldd, long long total8,
+                                                             int row8, int rs, const LayerDrop drop) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total8) return;
+  const long long r = i / row8;
+  const int c = (int)(i - r * row8);
+  const unsigned long long seed = drop_seed(drop);
+  const long long i4 = 2 * (r * rs * row8 + c);
+  const uint4 ra = drop_bits(i4, seed, drop.tag), rb = drop_bits(i4 + 1, seed, drop.tag);
+  const float inv = 1.0f / drop.keep;
+  const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + r * lds + 8 * c);
+  const fx4 lo = {(float)v[0] * drop_factor(ra.x, drop.keep, inv), (float)v[1] * drop_factor(ra.y, drop.keep, inv),
+                  (float)v[2] * drop_factor(ra.z, drop.keep, inv), (float)v[3] * drop_factor(ra.w, drop.keep, inv)};
+  const fx4 hi = {(float)v[4] * drop_factor(rb.x, drop.keep, inv), (float)v[5] * drop_factor(rb.y, drop.keep, inv),
+                  (float)v[6] * drop_factor(rb.z, drop.keep, inv), (float)v[7] * drop_factor(rb.w, drop.keep, inv)};
+  // (whole-vector shuffle: see load8 below)
+  *reinterpret_cast<bf16x8*>(dst + r * ldd + 8 * c) =
+      __builtin_shufflevector(__builtin_convertvector(lo, bf16x4), __builtin_convertvector(hi, bf16x4), 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 }  // namespace
+
+int drop_rows_bf16(const bf16_t* src, long long lds, bf16_t* dst, long long ldd, long long rows, int width, int rs, const LayerDrop& drop,
+                   hipStream_t st) {
+  DGVIT_CHECK_ARG(src && dst && rows > 0 && width > 0 && rs >= 1, "drop_rows_bf16: null pointer or empty block (rows=%lld, width=%d, rs=%d)", rows, width, rs);
+  DGVIT_CHECK_ARG(width % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && lds >= width && ldd >= width && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
+                  "drop_rows_bf16: width=%d and the row strides %lld / %lld must be multiples of 8 elements, the strides >= width, the pointers 16-byte aligned",
+                  width, lds, ldd);
+  DGVIT_CHECK_ARG(drop.keep > 0.f && drop.keep <= 1.f, "drop_rows_bf16: keep=%g must be in (0, 1]", (double)drop.keep);
+  const long long total8 = rows * (width / 8);
+  DGVIT_CHECK_ARG((total8 + 255) / 256 < (1ll << 31), "drop_rows_bf16: too many elements");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, st);
+    hipLaunchKernelGGL(drop_rows_bf16_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, st, src, lds, dst, ldd, total8, width / 8, rs, drop);
+  }
+  DGVIT_CHECK_LAUNCH("drop_rows_bf16");
+  return DGVIT_OK;
+}
 
 int residual_add_bf16(const float* x, const bf16_t* delta, float* xout, int rows, int D, int rs, hipStream_t st) {
   DGVIT_CHECK_ARG(x && delta && xout && rows > 0 && D > 0 && D % 4 == 0, "residual_add_bf16: bad arguments");

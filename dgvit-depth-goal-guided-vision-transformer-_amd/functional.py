@@ -738,6 +738,78 @@ def op_attention_bwd_bf16_tiled(qkv, out, dout, lse, heads, dim_head=64, *, delt
     return dqkv
 
 
+def _drop_args(keep, seed, layer):
+    """(keep, host seed, device seed tensor or None, layer) as the *_drop entry points take them"""
+    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    return float(keep), (0 if seed_dev is not None else int(seed)), seed_dev, int(layer)
+
+
+def op_attention_bf16_tiled_drop(qkv, heads, keep, seed, layer, dim_head=64, nq=None, want_lse=False, *, out=None, lse=None):
+    """op_attention_bf16_tiled with the attention-dropout mask of ``layer`` (site 0 of the table in include/dgvit_hip.h) on the
+    probabilities that feed P V; ``seed``: an int, or a one-element int64 device tensor read at run time.  lse is the undropped
+    softmax's; keep = 1 is op_attention_bf16_tiled, bit for bit."""
+    lib = _lib.load()
+    qkv = _dev_bf16(qkv, "qkv")
+    B, N, W = qkv.shape
+    if W != 3 * heads * dim_head:
+        raise DgvitError(f"qkv last dim {W} != 3*{heads}*{dim_head}")
+    nq = N if nq is None else nq
+    out = torch.empty(B, N, heads * dim_head, dtype=torch.bfloat16, device=qkv.device) if out is None else _dev_bf16(out, "out")
+    if lse is None and want_lse:
+        lse = torch.empty(B, heads, N, dtype=torch.float32, device=qkv.device)
+    keep, seed_val, seed_dev, layer = _drop_args(keep, seed, layer)
+    with torch.cuda.device(qkv.device):
+        rc = lib.dgvit_attention_forward_bf16_tiled_drop(_ptr(qkv), _ptr(out), _ptr(lse), B, N, heads, dim_head, int(nq), keep, seed_val,
+                                                         _ptr(seed_dev), layer, _stream())
+    _lib.check(rc, "dgvit_attention_forward_bf16_tiled_drop")
+    return (out, lse) if want_lse else out
+
+
+def op_attention_bwd_bf16_tiled_drop(qkv, out, dout, lse, heads, keep, seed, layer, dim_head=64, *, delta=None):
+    """op_attention_bwd_bf16_tiled for a forward that ran op_attention_bf16_tiled_drop with the same keep, seed and layer (the mask is
+    regenerated: nothing is stored)."""
+    lib = _lib.load()
+    qkv, out, dout, lse = _dev_bf16(qkv, "qkv"), _dev_bf16(out, "out"), _dev_bf16(dout, "dout"), _dev(lse, "lse")
+    B, N, _ = qkv.shape
+    dqkv = torch.empty_like(qkv)
+    if delta is None:
+        delta = torch.empty(B * heads * N, dtype=torch.float32, device=qkv.device)
+    if delta.numel() < B * heads * N:
+        raise DgvitError(f"delta has {delta.numel()} floats, {B * heads * N} needed")
+    keep, seed_val, seed_dev, layer = _drop_args(keep, seed, layer)
+    with torch.cuda.device(qkv.device):
+        rc = lib.dgvit_attention_backward_bf16_tiled_drop(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _ptr(_dev(delta, "delta")),
+                                                          B, N, heads, dim_head, keep, seed_val, _ptr(seed_dev), layer, _stream())
+    _lib.check(rc, "dgvit_attention_backward_bf16_tiled_drop")
+    return dqkv
+
+
+def op_drop_rows_bf16(x, keep, seed, layer, site, rs=1, out=None):
+    """The bf16 row kernel of dropout sites 1 - 3: x (..., width) bf16, rows of stride x.stride(-2), -> x o mask / keep written to
+    ``out`` (default: in place, returned).  Row r of the flattened leading dimensions is absolute token row r * rs of the site's
+    (token row, width) tensor."""
+    lib = _lib.load()
+    if x.dtype != torch.bfloat16 or not x.is_cuda or x.dim() < 2 or x.stride(-1) != 1:
+        raise DgvitError("x: expected a bf16 tensor on a ROCm device with contiguous rows")
+    out = x if out is None else out
+    if out.dtype != torch.bfloat16 or out.device != x.device or out.shape != x.shape or out.stride(-1) != 1:
+        raise DgvitError("out: expected a bf16 tensor of x's shape on x's device with contiguous rows")
+    width = x.shape[-1]
+    rows = x.numel() // width
+    for t, name in ((x, "x"), (out, "out")):
+        lead = t.reshape(-1, width) if t.is_contiguous() else t
+        if lead.dim() != 2:
+            raise DgvitError(f"{name}: a strided tensor must be 2-D (rows, width)")
+    lds = x.stride(-2) if not x.is_contiguous() else width
+    ldd = out.stride(-2) if not out.is_contiguous() else width
+    keep, seed_val, seed_dev, layer = _drop_args(keep, seed, layer)
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_drop_rows_bf16(_ptr(x), lds, _ptr(out), ldd, rows, width, int(rs), keep, seed_val, _ptr(seed_dev), layer, int(site),
+                                      _stream())
+    _lib.check(rc, "dgvit_drop_rows_bf16")
+    return out
+
+
 class Bf16Weights:
     """bf16 copies of an encoder's GEMM weights in one arena (dgvit_got_pack_weights_bf16).
 
@@ -848,6 +920,7 @@ class _GoTEncoderBf16(torch.autograd.Function):
         cfg = dgvit_config(*cfg_tuple)
         img, goal, params = _encoder_inputs(cfg, img, goal, params)
         B = img.shape[0]
+        keep, lkeep = _keeps(keep)
         wpack = weights.get(cfg, params, with_transposes=bool(need_grad))
         nws = lib.dgvit_got_bf16_workspace_bytes(ctypes.byref(cfg), B, int(need_grad))
         if nws < 0:
@@ -857,11 +930,11 @@ class _GoTEncoderBf16(torch.autograd.Function):
         seed_dev = seed if isinstance(seed, torch.Tensor) else None
         seed_val = 0 if seed_dev is not None else int(seed)
         with torch.cuda.device(img.device):
-            rc = lib.dgvit_got_forward_bf16(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws),
-                                            nws, B, int(need_grad), float(keep), seed_val, _ptr(seed_dev), _stream())
+            rc = lib.dgvit_got_forward_bf16_v2(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws),
+                                               nws, B, int(need_grad), float(keep), lkeep, seed_val, _ptr(seed_dev), _stream())
         _lib.check(rc, "dgvit_got_forward_bf16")
         if need_grad:
-            ctx.cfg_tuple, ctx.keep, ctx.seed, ctx.batch = cfg_tuple, float(keep), seed_val, B
+            ctx.cfg_tuple, ctx.keep, ctx.lkeep, ctx.seed, ctx.batch = cfg_tuple, float(keep), lkeep, seed_val, B
             ctx.seed_dev, ctx.ws, ctx.wpack, ctx.img = seed_dev, ws, wpack, img
             ctx.grad_hook = grad_hook
             ctx.save_for_backward(*params)
@@ -883,9 +956,10 @@ class _GoTEncoderBf16(torch.autograd.Function):
         evs = _layer_events(dev, cfg.depth) if _wants_hook(ctx, grads) else None
         events, keep_alive = _grad_events(cfg.depth, evs) if evs else (None, None)
         with torch.cuda.device(dev):
-            rc = lib.dgvit_got_backward_bf16_v2_ev(ctypes.byref(cfg), _table(params), _ptr(ctx.wpack), _grad_table(grads), _ptr(dfeat),
+            rc = lib.dgvit_got_backward_bf16_v3_ev(ctypes.byref(cfg), _table(params), _ptr(ctx.wpack), _grad_table(grads), _ptr(dfeat),
                                                    _ptr(dgoal), _ptr(dimg), _ptr(ctx.img), _ptr(ws), ws.numel(), _ptr(scratch), nsc, B, ctx.keep,
-                                                   ctx.seed, _ptr(ctx.seed_dev), _stream(), ctypes.byref(events) if events is not None else None)
+                                                   ctx.lkeep, ctx.seed, _ptr(ctx.seed_dev), _stream(),
+                                                   ctypes.byref(events) if events is not None else None)
         _lib.check(rc, "dgvit_got_backward_bf16")
         ctx.ws = ctx.wpack = ctx.img = None
         if evs:
@@ -899,9 +973,22 @@ def _refuse_no_projection_bf16(params):
                                   "runs on the fp32 path only)")
 
 
-def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout_keep=1.0, dropout_seed=0, grad_hook=None):
-    """GoT.forward in the bf16 configuration (bf16 storage of GEMM operands, fp32 master parameters and gradients)."""
+def _layer_keep(layer_dropout_keep):
+    lkeep = float(layer_dropout_keep)
+    if not 0.0 < lkeep <= 1.0:
+        raise DgvitError(f"layer_dropout_keep={lkeep} must be in (0, 1]")
+    return lkeep
+
+
+def got_encoder_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, dropout_keep=1.0, dropout_seed=0, grad_hook=None,
+                     layer_dropout_keep=1.0):
+    """GoT.forward in the bf16 configuration (bf16 storage of GEMM operands, fp32 master parameters and gradients).
+    ``layer_dropout_keep``: 1 - the transformer ``dropout`` (train mode; 1 in eval mode), as in got_encoder: below 1 the masks of the
+    four transformer sites are drawn from ``dropout_seed`` -- the masks an fp32 model draws from the same seed -- and the attention
+    runs on the K / V-tiled bf16 kernels for every N."""
     _refuse_no_projection_bf16(params)
+    lkeep = _layer_keep(layer_dropout_keep)
+    dropout_keep = dropout_keep if lkeep == 1.0 else (float(dropout_keep), lkeep)
     if img.shape[0] == 0:
         return _empty_batch((0, int(cfg_tuple[4])), [img, goal, *params])
     need_grad = torch.is_grad_enabled() and (img.requires_grad or goal.requires_grad or any(p.requires_grad for p in params))
@@ -964,12 +1051,15 @@ def got_attention_maps(img, goal, cfg_tuple, params, rows="goal", dropout_keep=1
 
 
 @torch.no_grad()
-def got_attention_maps_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, rows="goal", dropout_keep=1.0, dropout_seed=0):
-    """got_attention_maps in the bf16 configuration (dgvit_got_forward_maps_bf16): the probabilities come from the bf16 q / k the
-    attention kernel reads, with fp32 scores, softmax and output; feat is got_encoder_bf16's result under no_grad."""
+def got_attention_maps_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, rows="goal", dropout_keep=1.0, dropout_seed=0,
+                            layer_dropout_keep=1.0):
+    """got_attention_maps in the bf16 configuration (dgvit_got_forward_maps_bf16_v2): the probabilities come from the bf16 q / k the
+    attention kernel reads, with fp32 scores, softmax and output -- before the attention-dropout site; feat is got_encoder_bf16's
+    result under no_grad for the same keeps and seed."""
     r = maps_rows(rows)
     cfg = dgvit_config(*cfg_tuple)
     _refuse_no_projection_bf16(params)
+    lkeep = _layer_keep(layer_dropout_keep)
     if img.shape[0] == 0:
         return _empty_maps(cfg, r, img, goal, params)
     lib = _lib.load()
@@ -984,8 +1074,8 @@ def got_attention_maps_bf16(img, goal, cfg_tuple, params, weights: Bf16Weights, 
     maps = torch.empty(_maps_shape(cfg, B, r), dtype=torch.float32, device=img.device)
     seed_val, seed_dev = _seed_args(dropout_seed)
     with torch.cuda.device(img.device):
-        rc = lib.dgvit_got_forward_maps_bf16(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(maps), r,
-                                             _ptr(ws), nws, B, float(dropout_keep), seed_val, _ptr(seed_dev), _stream())
+        rc = lib.dgvit_got_forward_maps_bf16_v2(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(maps), r,
+                                                _ptr(ws), nws, B, float(dropout_keep), lkeep, seed_val, _ptr(seed_dev), _stream())
     _lib.check(rc, "dgvit_got_forward_maps_bf16")
     return feat, maps
 

@@ -129,6 +129,7 @@ class GoT(nn.Module):
                      1 if pool == 'mean' else 0, 0)       # last entry: schedule flags (set_schedule)
         self.compute_dtype = torch.float32
         self._long_sequence_bf16 = False   # set_schedule(long_sequence_bf16=True): the long-sequence request covers bf16 too
+        self._dropout_bf16 = False         # set_schedule(dropout_bf16=True): transformer dropout > 0 is accepted in the bf16 configuration
         self._bf16_weights = F_.Bf16Weights()
         self._grad_hook = None     # set by parallel.GradSync(overlap=True): called inside the backward with the gradient-ready events
         self.register_load_state_dict_post_hook(_weights_loaded)
@@ -155,7 +156,7 @@ class GoT(nn.Module):
         return self
 
     def set_schedule(self, dense_last_block: bool = False, wgrad_overlap: bool = False, long_sequence: bool = False,
-                     long_sequence_bf16: bool = False):
+                     long_sequence_bf16: bool = False, dropout_bf16: bool = False):
         """Per-module schedule options, passed to the C ABI with every call (``dgvit_config.flags``; nothing global).
         ``dense_last_block``: run the whole last block instead of its token-0 rows only (identical results; A/B measurements).
         ``wgrad_overlap``: the backward runs the weight-gradient GEMMs on a helper stream beside the data-gradient chain
@@ -166,6 +167,12 @@ class GoT(nn.Module):
         ``long_sequence_bf16``: the same option for both compute dtypes -- on an fp32 model it is ``long_sequence=True``; on a bf16
         model (set before or after ``set_compute_dtype(torch.bfloat16)``) the attention of N > 288 tokens runs on the bf16 K / V-tiled
         kernels, forward, backward and ``attention_maps``; N <= 288 is unchanged, bit for bit, and no buffer size changes.
+        ``dropout_bf16``: accept a transformer ``dropout`` > 0 on a bf16 model (set before or after
+        ``set_compute_dtype(torch.bfloat16)``; without it the bf16 configuration refuses p > 0).  Train-mode forwards then draw the
+        masks of the four transformer sites from the forward's one Philox seed -- the masks an fp32 model draws from the same seed --
+        and every attention call runs on the bf16 K / V-tiled kernels, whatever N is (N > 288 still needs ``long_sequence_bf16``).
+        Eval mode and p = 0 are unchanged, bit for bit; no buffer size changes; a Python-side attribute (``dgvit_config.flags`` has no
+        bit for it) and a no-op on an fp32 model.
         Every option is reset by the next call that omits it."""
         from ._lib import FLAG_DENSE_LAST_BLOCK, FLAG_LONG_SEQUENCE, FLAG_WGRAD_OVERLAP
         if long_sequence and not long_sequence_bf16:
@@ -174,6 +181,7 @@ class GoT(nn.Module):
                  | (FLAG_LONG_SEQUENCE if long_sequence or long_sequence_bf16 else 0))
         self._cfg = (*self._cfg[:10], flags)
         self._long_sequence_bf16 = bool(long_sequence_bf16)
+        self._dropout_bf16 = bool(dropout_bf16)
         return self
 
     def long_sequence(self) -> bool:
@@ -194,13 +202,15 @@ class GoT(nn.Module):
         return float(ff[2].p)
 
     def _check_dropout_dtype(self, dtype):
-        if dtype == torch.bfloat16 and self.layer_dropout() > 0:
+        if dtype == torch.bfloat16 and self.layer_dropout() > 0 and not getattr(self, "_dropout_bf16", False):
             raise NotImplementedError(f"transformer dropout={self.layer_dropout()} is implemented on the fp32 path only; "
-                                      "the bf16 configuration needs dropout=0")
+                                      "the bf16 configuration needs dropout=0 unless it is asked for with "
+                                      "set_schedule(dropout_bf16=True)")
 
     def set_compute_dtype(self, dtype):
         """torch.float32 (default: exact fp32 MFMA path) or torch.bfloat16 (BASELINE config 5: bf16 storage for the GEMM
-        operands, fp32 residual stream / statistics / accumulation; parameters stay fp32 masters).  Transformer dropout > 0 is fp32 only."""
+        operands, fp32 residual stream / statistics / accumulation; parameters stay fp32 masters).  Transformer dropout > 0 is fp32 only
+        unless ``set_schedule(dropout_bf16=True)`` is in effect."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compute dtype {dtype} unsupported (torch.float32 or torch.bfloat16)")
         self._check_dropout_dtype(dtype)
@@ -242,7 +252,8 @@ class GoT(nn.Module):
         keep, seed, lkeep = self._dropout_args(img)
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:
-            return F_.got_encoder_bf16(img, goal, self._cfg, params, self._bf16_weights, keep, seed, grad_hook=self._grad_hook)
+            return F_.got_encoder_bf16(img, goal, self._cfg, params, self._bf16_weights, keep, seed, grad_hook=self._grad_hook,
+                                       layer_dropout_keep=lkeep)
         return F_.got_encoder(img, goal, self._cfg, params, keep, seed, grad_hook=self._grad_hook, layer_dropout_keep=lkeep)
 
     def attention_maps(self, img, goal, rows="goal"):
@@ -256,5 +267,5 @@ class GoT(nn.Module):
         keep, seed, lkeep = self._dropout_args(img)
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:
-            return F_.got_attention_maps_bf16(img, goal, self._cfg, params, self._bf16_weights, rows, keep, seed)
+            return F_.got_attention_maps_bf16(img, goal, self._cfg, params, self._bf16_weights, rows, keep, seed, layer_dropout_keep=lkeep)
         return F_.got_attention_maps(img, goal, self._cfg, params, rows, keep, seed, layer_dropout_keep=lkeep)

@@ -157,7 +157,7 @@ int dgvit_got_backward_ev(const dgvit_config* cfg, const float* const* params, f
  *   s = 2  FeedForward hidden (token row, mlp_dim), after GELU  i4 = (row*mlp_dim + c)/4
  *   s = 3  FeedForward output (token row, D), before the residual
  * row = b*N + t, the absolute token row.  Projection-less attention (heads == 1, dim_head == dim) has no site 1.  The bf16 entry points
- * do not take it.  Returns DGVIT_ERR_ARG when layer_dropout_keep is outside (0, 1]. */
+ * that take it are dgvit_got_forward_bf16_v2 and its companions below.  Returns DGVIT_ERR_ARG when layer_dropout_keep is outside (0, 1]. */
 int dgvit_got_forward_v2(const dgvit_config* cfg, const float* const* params, const float* img, const float* goal,
                          float* feat, float* workspace, long long workspace_floats, int batch, int save_for_backward,
                          float dropout_keep, float layer_dropout_keep, unsigned long long dropout_seed,
@@ -677,6 +677,51 @@ int dgvit_got_forward_maps_bf16(const dgvit_config* cfg, const float* const* par
 /* probabilities from bf16 qkv (dh 64) and the lse of dgvit_attention_forward_bf16; layouts as dgvit_attention_probs */
 int dgvit_attention_probs_bf16(const unsigned short* qkv, const float* lse, float* probs, int B, int N, int H, int dh, int rows,
                                void* stream);
+
+/* Transformer-internal dropout in the bf16 configuration: the entry points above with one more argument, layer_keep in (0, 1]
+ * (= 1 - GoT(dropout=p); 1.0f in eval mode), after dropout_keep.  The entry points above are these with layer_keep = 1: the same
+ * launches, the same bits.  Below 1 the masks of the table at dgvit_got_forward_v2 are applied -- the same counters, keep test and
+ * 1/keep scale (in fp32, before the rounding to bf16), so a bf16 and an fp32 model draw the same masks from one seed:
+ *   s = 0  on the un-normalised probabilities before they are rounded to bf16 for P V; every attention call then runs on the
+ *          K / V-tiled kernels, whatever N is (N > 288 still needs DGVIT_FLAG_LONG_SEQUENCE); lse stays the undropped one, so
+ *          the maps of dgvit_got_forward_maps_bf16_v2 are the probabilities before the dropout
+ *   s = 1, 3  on the bf16 branch output before it joins the fp32 residual stream;  s = 2  on the GELU output (the saved
+ *          pre-activation is left as it is)
+ * Nothing is stored; the backward regenerates every mask (pass it the forward's keeps and seed).  No buffer size changes: the
+ * masked copies of the branch-output gradients live in a buffer of the scratch that is free at that point.
+ * Returns DGVIT_ERR_ARG when layer_keep is outside (0, 1] (NaN included). */
+int dgvit_got_forward_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
+                              const float* goal, float* feat, void* workspace, long long workspace_bytes, int batch,
+                              int save_for_backward, float dropout_keep, float layer_keep, unsigned long long dropout_seed,
+                              const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_forward_maps_bf16_v2(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, const float* img,
+                                   const float* goal, float* feat, float* maps, int rows, void* workspace, long long workspace_bytes,
+                                   int batch, float dropout_keep, float layer_keep, unsigned long long dropout_seed,
+                                   const unsigned long long* dropout_seed_dev, void* stream);
+int dgvit_got_backward_bf16_v3(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, float* const* grads,
+                               const float* dfeat, float* dgoal, float* dimg, const float* img, const void* workspace,
+                               long long workspace_bytes, void* scratch, long long scratch_bytes, int batch, float dropout_keep,
+                               float layer_keep, unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev,
+                               void* stream);
+int dgvit_got_backward_bf16_v3_ev(const dgvit_config* cfg, const float* const* params, const unsigned short* wpack, float* const* grads,
+                                  const float* dfeat, float* dgoal, float* dimg, const float* img, const void* workspace,
+                                  long long workspace_bytes, void* scratch, long long scratch_bytes, int batch, float dropout_keep,
+                                  float layer_keep, unsigned long long dropout_seed, const unsigned long long* dropout_seed_dev,
+                                  void* stream, const dgvit_grad_events* events);
+/* operator level: the K / V-tiled bf16 attention with the site-0 mask of `layer` (keep in (0, 1]; 1 = the calls without _drop, bit
+ * for bit; seed_dev, if not NULL, overrides seed at run time), and the row kernel of sites 1 - 3: dst[r][c] = src[r][c] * mask / keep
+ * on `rows` rows of `width` bf16 elements (width, lds, ldd % 8 == 0, 16-byte aligned; dst may be src), buffer row r being the
+ * absolute token row r * rs of a (token row, width) tensor. */
+int dgvit_attention_forward_bf16_tiled_drop(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh,
+                                            int nq, float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer,
+                                            void* stream);
+int dgvit_attention_backward_bf16_tiled_drop(const unsigned short* qkv, const unsigned short* out, const unsigned short* dout,
+                                             const float* lse, unsigned short* dqkv, float* delta, int B, int N, int H, int dh,
+                                             float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer,
+                                             void* stream);
+int dgvit_drop_rows_bf16(const unsigned short* src, long long lds, unsigned short* dst, long long ldd, long long rows, int width,
+                         int rs, float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer, int site,
+                         void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Optional live kernel timing (HIP events on the launch stream around kernel launches).
