@@ -9,10 +9,11 @@ dimension explicit:
   * |got - ref| <= tol(K) * max(1, |f|) element-wise, tol(K) = 1e-4 * max(1, sqrt(K / 256)) (the bound test_gemm_epilogues already asserts,
     grown like the project's sqrt(K) accumulation bounds), f the multiplier of epilogues 2 and 7.  No relative term.
 
-Worst error / bound per class: NOT MEASURED on an MI355X yet - this file was added on 58772b7 without a GPU run (each test prints its
-figure; record the per-class maxima here with the commit of the first run).  What is known without a GPU, from
-tests/test_gemm_epilogue_matrix_host.py at that commit: a plain fp32 CPU evaluation of the same cases reaches 0.043 (vec), 0.047 (pad),
-0.061 (elem), 0.036 (scalar), 0.013 (tiny), 0.042 (split), 0.091 (split-wide) and 0.075 (TN) of the bound.
+Worst error / bound per class, kernels on an MI355X at 6ee6c33 (this file is unchanged since 58772b7): product library 0.0458 (vec),
+0.0465 (pad), 0.0513 (elem), 0.0357 (scalar), 0.0152 (tiny), 0.0311 (split), 0.0340 (split-wide), 0.0489 (TN); the sweep over the eight
+tiles 0.0458 (vec), 0.0456 (split).  For comparison, from tests/test_gemm_epilogue_matrix_host.py at 58772b7: a plain fp32 CPU
+evaluation of the same cases reaches 0.043 (vec), 0.047 (pad), 0.061 (elem), 0.036 (scalar), 0.013 (tiny), 0.042 (split), 0.091
+(split-wide) and 0.075 (TN) of the bound.
 """
 import functools
 
