@@ -38,7 +38,16 @@ class dgvit_grad_events(Structure):
     _fields_ = [("n_layers", c_int), ("layer", POINTER(c_void_p)), ("head", c_void_p)]
 
 
-GRAD_NORM_PARTIALS = 512    # include/dgvit_hip.h: DGVIT_GRAD_NORM_PARTIALS (doubles of scratch for dgvit_grad_sqnorm_partials)
+SMALL_FIELDS = 5            # include/dgvit_hip.h: DGVIT_SMALL_FIELDS
+
+
+class dgvit_small_fields(Structure):
+    """include/dgvit_hip.h: the five small fields of dgvit_ring_store_small, passed by value"""
+    _fields_ = [("src", c_void_p * SMALL_FIELDS), ("ring", c_void_p * SMALL_FIELDS), ("src_ld", c_longlong * SMALL_FIELDS),
+                ("cols", c_int * SMALL_FIELDS), ("ring_ld", c_int * SMALL_FIELDS)]
+
+
+GRAD_NORM_PARTIALS = 512   # include/dgvit_hip.h: DGVIT_GRAD_NORM_PARTIALS (doubles of scratch for dgvit_grad_sqnorm_partials)
 NUM_GLOBAL_PARAMS = 4
 PARAMS_PER_LAYER = 11
 ABI_VERSION = 7
@@ -106,6 +115,10 @@ SIGNATURES = {
     "dgvit_gather_shift_frames_u8": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _LL, _I, _I, _ULL, _P, _P]),
     "dgvit_ring_mark": (_I, [_P, _LL, _LL, _LL, _P]),
     "dgvit_nstep_walk": (_I, [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _LL, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
+    # the ring of E parallel environments (include/dgvit_hip.h: The ring of E parallel environments)
+    "dgvit_ring_store_frames": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _P, _I, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_ring_store_small": (_I, [dgvit_small_fields, _P, _P, _I, _LL, _LL, _LL, _P]),
+    "dgvit_nstep_walk_strided": (_I, [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _LL, _LL, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "dgvit_per_tree_floats": (_LL, [_LL]),
     "dgvit_per_init": (_I, [_P, _LL, _P]),
     "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),

@@ -299,6 +299,24 @@ extern "C" int dgvit_nstep_walk(const float* rew, long long rew_ld, const float*
   return nstep_walk(rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, n, gamma, ret_out, done_out, discount_out,
                     next_small_out, steps_out, tail_out, (hipStream_t)stream);
 }
+// the ring of E parallel environments (replay_ring.hip)
+extern "C" int dgvit_ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld,
+                                       void* ring0, void* ring1, int ring_u8, long long ring_ld, long long n, long long cols,
+                                       long long nrows, long long start, void* stream) {
+  return ring_store_frames(src0, src0_u8, src0_ld, src1, src1_u8, src1_ld, ring0, ring1, ring_u8, ring_ld, n, cols, nrows, start,
+                           (hipStream_t)stream);
+}
+extern "C" int dgvit_ring_store_small(dgvit_small_fields fields, unsigned char* flags, const void* episode_end, int end_f32, long long n,
+                                      long long nrows, long long start, void* stream) {
+  return ring_store_small(fields, flags, episode_end, end_f32, n, nrows, start, (hipStream_t)stream);
+}
+extern "C" int dgvit_nstep_walk_strided(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                                        const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows,
+                                        long long stride, int n, double gamma, float* ret_out, float* done_out, float* discount_out,
+                                        float* next_small_out, int* steps_out, long long* tail_out, void* stream) {
+  return nstep_walk_strided(rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, stride, n, gamma, ret_out, done_out,
+                            discount_out, next_small_out, steps_out, tail_out, (hipStream_t)stream);
+}
 // prioritized replay (replay.hip)
 extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }
 extern "C" int dgvit_per_init(float* tree, long long capacity, void* stream) { return per_init(tree, capacity, (hipStream_t)stream); }

@@ -90,6 +90,16 @@ int ring_mark(unsigned char* flags, long long nrows, long long start, long long 
 int nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags, const float* next_small,
                long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma, float* ret_out, float* done_out,
                float* discount_out, float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream);
+// the ring of E parallel environments: the store path that reads device memory only, and the walk with a stride
+int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
+                      void* ring1, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
+                      hipStream_t stream);
+int ring_store_small(const dgvit_small_fields& fields, unsigned char* flags, const void* episode_end, int end_f32, long long n,
+                     long long nrows, long long start, hipStream_t stream);
+int nstep_walk_strided(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                       const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, long long stride,
+                       int n, double gamma, float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out,
+                       long long* tail_out, hipStream_t stream);
 // replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
 long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
 int per_init(float* tree, long long capacity, hipStream_t stream);

@@ -9,6 +9,9 @@
 //   ring_mark               : the per-slot episode flags after a store: the written slots forget their marks, the newest one is the HEAD
 //   nstep_walk              : the n-step return of each sampled slot: a walk along the ring that stops at done, at a flag or after n slots,
 //                             one wave per sample, the rewards summed in double in ascending order
+//   ring_store_frames       : both frame fields of one vector step of E environments from device memory, fp32 or uint8 source, either ring
+//   ring_store_small        : its five small fields and its marks (HEAD | END per environment) in one launch
+//   nstep_walk_strided      : nstep_walk along one environment's slots, (i + k E) mod nrows
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
 // the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
@@ -172,22 +175,13 @@ __global__ void __launch_bounds__(256) ring_mark_kernel(unsigned char* __restric
 // the walk is one memory round trip; the ballot of the stop predicate gives m, the slots visited; the sum runs over lanes < m in ascending
 // order in double, every lane the same arithmetic; then the lanes copy the next_small row of the last slot.  Every slot index is reduced
 // mod nrows and i is clamped: nothing here can address outside the ring.  No atomics: the result is a function of the ring and idx[b].
-__global__ void __launch_bounds__(256) nstep_walk_kernel(const float* __restrict__ rew, long long rew_ld, const float* __restrict__ done,
-                                                         long long done_ld, const unsigned char* __restrict__ flags,
-                                                         const float4* __restrict__ next_small, int small4, const long long* __restrict__ idx,
-                                                         long long nsel, long long nrows, int n, double gamma, float* __restrict__ ret_out,
-                                                         float* __restrict__ done_out, float* __restrict__ discount_out,
-                                                         float4* __restrict__ next_small_out, int* __restrict__ steps_out,
-                                                         long long* __restrict__ tail_out) {
-  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (w >= nsel) return;       // wave-uniform
-  long long s = ring_row(idx[w], nrows) + lane;
-  if (nrows >= NSTEP_MAX) {    // s < 2 nrows: one subtraction wraps the ring
-    if (s >= nrows) s -= nrows;
-  } else {
-    s = (long long)((unsigned)s % (unsigned)nrows);   // a ring shorter than the walk: s < 128
-  }
+// the walk of wave w once lane k knows its slot s = s_k < nrows: shared by the two kernels below, which differ in s_k alone
+__device__ __forceinline__ void nstep_walk_from(long long s, long long w, int lane, const float* __restrict__ rew, long long rew_ld,
+                                                const float* __restrict__ done, long long done_ld, const unsigned char* __restrict__ flags,
+                                                const float4* __restrict__ next_small, int small4, int n, double gamma,
+                                                float* __restrict__ ret_out, float* __restrict__ done_out, float* __restrict__ discount_out,
+                                                float4* __restrict__ next_small_out, int* __restrict__ steps_out,
+                                                long long* __restrict__ tail_out) {
   const bool active = lane < n;
   const float r = active ? rew[s * rew_ld] : 0.f;
   const float d = active ? done[s * done_ld] : 0.f;
@@ -209,6 +203,149 @@ __global__ void __launch_bounds__(256) nstep_walk_kernel(const float* __restrict
     tail_out[w] = tail;
   }
   for (int c = lane; c < small4; c += 64) next_small_out[w * small4 + c] = next_small[tail * small4 + c];
+}
+
+__global__ void __launch_bounds__(256) nstep_walk_kernel(const float* __restrict__ rew, long long rew_ld, const float* __restrict__ done,
+                                                         long long done_ld, const unsigned char* __restrict__ flags,
+                                                         const float4* __restrict__ next_small, int small4, const long long* __restrict__ idx,
+                                                         long long nsel, long long nrows, int n, double gamma, float* __restrict__ ret_out,
+                                                         float* __restrict__ done_out, float* __restrict__ discount_out,
+                                                         float4* __restrict__ next_small_out, int* __restrict__ steps_out,
+                                                         long long* __restrict__ tail_out) {
+  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (w >= nsel) return;       // wave-uniform
+  long long s = ring_row(idx[w], nrows) + lane;
+  if (nrows >= NSTEP_MAX) {    // s < 2 nrows: one subtraction wraps the ring
+    if (s >= nrows) s -= nrows;
+  } else {
+    s = (long long)((unsigned)s % (unsigned)nrows);   // a ring shorter than the walk: s < 128
+  }
+  nstep_walk_from(s, w, lane, rew, rew_ld, done, done_ld, flags, next_small, small4, n, gamma, ret_out, done_out, discount_out, next_small_out,
+                  steps_out, tail_out);
+}
+
+// The walk in a ring of `stride` parallel environments: s_k = (i + k * stride) mod nrows.  i < nrows and k * stride <=
+// 63 * stride, so where 63 * stride <= nrows (wave-uniform: a ring of at least 63 steps) one subtraction wraps; a shorter ring, down to
+// nrows == stride where every lane visits slot i, takes the 64-bit remainder.  stride == 1 gives nstep_walk_kernel's slots.
+__global__ void __launch_bounds__(256) nstep_walk_strided_kernel(const float* __restrict__ rew, long long rew_ld,
+                                                                 const float* __restrict__ done, long long done_ld,
+                                                                 const unsigned char* __restrict__ flags,
+                                                                 const float4* __restrict__ next_small, int small4,
+                                                                 const long long* __restrict__ idx, long long nsel, long long nrows,
+                                                                 long long stride, int n, double gamma, float* __restrict__ ret_out,
+                                                                 float* __restrict__ done_out, float* __restrict__ discount_out,
+                                                                 float4* __restrict__ next_small_out, int* __restrict__ steps_out,
+                                                                 long long* __restrict__ tail_out) {
+  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (w >= nsel) return;       // wave-uniform
+  long long s = ring_row(idx[w], nrows) + lane * stride;   // stride <= nrows < 2^56 (launcher): no overflow
+  if ((NSTEP_MAX - 1) * stride <= nrows) {
+    if (s >= nrows) s -= nrows;
+  } else {
+    s = (long long)((unsigned long long)s % (unsigned long long)nrows);
+  }
+  nstep_walk_from(s, w, lane, rew, rew_ld, done, done_ld, flags, next_small, small4, n, gamma, ret_out, done_out, discount_out, next_small_out,
+                  steps_out, tail_out);
+}
+
+// One frame field of ring_store_frames: where its rows come from.  vec: whole groups may be read at once (16-byte aligned fp32 rows,
+// 4-byte aligned uint8 rows); otherwise element by element.
+struct frame_src {
+  const void* p;
+  long long ld;   // elements between rows
+  int u8, vec;
+};
+
+// Both frame fields of a vector step in one launch: blockIdx.y is the field, so its source, element type and alignment are
+// wave-uniform; thread = one group of 4 pixels of a ring row, a float4 of an fp32 ring or a dword of a byte ring.  Pixels at or beyond
+// `cols` are never read and are written as zeros (q(0) = 0).  start + r wraps as in quantize_rows_u8_kernel.
+template <bool RING_U8>
+__global__ void __launch_bounds__(256) ring_store_frames_kernel(frame_src s0, frame_src s1, void* __restrict__ ring0, void* __restrict__ ring1,
+                                                                long long total4, int row4, int cols, long long nrows, long long start) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const frame_src s = blockIdx.y == 0 ? s0 : s1;
+  void* __restrict__ ring = blockIdx.y == 0 ? ring0 : ring1;
+  const long long r = i / row4;
+  const int c = (int)(i - r * row4), p0 = 4 * c;
+  long long d = start + r;      // start < nrows and r < n <= nrows: one subtraction wraps the ring
+  if (d >= nrows) d -= nrows;
+  const bool whole = s.vec && p0 + 4 <= cols;
+  if (RING_U8 && s.u8) {        // codes as they are
+    const unsigned char* __restrict__ b = static_cast<const unsigned char*>(s.p) + r * s.ld + p0;
+    uint32_t w = 0;
+    if (whole) {
+      w = *reinterpret_cast<const uint32_t*>(b);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (p0 + e < cols) w |= (uint32_t)b[e] << (8 * e);
+    }
+    static_cast<uint32_t*>(ring)[d * row4 + c] = w;
+    return;
+  }
+  const float* __restrict__ f = static_cast<const float*>(s.p) + r * s.ld + p0;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (whole) {
+    const float4 t = *reinterpret_cast<const float4*>(f);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (p0 + e < cols) v[e] = f[e];
+  }
+  if (RING_U8)
+    static_cast<uint32_t*>(ring)[d * row4 + c] = quant_u8(v[0]) | (quant_u8(v[1]) << 8) | (quant_u8(v[2]) << 16) | (quant_u8(v[3]) << 24);
+  else
+    static_cast<float4*>(ring)[d * row4 + c] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// The five small fields of a vector step and its marks in one launch.  Threads 0 .. n * tot4 - 1: one float4 of a ring row each, the
+// fields' rows side by side (tot4 = sum of ring_ld[f] / 4; the loop over the fields is unrolled, so the by-value struct is never indexed
+// with a register).  With flags, threads n * tot4 + j: j < n marks written slot j, n <= j < 2n takes HEAD from slot j - n of the step
+// before -- other slots than the written ones, since n divides nrows and n < nrows there.  Sources are read element by element: a
+// (n, 2) tensor has 8-byte rows.
+__global__ void __launch_bounds__(256) ring_store_small_kernel(dgvit_small_fields p, int tot4, unsigned char* __restrict__ flags,
+                                                               const void* __restrict__ episode_end, int end_f32, long long n,
+                                                               long long nrows, long long start) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long cells = n * tot4;
+  if (i < cells) {
+    const long long r = i / tot4;
+    int j = (int)(i - r * tot4);
+    long long d = start + r;
+    if (d >= nrows) d -= nrows;
+#pragma unroll
+    for (int f = 0; f < DGVIT_SMALL_FIELDS; ++f) {
+      const int w4 = p.ring_ld[f] >> 2;
+      if (j >= 0 && j < w4) {
+        const float* __restrict__ s = p.src[f] + r * p.src_ld[f] + 4 * j;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (4 * j + e < p.cols[f]) v[e] = s[e];
+        reinterpret_cast<float4*>(p.ring[f])[d * w4 + j] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+      j -= w4;
+    }
+    return;
+  }
+  if (!flags) return;
+  const long long j = i - cells;
+  if (j < n) {
+    long long d = start + j;
+    if (d >= nrows) d -= nrows;
+    bool end = false;
+    if (episode_end)
+      end = end_f32 ? static_cast<const float*>(episode_end)[j] != 0.f : static_cast<const unsigned char*>(episode_end)[j] != 0;
+    flags[d] = RING_HEAD | (end ? RING_END : 0);
+  } else if (j < 2 * n && n < nrows) {
+    long long d = start - 2 * n + j;    // start - n + (j - n) > -nrows
+    if (d < 0) d += nrows;
+    flags[d] &= RING_END;
+  }
 }
 
 // both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
@@ -342,5 +479,94 @@ int nstep_walk(const float* rew, long long rew_ld, const float* done, long long 
                      reinterpret_cast<const float4*>(next_small), (int)(small_ld / 4), idx, nsel, nrows, n, gamma, ret_out, done_out,
                      discount_out, reinterpret_cast<float4*>(next_small_out), steps_out, tail_out);
   DGVIT_CHECK_LAUNCH("nstep_walk");
+  return DGVIT_OK;
+}
+
+int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
+                      void* ring1, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
+                      hipStream_t stream) {
+  DGVIT_CHECK_ARG(src0 && src1 && ring0 && ring1, "ring_store_frames: src0, src1, ring0 and ring1 must not be null");
+  DGVIT_CHECK_ARG((src0_u8 | src1_u8 | ring_u8) >> 1 == 0, "ring_store_frames: src0_u8=%d, src1_u8=%d and ring_u8=%d must be 0 or 1", src0_u8,
+                  src1_u8, ring_u8);
+  DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "ring_store_frames: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring", src0_u8,
+                  src1_u8);
+  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows, "ring_store_frames: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_store_frames: cols=%lld must be in [1, 2^25]", cols);
+  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
+                  "ring_store_frames: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring_ld, ring_u8 ? 16 : 4,
+                  cols);
+  DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "ring_store_frames: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld", src0_ld,
+                  src1_ld, cols);
+  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_store_frames: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  DGVIT_CHECK_ARG(al16(ring0) && al16(ring1) && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)),
+                  "ring_store_frames: the rings must be 16-byte and fp32 sources 4-byte aligned");
+  const int row4 = (int)(ring_ld / 4);   // groups of 4 pixels per ring row, a dword of bytes or a float4
+  const long long total4 = n * row4, blocks = (total4 + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_store_frames: n=%lld rows of ring_ld=%lld are more than one launch covers", n, ring_ld);
+  const auto source = [](const void* p, int u8, long long ld) {
+    const bool vec = u8 ? (ld % 4 == 0 && al4p(p)) : (ld % 4 == 0 && al16(p));
+    return frame_src{p, ld, u8, (int)vec};
+  };
+  const frame_src s0 = source(src0, src0_u8, src0_ld), s1 = source(src1, src1_u8, src1_ld);
+  if (ring_u8)
+    hipLaunchKernelGGL(ring_store_frames_kernel<true>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, ring0, ring1, total4, row4,
+                       (int)cols, nrows, start);
+  else
+    hipLaunchKernelGGL(ring_store_frames_kernel<false>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, ring0, ring1, total4, row4,
+                       (int)cols, nrows, start);
+  DGVIT_CHECK_LAUNCH("ring_store_frames");
+  return DGVIT_OK;
+}
+
+int ring_store_small(const dgvit_small_fields& fields, unsigned char* flags, const void* episode_end, int end_f32, long long n,
+                     long long nrows, long long start, hipStream_t stream) {
+  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows && nrows % n == 0,
+                  "ring_store_small: n=%lld must be in [1, nrows] and divide nrows=%lld, which must be positive", n, nrows);
+  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_store_small: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  DGVIT_CHECK_ARG(end_f32 == 0 || end_f32 == 1, "ring_store_small: end_f32=%d must be 0 or 1", end_f32);
+  DGVIT_CHECK_ARG(!episode_end || flags, "ring_store_small: episode_end without flags: the flags must not be null when ends are given");
+  DGVIT_CHECK_ARG(!episode_end || !end_f32 || al4p(episode_end), "ring_store_small: an fp32 episode_end must be 4-byte aligned");
+  long long tot4 = 0;
+  for (int f = 0; f < DGVIT_SMALL_FIELDS; ++f) {
+    DGVIT_CHECK_ARG(fields.src[f] && fields.ring[f], "ring_store_small: src[%d] and ring[%d] must not be null", f, f);
+    DGVIT_CHECK_ARG(fields.cols[f] >= 1 && fields.ring_ld[f] % 4 == 0 && fields.ring_ld[f] >= fields.cols[f] && fields.ring_ld[f] <= (1 << 20),
+                    "ring_store_small: cols[%d]=%d must be at least 1 and ring_ld[%d]=%d a multiple of 4, at least cols and at most 2^20", f,
+                    fields.cols[f], f, fields.ring_ld[f]);
+    DGVIT_CHECK_ARG(fields.src_ld[f] >= fields.cols[f], "ring_store_small: src_ld[%d]=%lld must be at least cols[%d]=%d", f, fields.src_ld[f], f,
+                    fields.cols[f]);
+    DGVIT_CHECK_ARG(al4p(fields.src[f]) && al16(fields.ring[f]), "ring_store_small: src[%d] must be 4-byte and ring[%d] 16-byte aligned", f, f);
+    tot4 += fields.ring_ld[f] / 4;
+  }
+  const long long threads = n * tot4 + (flags ? 2 * n : 0), blocks = (threads + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_store_small: n=%lld slots are more than one launch covers", n);
+  hipLaunchKernelGGL(ring_store_small_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, fields, (int)tot4, flags, episode_end, end_f32, n,
+                     nrows, start);
+  DGVIT_CHECK_LAUNCH("ring_store_small");
+  return DGVIT_OK;
+}
+
+int nstep_walk_strided(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                       const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, long long stride,
+                       int n, double gamma, float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out,
+                       long long* tail_out, hipStream_t stream) {
+  DGVIT_CHECK_ARG(rew && done && flags && next_small && idx, "nstep_walk_strided: rew, done, flags, next_small and idx must not be null");
+  DGVIT_CHECK_ARG(ret_out && done_out && discount_out && next_small_out && steps_out && tail_out,
+                  "nstep_walk_strided: ret_out, done_out, discount_out, next_small_out, steps_out and tail_out must not be null");
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0 && nrows < (1ll << 56),
+                  "nstep_walk_strided: nsel=%lld must be in [1, 2^31) and nrows=%lld in [1, 2^56)", nsel, nrows);
+  DGVIT_CHECK_ARG(stride >= 1 && stride <= nrows, "nstep_walk_strided: stride=%lld must be in [1, nrows] = [1, %lld]", stride, nrows);
+  DGVIT_CHECK_ARG(n >= 1 && n <= NSTEP_MAX, "nstep_walk_strided: n=%d must be in [1, %d]", n, NSTEP_MAX);
+  DGVIT_CHECK_ARG(gamma >= 0.0 && gamma <= 1.0, "nstep_walk_strided: gamma=%g must be in [0, 1]", gamma);   // a NaN fails both comparisons
+  DGVIT_CHECK_ARG(rew_ld > 0 && done_ld > 0, "nstep_walk_strided: rew_ld=%lld and done_ld=%lld must be positive", rew_ld, done_ld);
+  DGVIT_CHECK_ARG(small_ld > 0 && small_ld % 4 == 0 && small_ld <= (1ll << 20),
+                  "nstep_walk_strided: small_ld=%lld must be a positive multiple of 4, at most 2^20", small_ld);
+  DGVIT_CHECK_ARG(al16(next_small) && al16(next_small_out), "nstep_walk_strided: next_small and next_small_out must be 16-byte aligned");
+  DGVIT_CHECK_ARG(al4p(rew) && al4p(done) && al4p(ret_out) && al4p(done_out) && al4p(discount_out) && al4p(steps_out) &&
+                      (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (reinterpret_cast<uintptr_t>(tail_out) & 7) == 0,
+                  "nstep_walk_strided: float and int32 pointers must be 4-byte aligned, idx and tail_out 8-byte aligned");
+  hipLaunchKernelGGL(nstep_walk_strided_kernel, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags,
+                     reinterpret_cast<const float4*>(next_small), (int)(small_ld / 4), idx, nsel, nrows, stride, n, gamma, ret_out, done_out,
+                     discount_out, reinterpret_cast<float4*>(next_small_out), steps_out, tail_out);
+  DGVIT_CHECK_LAUNCH("nstep_walk_strided");
   return DGVIT_OK;
 }

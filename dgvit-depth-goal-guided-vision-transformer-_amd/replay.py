@@ -11,7 +11,9 @@ the fp32 frame.
 
 Consecutive ring slots are consecutive environment steps, so ``sample(..., n_step=n, gamma=g)`` returns multi-step transitions -- cpprb's
 ``Nstep`` option -- by a walk along the ring at sample time: nothing extra is stored and n and gamma may change from call
-to call.  What a walk may not cross is kept in ``episode_flags``, one byte per slot on the device.
+to call.  What a walk may not cross is kept in ``episode_flags``, one byte per slot on the device.  With ``num_envs=E`` the ring holds E
+parallel environments, a vector step in E consecutive slots, and an environment's steps lie E slots apart: ``add_vec``
+stores such a step from device tensors without visiting the host.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -35,6 +37,7 @@ def _al16(n: int) -> int:
 
 FRAME_FIELDS = ("obs", "next_obs")
 FLAG_END, FLAG_HEAD = 1, 2  # include/dgvit_hip.h: DGVIT_RING_END, DGVIT_RING_HEAD (bits of episode_flags)
+_INDEX_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
 NSTEP_MAX = 64              # one lane of a wave per visited slot
 
 
@@ -54,6 +57,17 @@ def _n_step(n):
     return int(n)
 
 
+def _num_envs(num_envs, size):
+    """``num_envs`` after its check: host-only, runs before anything touches a device"""
+    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)) or not 1 <= int(num_envs) <= int(size) \
+            or int(size) % int(num_envs):
+        raise ValueError(f"num_envs must be an int in [1, size] that divides size={int(size)}, got {num_envs!r}")
+    return int(num_envs)
+
+
+SMALL_FIELDS = ("pobs", "act", "rew", "next_pobs", "done")   # what one dgvit_ring_store_small launch stores
+
+
 class DeviceReplayBuffer:
     """The replay ring in HBM.  ``frame_dtype=torch.uint8`` (keyword-only; default ``torch.float32``) stores ``obs`` and ``next_obs`` as
     one byte per pixel, a quarter of the fp32 ring: ``store["obs"]`` and ``store["next_obs"]`` are then
@@ -71,11 +85,19 @@ class DeviceReplayBuffer:
     reference fetches ``done`` and never applies it, so ``done`` alone cannot mark episodes), bit 1 (HEAD) the newest slot written.  A
     buffer that never uses them allocates nothing and launches nothing more than before.  Episode ends before tracking started are
     unknown, apart from ``done``: call ``track_episodes()`` before the first ``add`` if n-step sampling is meant.  ``add_batch`` writes
-    consecutive slots, so demonstrations go in one episode per call, each followed by ``on_episode_end()`` -- or rely on their ``done``."""
+    consecutive slots, so demonstrations go in one episode per call, each followed by ``on_episode_end()`` -- or rely on their ``done``.
+
+    Parallel environments.  ``num_envs=E`` (keyword-only; an int in [1, size] that divides ``size``; default 1) gives the ring
+    a second axis: ``add_vec`` stores one step of E environments in the E consecutive slots ``base .. base + E - 1``, ``base`` a multiple
+    of E, environment e in slot ``base + e``.  The successor of slot s in its episode is ``(s + E) % size``, and because E divides ``size``
+    the lane ``s % E`` survives the wrap; ``sample(n_step=...)`` walks with that stride, ``idx % num_envs`` is a sampled slot's
+    environment, and ``stored`` / ``next_index`` keep counting slots.  HEAD then marks the E newest slots.  With E > 1 ``add`` and
+    ``add_batch`` are refused (a demonstration episode has no lane) and ``on_episode_end`` takes the environments that ended."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2,
-                 device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32):
+                 device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32, num_envs=1):
         self.frame_dtype = _frame_dtype(frame_dtype)
+        self.num_envs = _num_envs(num_envs, size)
         self.size, self.device = int(size), torch.device(device)
         if self.device.type != "cuda":
             raise _lib.DgvitError("DeviceReplayBuffer lives in HBM; pass a ROCm device")
@@ -104,26 +126,57 @@ class DeviceReplayBuffer:
         """hook: ring slots start .. start + n - 1 (mod size) have just been written"""
 
     def track_episodes(self) -> None:
-        """Start keeping ``episode_flags`` (idempotent).  On allocation the flags are zeros with HEAD on the newest slot, if anything
-        is stored: episode ends from before are unknown, apart from ``done``.  The allocation cannot happen inside a stream capture."""
+        """Start keeping ``episode_flags`` (idempotent).  On allocation the flags are zeros with HEAD on the newest slot (the
+        ``num_envs`` slots of the newest vector step), if anything is stored: episode ends from before are unknown, apart from ``done``.
+        The allocation cannot happen inside a stream capture."""
         if self.episode_flags is not None:
             return
         if torch.cuda.is_current_stream_capturing():
             raise _lib.DgvitError("track_episodes() allocates the episode flags, which a stream capture cannot: call it (or on_episode_end(), "
                                   "or an eager sample(n_step=...)) before capturing")
         flags = torch.zeros(self.size, dtype=torch.uint8, device=self.device)
-        if self.stored:
+        if self.stored and self.num_envs == 1:
             flags[(self.next_index - 1) % self.size] = FLAG_HEAD
+        elif self.stored:                        # the newest vector step: base is a multiple of num_envs, so the slice does not wrap
+            base = (self.next_index - self.num_envs) % self.size
+            flags[base:base + self.num_envs] = FLAG_HEAD
         self.episode_flags = flags
 
-    def on_episode_end(self) -> None:
+    def on_episode_end(self, envs=None) -> None:
         """The newest transition is the last of its episode, whatever its ``done`` says (cpprb's name): ORs END into its flags on the
-        device, without a host synchronisation."""
+        device, without a host synchronisation.  With ``num_envs > 1`` ``envs`` says whose: a bool mask (E,) or an integer index tensor or
+        array, on the host or on the device (a device mask or index never visits the host); with ``num_envs == 1`` it must be None."""
+        E = self.num_envs
+        if E == 1 and envs is not None:
+            raise ValueError("on_episode_end(envs=...) is for buffers with num_envs > 1; this one has a single environment")
+        if E > 1 and envs is None:
+            raise ValueError(f"on_episode_end() on a buffer with num_envs={E} needs envs=: a bool mask ({E},) or the indices of the "
+                             "environments whose episode ended")
         if self.stored == 0:
             raise RuntimeError("on_episode_end() on an empty buffer: there is no newest transition")
         self.track_episodes()
-        newest = (self.next_index - 1) % self.size
-        self.episode_flags[newest:newest + 1].bitwise_or_(FLAG_END)
+        if E == 1:
+            newest = (self.next_index - 1) % self.size
+            self.episode_flags[newest:newest + 1].bitwise_or_(FLAG_END)
+            return
+        if not (torch.is_tensor(envs) and envs.device.type != "cpu"):
+            envs = np.asarray(envs.numpy() if torch.is_tensor(envs) else envs)
+            envs = torch.from_numpy(np.ascontiguousarray(envs if envs.size else envs.astype(np.int64)))     # [] : nobody's episode ended
+            if envs.dtype != torch.bool and envs.numel() and not (envs.dtype in _INDEX_DTYPES and 0 <= int(envs.min()) and int(envs.max()) < E):
+                raise ValueError(f"envs: indices must be integers in [0, {E}), got {envs.tolist()!r}")
+            envs = envs.to(self.device)
+        elif envs.device != self.episode_flags.device:
+            raise ValueError(f"envs: the tensor is on {envs.device}, the ring on {self.episode_flags.device}")
+        if envs.dtype == torch.bool:
+            if tuple(envs.shape) != (E,):
+                raise ValueError(f"envs: a mask must be ({E},), got {tuple(envs.shape)}")
+            mask = envs.to(torch.uint8)          # END is bit 0: the mask as bytes is what is ORed in
+        elif envs.dtype in _INDEX_DTYPES:
+            mask = torch.zeros(E, dtype=torch.uint8, device=self.device).index_fill_(0, envs.reshape(-1).to(torch.int64), FLAG_END)
+        else:
+            raise ValueError(f"envs must be a bool mask or an integer index tensor or array, got dtype {envs.dtype}")
+        base = (self.next_index - E) % self.size
+        self.episode_flags[base:base + E].bitwise_or_(mask)
 
     def _travel(self, k, v, n):
         """How field k of n transitions travels into the ring: ("floats", (n, cnt) fp32 array), in the one staged matrix -- every field of
@@ -161,6 +214,9 @@ class DeviceReplayBuffer:
         staged as bytes (one byte matrix, one copy) and copied into the ring, device tensors are quantised (fp32) or copied (uint8)
         where they are.  Which frame fields the matrix holds is the call's, so its column offsets are too: fixed ones would stage
         2 H W unused floats per transition whenever the frames come as bytes or from the device."""
+        if self.num_envs > 1:
+            raise _lib.DgvitError(f"add() / add_batch() write consecutive slots of one episode, and this ring has num_envs={self.num_envs} "
+                                  "lanes: store a step of all environments with add_vec()")
         for k in self.fields:
             if k not in kw:
                 raise KeyError(f"missing field {k}")
@@ -219,6 +275,111 @@ class DeviceReplayBuffer:
         the host with numpy slicing, one host->device copy."""
         self._store(kw, len(kw["obs"]))
 
+    def _vec_field(self, k, v):
+        """Field k of one vector step, checked -> the (E, cnt) device tensor where it lies (fp32, or the uint8 codes of a frame of a uint8
+        ring; made contiguous on the device), or the (E, cnt) host array, float32 or uint8 codes, that will travel in the staged matrix."""
+        E, cnt = self.num_envs, self.fields[k]
+        codes_ok = self.frame_dtype is torch.uint8 and k in FRAME_FIELDS
+        on_device = torch.is_tensor(v) and v.device.type != "cpu"
+        if on_device:
+            home = self.store[k].device
+            if v.device != home:
+                raise ValueError(f"{k}: the tensor is on {v.device}, the ring on {home}")
+            v = v.detach()
+            codes = v.dtype == torch.uint8
+            if not codes and v.dtype != torch.float32:
+                raise ValueError(f"{k}: a device tensor must be float32{' or uint8' if codes_ok else ''}, got {v.dtype}")
+        else:
+            v = np.asarray(v.detach().numpy() if torch.is_tensor(v) else v)
+            codes = v.dtype == np.uint8 and k in FRAME_FIELDS
+        if codes and not codes_ok:
+            raise ValueError(f"{k}: uint8 codes can only be stored in the frame fields of a frame_dtype=torch.uint8 ring")
+        shape = tuple(v.shape)
+        if len(shape) == 0 or shape[0] != E or int(np.prod(shape)) != E * cnt:
+            raise ValueError(f"{k}: expected first axis num_envs={E} and {cnt} values per environment, got shape {shape}")
+        if on_device:
+            return v.reshape(E, cnt).contiguous()
+        return np.ascontiguousarray(v.reshape(E, cnt), dtype=np.uint8 if codes else np.float32)
+
+    def add_vec(self, *, obs, pobs, act, rew, next_obs, next_pobs, done, episode_end=None) -> None:
+        """One step of all ``num_envs`` environments: every field has first axis E, environment e goes to slot
+        ``next_index + e``; ``rew`` and ``done`` may be (E,) or (E, 1).  A field may be a tensor on the buffer's device -- fp32, or uint8
+        codes for the frame fields of a uint8 ring; it is read where it lies -- or a host array, CPU tensor or list; all host fields of a
+        call travel in ONE pinned staging matrix and one host->device copy, and the same kernels read them from there.  Per field, freely
+        mixed.  A wrong dtype, device or shape raises ValueError naming the field.
+
+        ``episode_end`` -- None, a host bool array-like (E,), or a device tensor (E,) of bool, uint8 or fp32, nonzero = end -- says that
+        environment e's transition of this step is the last of its episode, whatever its ``done`` says: ``on_episode_end()``'s meaning.
+        Passing it starts ``track_episodes()`` if nothing has, so the first such call must happen outside a capture.
+
+        Two launches: dgvit_ring_store_frames for ``obs`` and ``next_obs``, dgvit_ring_store_small for the other five fields and, when
+        episodes are tracked, the marks (the new slots get HEAD, and END where ``episode_end`` says so; the previous step's slots keep only
+        their END); the prioritized subclass adds its dgvit_per_set_range.  With every field and ``episode_end`` on the device nothing
+        synchronises with the host and nothing pinned is allocated.  ``num_envs == 1`` is allowed: the device-side ``add``."""
+        E, kw = self.num_envs, dict(obs=obs, pobs=pobs, act=act, rew=rew, next_obs=next_obs, next_pobs=next_pobs, done=done)
+        rows = {k: self._vec_field(k, kw[k]) for k in self.fields}
+        end, end_f32 = episode_end, 0
+        if end is not None:
+            if torch.is_tensor(end) and end.device.type != "cpu":
+                if end.device != self.store["obs"].device or end.dtype not in (torch.bool, torch.uint8, torch.float32) or end.numel() != E:
+                    raise ValueError(f"episode_end: a device tensor must be ({E},) bool, uint8 or float32 on {self.store['obs'].device}, got "
+                                     f"{tuple(end.shape)} {end.dtype} on {end.device}")
+                end, end_f32 = end.detach().reshape(E).contiguous(), int(end.dtype == torch.float32)
+            else:
+                end = np.asarray(end.detach().numpy() if torch.is_tensor(end) else end).reshape(-1)
+                if end.size != E:
+                    raise ValueError(f"episode_end: expected {E} entries, got {end.size}")
+                end, end_f32 = (end != 0).astype(np.float32), 1
+            self.track_episodes()
+        # the staged matrix: every host field's columns side by side, each block a multiple of 4 floats wide (codes four to a float), and
+        # behind its E rows the E episode ends of a host episode_end
+        off, row = {}, 0
+        for k, v in rows.items():
+            if not torch.is_tensor(v):
+                off[k] = row
+                row += _al4(self.fields[k]) if v.dtype == np.float32 else _al4(_al4(self.fields[k]) // 4)
+        host_end = end is not None and not torch.is_tensor(end)
+        dev = None
+        if off or host_end:
+            host = np.zeros(E * row + (E if host_end else 0), dtype=np.float32)
+            mat = host[:E * row].reshape(E, row)
+            for k, o in off.items():
+                if rows[k].dtype == np.float32:
+                    mat[:, o:o + self.fields[k]] = rows[k]
+                else:
+                    mat.view(np.uint8)[:, 4 * o:4 * o + self.fields[k]] = rows[k]
+            if host_end:
+                host[E * row:] = end
+            stage = torch.from_numpy(host).pin_memory()
+            dev = stage.to(self.device, non_blocking=True)
+            self._last_stage = [stage, dev]      # keep the pinned buffer alive until the async copy has certainly been issued
+
+        def source(k):
+            """(pointer, 1 for uint8 codes, row stride in elements) of field k's rows on the device"""
+            v = rows[k]
+            if torch.is_tensor(v):
+                return v.data_ptr(), int(v.dtype == torch.uint8), self.fields[k]
+            codes = v.dtype == np.uint8
+            return dev.data_ptr() + 4 * off[k], int(codes), 4 * row if codes else row
+
+        lib, st, i = _lib.load(), _stream(), self.next_index
+        u8 = self.frame_dtype is torch.uint8
+        small = _lib.dgvit_small_fields()
+        for j, k in enumerate(SMALL_FIELDS):
+            small.src[j], _, small.src_ld[j] = source(k)
+            small.ring[j], small.cols[j], small.ring_ld[j] = self.store[k].data_ptr(), self.fields[k], self.rows[k]
+        end_ptr = None if end is None else (end.data_ptr() if torch.is_tensor(end) else dev.data_ptr() + 4 * E * row)
+        with torch.cuda.device(self.device):
+            (p0, c0, ld0), (p1, c1, ld1) = source("obs"), source("next_obs")
+            rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
+                                             self.row_bytes if u8 else self.rows["obs"], E, self.fields["obs"], self.size, i, st)
+            _lib.check(rc, "dgvit_ring_store_frames")
+            rc = lib.dgvit_ring_store_small(small, _ptr(self.episode_flags), end_ptr, end_f32, E, self.size, i, st)
+            _lib.check(rc, "dgvit_ring_store_small")
+        self.next_index = (i + E) % self.size
+        self.stored = min(self.stored + E, self.size)
+        self._on_store(i, E)
+
     def sample_indices(self, batch_size: int) -> torch.Tensor:
         if self.stored == 0:
             raise RuntimeError("cannot sample from an empty buffer")
@@ -244,7 +405,9 @@ class DeviceReplayBuffer:
         ``update_priorities`` must get.  Five launches instead of seven: the ``obs``, ``pobs`` and ``act`` gathers, the walk (which
         produces ``rew``, ``done`` and ``next_pobs`` itself) and the ``next_obs`` gather at the walk's last slot.  Outside a capture
         the call starts ``track_episodes()`` if nothing has; inside one the flags must exist already, and a replayed graph follows
-        the ring as later ``add()``s move it.  ``n_step=None`` is the one-step path above, launch for launch."""
+        the ring as later ``add()``s move it.  ``n_step=None`` is the one-step path above, launch for launch.  On a ring with
+        ``num_envs=E > 1`` the walk follows the slot's own environment, ``(i + k E) % size``, and nothing else changes: ``indexes`` are
+        slots, ``indexes % num_envs`` their environments."""
         n_step, gamma = _n_step(n_step), _unit("gamma", gamma)
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
         if n_step is not None:
@@ -288,16 +451,19 @@ class DeviceReplayBuffer:
         return out
 
     def _walk(self, idx, n_step, gamma):
-        """the one dgvit_nstep_walk launch of an n-step sample: rew, done, next_pobs, discount, steps and the tail slots"""
+        """the one dgvit_nstep_walk launch of an n-step sample (dgvit_nstep_walk_strided on a ring of several environments): rew, done,
+        next_pobs, discount, steps and the tail slots"""
         B, dev = idx.numel(), self.device
         f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
         ret, done, disc, small = f32(B), f32(B), f32(B), f32(B, self.rows["next_pobs"])
         steps, tail = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
-        rc = _lib.load().dgvit_nstep_walk(_ptr(self.store["rew"]), self.rows["rew"], _ptr(self.store["done"]), self.rows["done"],
-                                          _ptr(self.episode_flags), _ptr(self.store["next_pobs"]), self.rows["next_pobs"], _ptr(idx), B,
-                                          self.size, n_step, gamma, _ptr(ret), _ptr(done), _ptr(disc), _ptr(small), _ptr(steps), _ptr(tail),
-                                          _stream())
-        _lib.check(rc, "dgvit_nstep_walk")
+        ring = (_ptr(self.store["rew"]), self.rows["rew"], _ptr(self.store["done"]), self.rows["done"], _ptr(self.episode_flags),
+                _ptr(self.store["next_pobs"]), self.rows["next_pobs"], _ptr(idx), B, self.size)
+        outs = (n_step, gamma, _ptr(ret), _ptr(done), _ptr(disc), _ptr(small), _ptr(steps), _ptr(tail), _stream())
+        if self.num_envs == 1:
+            _lib.check(_lib.load().dgvit_nstep_walk(*ring, *outs), "dgvit_nstep_walk")
+        else:                                    # an environment's next transition is num_envs slots on (DESIGN 3.35)
+            _lib.check(_lib.load().dgvit_nstep_walk_strided(*ring, self.num_envs, *outs), "dgvit_nstep_walk_strided")
         return {"rew": ret.view(B, 1), "done": done.view(B, 1), "next_pobs": small[:, :self.fields["next_pobs"]], "discount": disc.view(B, 1),
                 "steps": steps, "tail": tail}
 
@@ -342,14 +508,15 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",
-                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32):
+                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32, num_envs=1):
         _frame_dtype(frame_dtype)
+        _num_envs(num_envs, size)
         self.alpha = _unit("alpha", alpha)
         if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0.0 <= float(eps) < float("inf"):
             raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
         self.eps = float(eps)
         self._levels, floats = per_tree_layout(int(size))
-        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed, frame_dtype=frame_dtype)
+        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed, frame_dtype=frame_dtype, num_envs=num_envs)
         lib = _lib.load()
         if lib.dgvit_per_tree_floats(self.size) != floats:
             raise _lib.DgvitError("dgvit_per_tree_floats disagrees with replay.per_tree_layout; rebuild the library")

@@ -445,6 +445,51 @@ int dgvit_nstep_walk(const float* rew, long long rew_ld, const float* done, long
                      void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The ring of E parallel environments (dgvit_amd.replay: DeviceReplayBuffer(num_envs=E), add_vec).  Vector step t lies in
+ * the E consecutive slots base .. base + E - 1, base a multiple of E, environment e in slot base + e; E divides nrows, so the successor
+ * of slot s in its episode is (s + E) mod nrows and the lane s mod E survives the wrap.  The store path below reads device memory only:
+ * a source is a device tensor where it lies, or a column block of one staged matrix.
+ *
+ * dgvit_ring_store_frames: both frame fields of n consecutive slots in ONE launch; field f in {0, 1} is one grid dimension with its own
+ *   source src[f] (element type src_u8[f]: 0 fp32, 1 uint8; row stride src_ld[f] >= cols in ELEMENTS, which need not be a multiple of 4)
+ *   and its own ring matrix ring[f] (element type ring_u8, the same for both; row stride ring_ld in elements):
+ *     fp32 -> fp32 ring:   ring[(start + i) % nrows][c] = src[i][c]                 ring_ld a multiple of 4 floats
+ *     fp32 -> uint8 ring:  ring[(start + i) % nrows][c] = q(src[i][c])              q of dgvit_quantize_rows_u8; ring_ld a multiple of 16
+ *     uint8 -> uint8 ring: ring[(start + i) % nrows][c] = src[i][c]                 copied a dword at a time
+ *   for i < n, c < cols; columns cols .. ring_ld - 1 of every written row are zeros.  uint8 into an fp32 ring is refused.  A source
+ *   whose rows are 16-byte (fp32) or 4-byte (uint8) aligned is read in whole groups, any other element by element: the same bytes.
+ *   ring[f] 16-byte aligned, an fp32 source 4-byte aligned; 1 <= n <= nrows, 0 <= start < nrows, cols <= 2^25, ring_ld <= 2^26.
+ * dgvit_ring_store_small: the five small fields (dgvit_small_fields: pobs, act, rew, next_pobs, done in any order) of the same n slots
+ *   and, when `flags` is not NULL, their marks, in ONE launch:
+ *     ring[f][(start + i) % nrows][c] = src[f][i * src_ld[f] + c]   for c < cols[f], zeros up to ring_ld[f] (a multiple of 4 floats)
+ *     flags[(start + i) % nrows]      = HEAD | (episode_end && episode_end[i] != 0 ? END : 0)
+ *     flags[(start - n + i) % nrows] &= END                         the previous step is no longer the newest; skipped when n == nrows
+ *   episode_end may be NULL (no ends); it is n bytes (bool / uint8; end_f32 == 0) or n floats (end_f32 == 1), nonzero = end.  n must
+ *   divide nrows (so the previous step's slots are not the written ones); 1 <= cols[f] <= ring_ld[f] <= 2^20, src_ld[f] >= cols[f].
+ * dgvit_nstep_walk_strided: dgvit_nstep_walk with s_k = (i + k * stride) mod nrows, 1 <= stride <= nrows; everything else, every
+ *   output and every check as there.  stride == 1 gives the bits of dgvit_nstep_walk.  i + 63 * stride may exceed 2 * nrows (a ring of
+ *   fewer than 64 steps): the slot is then reduced by a true modulo, by one subtraction where that is enough.
+ * None of the three synchronises; all are capturable.
+ * -------------------------------------------------------------------------------------------- */
+#define DGVIT_SMALL_FIELDS 5
+typedef struct {
+  const float* src[DGVIT_SMALL_FIELDS];    /* device rows of field f, src_ld[f] floats apart */
+  float* ring[DGVIT_SMALL_FIELDS];         /* (nrows, ring_ld[f]) fp32, 16-byte aligned */
+  long long src_ld[DGVIT_SMALL_FIELDS];
+  int cols[DGVIT_SMALL_FIELDS];
+  int ring_ld[DGVIT_SMALL_FIELDS];
+} dgvit_small_fields;
+int dgvit_ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
+                            void* ring1, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
+                            void* stream);
+int dgvit_ring_store_small(dgvit_small_fields fields, unsigned char* flags /* may be NULL */, const void* episode_end /* may be NULL */,
+                           int end_f32, long long n, long long nrows, long long start, void* stream);
+int dgvit_nstep_walk_strided(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                             const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows,
+                             long long stride, int n, double gamma, float* ret_out, float* done_out, float* discount_out,
+                             float* next_small_out, int* steps_out, long long* tail_out, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
  * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
  *
