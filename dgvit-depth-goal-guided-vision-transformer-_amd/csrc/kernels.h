@@ -90,7 +90,8 @@ int ring_mark(unsigned char* flags, long long nrows, long long start, long long 
 int nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags, const float* next_small,
                long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma, float* ret_out, float* done_out,
                float* discount_out, float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream);
-// the ring of E parallel environments: the store path that reads device memory only, and the walk with a stride
+// the ring of E parallel environments: the store path that reads device memory only -- since DESIGN 3.36 the one store path of add and
+// add_batch as well -- and the walk with a stride
 int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
                       void* ring1, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
                       hipStream_t stream);

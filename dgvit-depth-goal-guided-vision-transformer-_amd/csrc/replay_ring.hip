@@ -3,14 +3,16 @@
 // are k/255 with k in 0..255, env_lab.py:420-434, and the fp32 frame is restored inside the gather).
 //   gather_rows             : out[i] = src[idx[i]]                                          (replay sampling)
 //   gather_rows_u8          : out[i][c] = (float)ring[idx[i]][c] / 255.0f
-//   quantize_rows_u8        : ring[(start + i) % nrows][c] = q(src[i][c]),  q(x) = (uint8) rintf(fminf(fmaxf(x * 255, 0), 255))
+//   quantize_rows_u8        : ring[(start + i) % nrows][c] = q(src[i][c]),  q(x) = (uint8) rintf(fminf(fmaxf(x * 255, 0), 255)); an
+//                             exported entry point that the Python package no longer calls
 //   gather_shift_frames     : the gather with the DrQ random shift (replicate-pad by `pad`, crop at a per-sample offset) folded in
 //   gather_shift_frames_u8  : the same kernel template over a byte ring: one draw, one set of clamps
 //   ring_mark               : the per-slot episode flags after a store: the written slots forget their marks, the newest one is the HEAD
 //   nstep_walk              : the n-step return of each sampled slot: a walk along the ring that stops at done, at a flag or after n slots,
 //                             one wave per sample, the rewards summed in double in ascending order
-//   ring_store_frames       : both frame fields of one vector step of E environments from device memory, fp32 or uint8 source, either ring
-//   ring_store_small        : its five small fields and its marks (HEAD | END per environment) in one launch
+//   ring_store_frames       : both frame fields of n slots -- add, add_batch (n may cross the ring's end) or one vector step of E
+//                             environments -- from device memory, fp32 or uint8 source, either ring
+//   ring_store_small        : their five small fields and, for one step, its marks (HEAD | END per environment) in one launch
 //   nstep_walk_strided      : nstep_walk along one environment's slots, (i + k E) mod nrows
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
@@ -72,7 +74,9 @@ __global__ void __launch_bounds__(256) gather_rows_u8_kernel(const unsigned char
   reinterpret_cast<float4*>(out)[i] = o;
 }
 
-// thread = one dword of a ring row.  VEC: src rows are 16-byte aligned (src_ld % 4 == 0 and an aligned base), a whole group is one float4
+// thread = one dword of a ring row.  VEC: src rows are 16-byte aligned (src_ld % 4 == 0 and an aligned base), a whole group is one float4.
+// This is the fp32 -> uint8 case of ring_store_frames_kernel<true> below for one field, and is kept beside it: launched in its place
+// (gridDim.y = 1) that kernel took 10.3 us where this one takes 9.8 us on 512 rows of 128 x 160
 template <bool VEC>
 __global__ void __launch_bounds__(256) quantize_rows_u8_kernel(const float* __restrict__ src, long long src_ld, uint32_t* __restrict__ ring,
                                                                long long total4, int row4, int cols, long long nrows, long long start) {
@@ -377,6 +381,49 @@ int launch_gather_shift(const char* name, const T* src, const long long* idx, fl
 }
 
 inline bool al4p(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+inline bool al8p(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; }
+
+// the slots of a store, n from `start` on: what ring_mark and the three store entry points ask of them
+int check_slots(const char* name, long long n, long long nrows, long long start) {
+  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows, "%s: n=%lld must be in [1, nrows] and nrows=%lld positive", name, n, nrows);
+  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "%s: start=%lld must be in [0, nrows) = [0, %lld)", name, start, nrows);
+  return DGVIT_OK;
+}
+
+// both walks: `name` is the entry point's, `stride` null for nstep_walk, whose kernel has no such argument
+int launch_nstep_walk(const char* name, const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
+                      const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows,
+                      const long long* stride, int n, double gamma, float* ret_out, float* done_out, float* discount_out,
+                      float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream) {
+  DGVIT_CHECK_ARG(rew && done && flags && next_small && idx, "%s: rew, done, flags, next_small and idx must not be null", name);
+  DGVIT_CHECK_ARG(ret_out && done_out && discount_out && next_small_out && steps_out && tail_out,
+                  "%s: ret_out, done_out, discount_out, next_small_out, steps_out and tail_out must not be null", name);
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0, "%s: nsel=%lld must be in [1, 2^31) and nrows=%lld positive", name, nsel, nrows);
+  if (stride) {
+    DGVIT_CHECK_ARG(nrows < (1ll << 56), "%s: nrows=%lld must be below 2^56", name, nrows);   // lane * stride cannot overflow
+    DGVIT_CHECK_ARG(*stride >= 1 && *stride <= nrows, "%s: stride=%lld must be in [1, nrows] = [1, %lld]", name, *stride, nrows);
+  }
+  DGVIT_CHECK_ARG(n >= 1 && n <= NSTEP_MAX, "%s: n=%d must be in [1, %d]", name, n, NSTEP_MAX);
+  DGVIT_CHECK_ARG(gamma >= 0.0 && gamma <= 1.0, "%s: gamma=%g must be in [0, 1]", name, gamma);   // a NaN fails both comparisons
+  DGVIT_CHECK_ARG(rew_ld > 0 && done_ld > 0, "%s: rew_ld=%lld and done_ld=%lld must be positive", name, rew_ld, done_ld);
+  DGVIT_CHECK_ARG(small_ld > 0 && small_ld % 4 == 0 && small_ld <= (1ll << 20), "%s: small_ld=%lld must be a positive multiple of 4, at most 2^20",
+                  name, small_ld);
+  DGVIT_CHECK_ARG(al16(next_small) && al16(next_small_out), "%s: next_small and next_small_out must be 16-byte aligned", name);
+  DGVIT_CHECK_ARG(al4p(rew) && al4p(done) && al4p(ret_out) && al4p(done_out) && al4p(discount_out) && al4p(steps_out) && al8p(idx) &&
+                      al8p(tail_out),
+                  "%s: float and int32 pointers must be 4-byte aligned, idx and tail_out 8-byte aligned", name);
+  const dim3 grid((unsigned)((nsel + 3) / 4));
+  const float4* small = reinterpret_cast<const float4*>(next_small);
+  float4* small_out = reinterpret_cast<float4*>(next_small_out);
+  if (stride)
+    hipLaunchKernelGGL(nstep_walk_strided_kernel, grid, dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags, small, (int)(small_ld / 4), idx,
+                       nsel, nrows, *stride, n, gamma, ret_out, done_out, discount_out, small_out, steps_out, tail_out);
+  else
+    hipLaunchKernelGGL(nstep_walk_kernel, grid, dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags, small, (int)(small_ld / 4), idx, nsel,
+                       nrows, n, gamma, ret_out, done_out, discount_out, small_out, steps_out, tail_out);
+  DGVIT_CHECK_LAUNCH(name);
+  return DGVIT_OK;
+}
 
 }  // namespace
 
@@ -408,12 +455,11 @@ int gather_shift_frames_u8(const unsigned char* ring, const long long* idx, floa
 int quantize_rows_u8(const float* src, long long src_ld, unsigned char* ring, long long n, long long cols, long long row_bytes,
                      long long nrows, long long start, hipStream_t stream) {
   DGVIT_CHECK_ARG(src && ring, "quantize_rows_u8: src and ring must not be null");
-  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows, "quantize_rows_u8: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  if (const int rc = check_slots("quantize_rows_u8", n, nrows, start)) return rc;
   DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "quantize_rows_u8: cols=%lld must be in [1, 2^25]", cols);
   DGVIT_CHECK_ARG(row_bytes % 16 == 0 && row_bytes >= cols && row_bytes <= (1ll << 26),
                   "quantize_rows_u8: row_bytes=%lld must be a multiple of 16, at least cols=%lld and at most 2^26", row_bytes, cols);
   DGVIT_CHECK_ARG(src_ld >= cols, "quantize_rows_u8: src_ld=%lld must be at least cols=%lld", src_ld, cols);
-  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "quantize_rows_u8: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
   DGVIT_CHECK_ARG(al4p(src) && al16(ring), "quantize_rows_u8: src must be 4-byte and ring 16-byte aligned");
   const int row4 = (int)(row_bytes / 4);
   const long long total4 = n * row4, blocks = (total4 + 255) / 256;
@@ -450,8 +496,7 @@ int gather_rows_u8(const unsigned char* ring, const long long* idx, float* out, 
 
 int ring_mark(unsigned char* flags, long long nrows, long long start, long long n, hipStream_t stream) {
   DGVIT_CHECK_ARG(flags, "ring_mark: flags must not be null");
-  DGVIT_CHECK_ARG(nrows > 0 && n > 0 && n <= nrows, "ring_mark: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
-  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_mark: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  if (const int rc = check_slots("ring_mark", n, nrows, start)) return rc;
   const long long blocks = (n + 1 + 255) / 256;
   DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_mark: n=%lld slots are more than one launch covers", n);
   hipLaunchKernelGGL(ring_mark_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, flags, nrows, start, n);
@@ -462,24 +507,8 @@ int ring_mark(unsigned char* flags, long long nrows, long long start, long long 
 int nstep_walk(const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags, const float* next_small,
                long long small_ld, const long long* idx, long long nsel, long long nrows, int n, double gamma, float* ret_out, float* done_out,
                float* discount_out, float* next_small_out, int* steps_out, long long* tail_out, hipStream_t stream) {
-  DGVIT_CHECK_ARG(rew && done && flags && next_small && idx, "nstep_walk: rew, done, flags, next_small and idx must not be null");
-  DGVIT_CHECK_ARG(ret_out && done_out && discount_out && next_small_out && steps_out && tail_out,
-                  "nstep_walk: ret_out, done_out, discount_out, next_small_out, steps_out and tail_out must not be null");
-  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0, "nstep_walk: nsel=%lld must be in [1, 2^31) and nrows=%lld positive", nsel, nrows);
-  DGVIT_CHECK_ARG(n >= 1 && n <= NSTEP_MAX, "nstep_walk: n=%d must be in [1, %d]", n, NSTEP_MAX);
-  DGVIT_CHECK_ARG(gamma >= 0.0 && gamma <= 1.0, "nstep_walk: gamma=%g must be in [0, 1]", gamma);   // a NaN fails both comparisons
-  DGVIT_CHECK_ARG(rew_ld > 0 && done_ld > 0, "nstep_walk: rew_ld=%lld and done_ld=%lld must be positive", rew_ld, done_ld);
-  DGVIT_CHECK_ARG(small_ld > 0 && small_ld % 4 == 0 && small_ld <= (1ll << 20),
-                  "nstep_walk: small_ld=%lld must be a positive multiple of 4, at most 2^20", small_ld);
-  DGVIT_CHECK_ARG(al16(next_small) && al16(next_small_out), "nstep_walk: next_small and next_small_out must be 16-byte aligned");
-  DGVIT_CHECK_ARG(al4p(rew) && al4p(done) && al4p(ret_out) && al4p(done_out) && al4p(discount_out) && al4p(steps_out) &&
-                      (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (reinterpret_cast<uintptr_t>(tail_out) & 7) == 0,
-                  "nstep_walk: float and int32 pointers must be 4-byte aligned, idx and tail_out 8-byte aligned");
-  hipLaunchKernelGGL(nstep_walk_kernel, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags,
-                     reinterpret_cast<const float4*>(next_small), (int)(small_ld / 4), idx, nsel, nrows, n, gamma, ret_out, done_out,
-                     discount_out, reinterpret_cast<float4*>(next_small_out), steps_out, tail_out);
-  DGVIT_CHECK_LAUNCH("nstep_walk");
-  return DGVIT_OK;
+  return launch_nstep_walk("nstep_walk", rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, nullptr, n, gamma, ret_out,
+                           done_out, discount_out, next_small_out, steps_out, tail_out, stream);
 }
 
 int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
@@ -490,14 +519,13 @@ int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const vo
                   src1_u8, ring_u8);
   DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "ring_store_frames: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring", src0_u8,
                   src1_u8);
-  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows, "ring_store_frames: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  if (const int rc = check_slots("ring_store_frames", n, nrows, start)) return rc;
   DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_store_frames: cols=%lld must be in [1, 2^25]", cols);
   DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
                   "ring_store_frames: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring_ld, ring_u8 ? 16 : 4,
                   cols);
   DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "ring_store_frames: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld", src0_ld,
                   src1_ld, cols);
-  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_store_frames: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
   DGVIT_CHECK_ARG(al16(ring0) && al16(ring1) && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)),
                   "ring_store_frames: the rings must be 16-byte and fp32 sources 4-byte aligned");
   const int row4 = (int)(ring_ld / 4);   // groups of 4 pixels per ring row, a dword of bytes or a float4
@@ -520,9 +548,9 @@ int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const vo
 
 int ring_store_small(const dgvit_small_fields& fields, unsigned char* flags, const void* episode_end, int end_f32, long long n,
                      long long nrows, long long start, hipStream_t stream) {
-  DGVIT_CHECK_ARG(n > 0 && nrows > 0 && n <= nrows && nrows % n == 0,
-                  "ring_store_small: n=%lld must be in [1, nrows] and divide nrows=%lld, which must be positive", n, nrows);
-  DGVIT_CHECK_ARG(start >= 0 && start < nrows, "ring_store_small: start=%lld must be in [0, nrows) = [0, %lld)", start, nrows);
+  if (const int rc = check_slots("ring_store_small", n, nrows, start)) return rc;
+  // only the marks touch the previous step's slots, which are other slots than the written ones when n divides nrows
+  DGVIT_CHECK_ARG(!flags || nrows % n == 0, "ring_store_small: n=%lld must divide nrows=%lld when flags are given", n, nrows);
   DGVIT_CHECK_ARG(end_f32 == 0 || end_f32 == 1, "ring_store_small: end_f32=%d must be 0 or 1", end_f32);
   DGVIT_CHECK_ARG(!episode_end || flags, "ring_store_small: episode_end without flags: the flags must not be null when ends are given");
   DGVIT_CHECK_ARG(!episode_end || !end_f32 || al4p(episode_end), "ring_store_small: an fp32 episode_end must be 4-byte aligned");
@@ -549,24 +577,6 @@ int nstep_walk_strided(const float* rew, long long rew_ld, const float* done, lo
                        const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, long long stride,
                        int n, double gamma, float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out,
                        long long* tail_out, hipStream_t stream) {
-  DGVIT_CHECK_ARG(rew && done && flags && next_small && idx, "nstep_walk_strided: rew, done, flags, next_small and idx must not be null");
-  DGVIT_CHECK_ARG(ret_out && done_out && discount_out && next_small_out && steps_out && tail_out,
-                  "nstep_walk_strided: ret_out, done_out, discount_out, next_small_out, steps_out and tail_out must not be null");
-  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0 && nrows < (1ll << 56),
-                  "nstep_walk_strided: nsel=%lld must be in [1, 2^31) and nrows=%lld in [1, 2^56)", nsel, nrows);
-  DGVIT_CHECK_ARG(stride >= 1 && stride <= nrows, "nstep_walk_strided: stride=%lld must be in [1, nrows] = [1, %lld]", stride, nrows);
-  DGVIT_CHECK_ARG(n >= 1 && n <= NSTEP_MAX, "nstep_walk_strided: n=%d must be in [1, %d]", n, NSTEP_MAX);
-  DGVIT_CHECK_ARG(gamma >= 0.0 && gamma <= 1.0, "nstep_walk_strided: gamma=%g must be in [0, 1]", gamma);   // a NaN fails both comparisons
-  DGVIT_CHECK_ARG(rew_ld > 0 && done_ld > 0, "nstep_walk_strided: rew_ld=%lld and done_ld=%lld must be positive", rew_ld, done_ld);
-  DGVIT_CHECK_ARG(small_ld > 0 && small_ld % 4 == 0 && small_ld <= (1ll << 20),
-                  "nstep_walk_strided: small_ld=%lld must be a positive multiple of 4, at most 2^20", small_ld);
-  DGVIT_CHECK_ARG(al16(next_small) && al16(next_small_out), "nstep_walk_strided: next_small and next_small_out must be 16-byte aligned");
-  DGVIT_CHECK_ARG(al4p(rew) && al4p(done) && al4p(ret_out) && al4p(done_out) && al4p(discount_out) && al4p(steps_out) &&
-                      (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (reinterpret_cast<uintptr_t>(tail_out) & 7) == 0,
-                  "nstep_walk_strided: float and int32 pointers must be 4-byte aligned, idx and tail_out 8-byte aligned");
-  hipLaunchKernelGGL(nstep_walk_strided_kernel, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, rew, rew_ld, done, done_ld, flags,
-                     reinterpret_cast<const float4*>(next_small), (int)(small_ld / 4), idx, nsel, nrows, stride, n, gamma, ret_out, done_out,
-                     discount_out, reinterpret_cast<float4*>(next_small_out), steps_out, tail_out);
-  DGVIT_CHECK_LAUNCH("nstep_walk_strided");
-  return DGVIT_OK;
+  return launch_nstep_walk("nstep_walk_strided", rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, &stride, n, gamma,
+                           ret_out, done_out, discount_out, next_small_out, steps_out, tail_out, stream);
 }

@@ -76,12 +76,13 @@ class DeviceReplayBuffer:
     is exact for the reference's k / 255 frames and round-to-nearest otherwise (error at most 1/510 + 2^-23).  ``sample`` returns fp32
     frames, bit-equal to numpy's and CPU torch's ``codes / 255`` in fp32.  With a uint8 ring ``add`` / ``add_batch`` take each frame
     field, independently, as host floats (they travel in the one staged matrix and are quantised from it), as host uint8 (numpy or CPU
-    tensor: the codes themselves, staged as bytes) or as a device tensor, fp32 or uint8, which never visits the host.  Buffers have no
+    tensor: the codes themselves, four to a float of the same matrix) or as a device tensor, fp32 or uint8.  A device tensor given to
+    ``add`` / ``add_batch`` never visits the host, whatever the ring's format and whichever field it is.  Buffers have no
     ``state_dict``.
 
     Episodes.  ``episode_flags`` is None until ``track_episodes()``, ``on_episode_end()`` or ``sample(n_step=...)`` is first
-    used; from then on it is a (size,) uint8 device tensor that the store path keeps current with one more launch per ``add`` /
-    ``add_batch``: bit 0 (END) marks the last transition of an episode, whatever its ``done`` says (time limits, truncations -- the
+    used; from then on it is a (size,) uint8 device tensor that the store path keeps current, inside the second launch of an ``add`` or
+    ``add_vec`` and with one more launch per ``add_batch``: bit 0 (END) marks the last transition of an episode, whatever its ``done`` says (time limits, truncations -- the
     reference fetches ``done`` and never applies it, so ``done`` alone cannot mark episodes), bit 1 (HEAD) the newest slot written.  A
     buffer that never uses them allocates nothing and launches nothing more than before.  Episode ends before tracking started are
     unknown, apart from ``done``: call ``track_episodes()`` before the first ``add`` if n-step sampling is meant.  ``add_batch`` writes
@@ -179,101 +180,101 @@ class DeviceReplayBuffer:
         self.episode_flags[base:base + E].bitwise_or_(mask)
 
     def _travel(self, k, v, n):
-        """How field k of n transitions travels into the ring: ("floats", (n, cnt) fp32 array), in the one staged matrix -- every field of
-        an fp32 ring, device tensors included, and every non-frame field --, or, for a frame field of a uint8 ring, also ("bytes", (n, H*W)
-        uint8 array: the codes themselves) or ("device", (n, H*W) fp32 or uint8 tensor on self.device)."""
-        frame_u8 = self.frame_dtype is torch.uint8 and k in FRAME_FIELDS
-        if frame_u8 and torch.is_tensor(v) and v.device.type != "cpu":
+        """Field k of n transitions as add / add_batch take it -- any dtype, a tensor on any device, a scalar for ``rew`` / ``done``, any
+        shape that reshapes to (n, cnt); uint8 means codes for a frame field of a uint8 ring and the values 0..255 everywhere else -- in
+        the form ``_vec_field`` returns.  A device tensor stays on the device and is converted there if it must be."""
+        codes_ok = self.frame_dtype is torch.uint8 and k in FRAME_FIELDS
+        if torch.is_tensor(v) and v.device.type != "cpu":
             v = v.detach().to(self.device)
-            v = (v if v.dtype in (torch.uint8, torch.float32) else v.float()).reshape(n, -1).contiguous()
-            kind = "device"
+            v = (v if v.dtype == torch.float32 or (codes_ok and v.dtype == torch.uint8) else v.float()).reshape(n, -1).contiguous()
         else:
             if torch.is_tensor(v):
-                v = v.detach().cpu()
-                v = (v if v.dtype == torch.uint8 else v.float()).numpy()
-            elif frame_u8:
-                v = np.asarray(v)
-            kind = "bytes" if frame_u8 and v.dtype == np.uint8 else "floats"
-            v = np.asarray(v, dtype=np.uint8 if kind == "bytes" else np.float32).reshape(n, -1)
+                v = (v if v.dtype == torch.uint8 else v.detach().float()).numpy()
+            v = np.asarray(v)
+            v = np.ascontiguousarray(v.reshape(n, -1), dtype=np.uint8 if codes_ok and v.dtype == np.uint8 else np.float32)
         if v.shape[1] != self.fields[k]:
             raise ValueError(f"{k}: expected {self.fields[k]} values per transition, got {v.shape[1]}")
-        return kind, v
+        return v
 
-    def _ring_copy(self, k, rows, i, first) -> None:
-        """device rows (n, cnt) -> ring slots i .. of field k (ring wrap = two slices); the padding columns stay zero"""
-        cnt, n = self.fields[k], rows.shape[0]
-        self.store[k][i:i + first, :cnt].copy_(rows[:first])
-        if first < n:
-            self.store[k][:n - first, :cnt].copy_(rows[first:])
+    def _commit(self, rows, n, end=None) -> None:
+        """The one store path of add, add_batch and add_vec: ``rows`` holds every field of n <= size transitions as ``_vec_field`` returns
+        it, ``end`` the episode ends of an ``add_vec``, normalised.  Every host field's columns lie side by side in ONE staged fp32 matrix,
+        each block a multiple of 4 floats wide (codes four to a float), and behind its n rows the n ends of a host ``end``: one
+        host->device copy from pinned memory -- the reference converts and copies every field of every sampled batch instead
+        (DRL.py:379-386).  Which fields the matrix holds is the call's, so its column offsets are too.  Then dgvit_ring_store_frames for
+        ``obs`` and ``next_obs`` and dgvit_ring_store_small for the other five fields, both wrapping the ring per row.  The marks of one
+        step (n == num_envs: ``add``, ``add_vec``) are the second launch's; a longer run of one episode's slots (``add_batch``) is marked
+        by dgvit_ring_mark, only its last slot the HEAD, and only when episodes are tracked."""
+        off, row = {}, 0
+        for k, v in rows.items():
+            if not torch.is_tensor(v):
+                off[k] = row
+                row += _al4(self.fields[k]) if v.dtype == np.float32 else _al4(_al4(self.fields[k]) // 4)
+        host_end = end is not None and not torch.is_tensor(end)
+        dev = None
+        if off or host_end:
+            host = np.zeros(n * row + (n if host_end else 0), dtype=np.float32)
+            mat = host[:n * row].reshape(n, row)
+            for k, o in off.items():
+                if rows[k].dtype == np.float32:
+                    mat[:, o:o + self.fields[k]] = rows[k]
+                else:
+                    mat.view(np.uint8)[:, 4 * o:4 * o + self.fields[k]] = rows[k]
+            if host_end:
+                host[n * row:] = end
+            stage = torch.from_numpy(host).pin_memory()
+            dev = stage.to(self.device, non_blocking=True)
+            self._last_stage = [stage, dev]      # keep the pinned buffer alive until the async copy has certainly been issued
 
-    def _store(self, kw, n) -> None:
-        """add / add_batch of both ring kinds.  Every field that travels as host floats (``_travel``) lies side by side in ONE staged fp32
-        matrix: one host->device copy from pinned memory, then device-side copies into the field matrices -- the reference converts and
-        copies every field of every sampled batch instead (DRL.py:379-386).  A uint8 ring differs only in its frame fields: host floats
-        are quantised straight from the staged matrix by one dgvit_quantize_rows_u8 launch (the ring wrap inside it), host uint8 is
-        staged as bytes (one byte matrix, one copy) and copied into the ring, device tensors are quantised (fp32) or copied (uint8)
-        where they are.  Which frame fields the matrix holds is the call's, so its column offsets are too: fixed ones would stage
-        2 H W unused floats per transition whenever the frames come as bytes or from the device."""
+        def source(k):
+            """(pointer, 1 for uint8 codes, row stride in elements) of field k's rows on the device"""
+            v = rows[k]
+            if torch.is_tensor(v):
+                return v.data_ptr(), int(v.dtype == torch.uint8), self.fields[k]
+            codes = v.dtype == np.uint8
+            return dev.data_ptr() + 4 * off[k], int(codes), 4 * row if codes else row
+
+        lib, st, i = _lib.load(), _stream(), self.next_index
+        u8 = self.frame_dtype is torch.uint8
+        small = _lib.dgvit_small_fields()
+        for j, k in enumerate(SMALL_FIELDS):
+            small.src[j], _, small.src_ld[j] = source(k)
+            small.ring[j], small.cols[j], small.ring_ld[j] = self.store[k].data_ptr(), self.fields[k], self.rows[k]
+        end_ptr = None if end is None else (end.data_ptr() if torch.is_tensor(end) else dev.data_ptr() + 4 * n * row)
+        end_f32 = int(host_end or (end is not None and end.dtype == torch.float32))
+        step = n == self.num_envs
+        with torch.cuda.device(self.device):
+            (p0, c0, ld0), (p1, c1, ld1) = source("obs"), source("next_obs")
+            rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
+                                             self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, st)
+            _lib.check(rc, "dgvit_ring_store_frames")
+            rc = lib.dgvit_ring_store_small(small, _ptr(self.episode_flags if step else None), end_ptr, end_f32, n, self.size, i, st)
+            _lib.check(rc, "dgvit_ring_store_small")
+            if self.episode_flags is not None and not step:
+                _lib.check(lib.dgvit_ring_mark(_ptr(self.episode_flags), self.size, i, n, st), "dgvit_ring_mark")
+        self.next_index = (i + n) % self.size
+        self.stored = min(self.stored + n, self.size)
+        self._on_store(i, n)
+
+    def _add(self, kw, n) -> None:
+        """add / add_batch: of n > size transitions the last ``size`` are the ones that stay"""
         if self.num_envs > 1:
             raise _lib.DgvitError(f"add() / add_batch() write consecutive slots of one episode, and this ring has num_envs={self.num_envs} "
                                   "lanes: store a step of all environments with add_vec()")
         for k in self.fields:
             if k not in kw:
                 raise KeyError(f"missing field {k}")
-        rows = {k: self._travel(k, kw[k], n) for k in self.fields}
-        off, row = {}, 0
-        for k in self.fields:
-            if rows[k][0] == "floats":
-                off[k] = row
-                row += self.rows[k]
-        host = np.zeros((n, row), dtype=np.float32)
-        for k, o in off.items():
-            host[:, o:o + self.fields[k]] = rows[k][1]
-        drop = max(n - self.size, 0)             # n > size: the last `size` transitions are the ones that stay
-        n -= drop
-        stage = torch.from_numpy(host[drop:]).pin_memory()
-        dev = stage.to(self.device, non_blocking=True)
-        keep = [stage, dev]
-        as_bytes = [k for k in FRAME_FIELDS if rows[k][0] == "bytes"]
-        if as_bytes:
-            cnt = self.fields["obs"]
-            bstage = torch.empty(n, len(as_bytes) * cnt, dtype=torch.uint8).pin_memory()
-            for j, k in enumerate(as_bytes):
-                bstage.numpy()[:, j * cnt:(j + 1) * cnt] = rows[k][1][drop:]
-            bdev = bstage.to(self.device, non_blocking=True)
-            keep += [bstage, bdev]
-        i = self.next_index
-        first = min(n, self.size - i)
-        with torch.cuda.device(self.device):
-            for k, cnt in self.fields.items():
-                kind, v = rows[k]
-                if kind == "bytes":
-                    j = as_bytes.index(k)
-                    self._ring_copy(k, bdev[:, j * cnt:(j + 1) * cnt], i, first)
-                elif kind == "device" and v.dtype == torch.uint8:
-                    self._ring_copy(k, v[drop:], i, first)
-                elif self.store[k].dtype == torch.float32:
-                    self._ring_copy(k, dev[:, off[k]:off[k] + cnt], i, first)
-                else:                            # fp32 rows, staged or on the device, into a byte ring
-                    src, ld = (dev[:, off[k]:], row) if kind == "floats" else (v[drop:], cnt)
-                    rc = _lib.load().dgvit_quantize_rows_u8(_ptr(src), ld, _ptr(self.store[k]), n, cnt, self.row_bytes, self.size, i, _stream())
-                    _lib.check(rc, "dgvit_quantize_rows_u8")
-            if self.episode_flags is not None:   # one launch: the written slots forget their marks, the last of them is the HEAD
-                _lib.check(_lib.load().dgvit_ring_mark(_ptr(self.episode_flags), self.size, i, n, _stream()), "dgvit_ring_mark")
-        self._last_stage = keep                  # keep the pinned buffers alive until the async copies have certainly been issued
-        self.next_index = (i + n) % self.size
-        self.stored = min(self.stored + n, self.size)
-        self._on_store(i, n)
+        self._commit({k: self._travel(k, kw[k], n)[-self.size:] for k in self.fields}, min(n, self.size))
 
     def add(self, **kw) -> None:
-        """One transition (numpy arrays / scalars / tensors), same keywords as replay_buffer.add in DRL.py:439-448:
-        one staged host->device copy for the whole transition."""
-        self._store(kw, 1)
+        """One transition (numpy arrays / scalars / tensors), same keywords as replay_buffer.add in DRL.py:439-448: one staged
+        host->device copy for the host fields of the whole transition and two launches (``_commit``)."""
+        self._add(kw, 1)
 
     def add_batch(self, **kw) -> None:
         """Many transitions at once (first axis = transitions), e.g. the expert demonstrations of DRL.py:469-478: assembled on
-        the host with numpy slicing, one host->device copy."""
-        self._store(kw, len(kw["obs"]))
+        the host with numpy slicing, one host->device copy, two launches and a third for the marks when episodes are tracked."""
+        self._add(kw, len(kw["obs"]))
 
     def _vec_field(self, k, v):
         """Field k of one vector step, checked -> the (E, cnt) device tensor where it lies (fp32, or the uint8 codes of a frame of a uint8
@@ -312,73 +313,26 @@ class DeviceReplayBuffer:
         environment e's transition of this step is the last of its episode, whatever its ``done`` says: ``on_episode_end()``'s meaning.
         Passing it starts ``track_episodes()`` if nothing has, so the first such call must happen outside a capture.
 
-        Two launches: dgvit_ring_store_frames for ``obs`` and ``next_obs``, dgvit_ring_store_small for the other five fields and, when
-        episodes are tracked, the marks (the new slots get HEAD, and END where ``episode_end`` says so; the previous step's slots keep only
-        their END); the prioritized subclass adds its dgvit_per_set_range.  With every field and ``episode_end`` on the device nothing
+        Two launches (``_commit``): dgvit_ring_store_frames for ``obs`` and ``next_obs``, dgvit_ring_store_small for the other five fields
+        and, when episodes are tracked, the marks (the new slots get HEAD, and END where ``episode_end`` says so; the previous step's slots
+        keep only their END); the prioritized subclass adds its dgvit_per_set_range.  With every field and ``episode_end`` on the device nothing
         synchronises with the host and nothing pinned is allocated.  ``num_envs == 1`` is allowed: the device-side ``add``."""
         E, kw = self.num_envs, dict(obs=obs, pobs=pobs, act=act, rew=rew, next_obs=next_obs, next_pobs=next_pobs, done=done)
         rows = {k: self._vec_field(k, kw[k]) for k in self.fields}
-        end, end_f32 = episode_end, 0
+        end = episode_end
         if end is not None:
             if torch.is_tensor(end) and end.device.type != "cpu":
                 if end.device != self.store["obs"].device or end.dtype not in (torch.bool, torch.uint8, torch.float32) or end.numel() != E:
                     raise ValueError(f"episode_end: a device tensor must be ({E},) bool, uint8 or float32 on {self.store['obs'].device}, got "
                                      f"{tuple(end.shape)} {end.dtype} on {end.device}")
-                end, end_f32 = end.detach().reshape(E).contiguous(), int(end.dtype == torch.float32)
+                end = end.detach().reshape(E).contiguous()
             else:
                 end = np.asarray(end.detach().numpy() if torch.is_tensor(end) else end).reshape(-1)
                 if end.size != E:
                     raise ValueError(f"episode_end: expected {E} entries, got {end.size}")
-                end, end_f32 = (end != 0).astype(np.float32), 1
+                end = (end != 0).astype(np.float32)
             self.track_episodes()
-        # the staged matrix: every host field's columns side by side, each block a multiple of 4 floats wide (codes four to a float), and
-        # behind its E rows the E episode ends of a host episode_end
-        off, row = {}, 0
-        for k, v in rows.items():
-            if not torch.is_tensor(v):
-                off[k] = row
-                row += _al4(self.fields[k]) if v.dtype == np.float32 else _al4(_al4(self.fields[k]) // 4)
-        host_end = end is not None and not torch.is_tensor(end)
-        dev = None
-        if off or host_end:
-            host = np.zeros(E * row + (E if host_end else 0), dtype=np.float32)
-            mat = host[:E * row].reshape(E, row)
-            for k, o in off.items():
-                if rows[k].dtype == np.float32:
-                    mat[:, o:o + self.fields[k]] = rows[k]
-                else:
-                    mat.view(np.uint8)[:, 4 * o:4 * o + self.fields[k]] = rows[k]
-            if host_end:
-                host[E * row:] = end
-            stage = torch.from_numpy(host).pin_memory()
-            dev = stage.to(self.device, non_blocking=True)
-            self._last_stage = [stage, dev]      # keep the pinned buffer alive until the async copy has certainly been issued
-
-        def source(k):
-            """(pointer, 1 for uint8 codes, row stride in elements) of field k's rows on the device"""
-            v = rows[k]
-            if torch.is_tensor(v):
-                return v.data_ptr(), int(v.dtype == torch.uint8), self.fields[k]
-            codes = v.dtype == np.uint8
-            return dev.data_ptr() + 4 * off[k], int(codes), 4 * row if codes else row
-
-        lib, st, i = _lib.load(), _stream(), self.next_index
-        u8 = self.frame_dtype is torch.uint8
-        small = _lib.dgvit_small_fields()
-        for j, k in enumerate(SMALL_FIELDS):
-            small.src[j], _, small.src_ld[j] = source(k)
-            small.ring[j], small.cols[j], small.ring_ld[j] = self.store[k].data_ptr(), self.fields[k], self.rows[k]
-        end_ptr = None if end is None else (end.data_ptr() if torch.is_tensor(end) else dev.data_ptr() + 4 * E * row)
-        with torch.cuda.device(self.device):
-            (p0, c0, ld0), (p1, c1, ld1) = source("obs"), source("next_obs")
-            rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
-                                             self.row_bytes if u8 else self.rows["obs"], E, self.fields["obs"], self.size, i, st)
-            _lib.check(rc, "dgvit_ring_store_frames")
-            rc = lib.dgvit_ring_store_small(small, _ptr(self.episode_flags), end_ptr, end_f32, E, self.size, i, st)
-            _lib.check(rc, "dgvit_ring_store_small")
-        self.next_index = (i + E) % self.size
-        self.stored = min(self.stored + E, self.size)
-        self._on_store(i, E)
+        self._commit(rows, E, end)
 
     def sample_indices(self, batch_size: int) -> torch.Tensor:
         if self.stored == 0:

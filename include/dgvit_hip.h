@@ -393,7 +393,8 @@ int dgvit_gather_shift_frames(const float* src, const long long* idx /* may be N
  * dgvit_quantize_rows_u8:  ring[(start + i) % nrows][c] = q(src[i * src_ld + c])   for i < n, c < cols
  *     q(x) = (uint8) rintf(fminf(fmaxf(x * 255.0f, 0), 255))      half to even; NaN, -0 and -inf store 0, +inf stores 255
  *   The ring wrap happens inside the one launch.  src_ld >= cols is in floats (src 4-byte aligned), so src may be a column block of a
- *   staged matrix or a frame tensor.  0 <= start < nrows, 1 <= n <= nrows, cols <= 2^25.
+ *   staged matrix or a frame tensor.  0 <= start < nrows, 1 <= n <= nrows, cols <= 2^25.  No longer used by the Python
+ *   package, whose one store path is dgvit_ring_store_frames + dgvit_ring_store_small.
  * dgvit_gather_rows_u8:    out[i][c] = (float)ring[clamp(idx[i], 0, nrows-1)][c] / 255.0f      for i < nsel, c < cols
  *   The correctly rounded quotient, bit-equal to numpy's and CPU torch's uint8 -> float32 / 255.  A multiplication by 1.0f / 255.0f is
  *   not (it differs in 126 of the 256 codes); the kernels form the quotient as that product plus one Newton correction in two fused
@@ -464,8 +465,10 @@ int dgvit_nstep_walk(const float* rew, long long rew_ld, const float* done, long
  *     ring[f][(start + i) % nrows][c] = src[f][i * src_ld[f] + c]   for c < cols[f], zeros up to ring_ld[f] (a multiple of 4 floats)
  *     flags[(start + i) % nrows]      = HEAD | (episode_end && episode_end[i] != 0 ? END : 0)
  *     flags[(start - n + i) % nrows] &= END                         the previous step is no longer the newest; skipped when n == nrows
- *   episode_end may be NULL (no ends); it is n bytes (bool / uint8; end_f32 == 0) or n floats (end_f32 == 1), nonzero = end.  n must
- *   divide nrows (so the previous step's slots are not the written ones); 1 <= cols[f] <= ring_ld[f] <= 2^20, src_ld[f] >= cols[f].
+ *   episode_end may be NULL (no ends); it is n bytes (bool / uint8; end_f32 == 0) or n floats (end_f32 == 1), nonzero = end.  With
+ *   flags, n must divide nrows (so the previous step's slots are not the written ones); with flags == NULL nothing but the n written
+ *   rows is touched, any 1 <= n <= nrows is taken and the rows may cross the ring's end (add_batch, which marks with dgvit_ring_mark).
+ *   1 <= cols[f] <= ring_ld[f] <= 2^20, src_ld[f] >= cols[f].
  * dgvit_nstep_walk_strided: dgvit_nstep_walk with s_k = (i + k * stride) mod nrows, 1 <= stride <= nrows; everything else, every
  *   output and every check as there.  stride == 1 gives the bits of dgvit_nstep_walk.  i + 63 * stride may exceed 2 * nrows (a ring of
  *   fewer than 64 steps): the slot is then reduced by a true modulo, by one subtraction where that is enough.

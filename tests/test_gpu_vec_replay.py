@@ -247,6 +247,12 @@ def test_all_device_add_vec_never_synchronises(amd, monkeypatch):
         kw, _ = _step(d, t, "device", False)
         calls.append((kw, _dev(d["end"][t] | (t == 1))))
     idx = _dev(np.array([1], np.int64))
+    # add and add_batch with every field on the device: single-environment rings, episodes tracked so that the marks run too
+    singles = [_buffer(1, SIZE, cls=cls, frame_dtype=dtype) for cls, dtype, with_end in cases if with_end]
+    for s in singles:
+        s.track_episodes()
+    three = {k: v for k, v in calls[0][0].items() if k != "episode_end"}
+    one = {k: v[0] for k, v in calls[1][0].items() if k != "episode_end"}
     torch.cuda.synchronize()
 
     def run():
@@ -256,6 +262,9 @@ def test_all_device_add_vec_never_synchronises(amd, monkeypatch):
                 if with_end:
                     buf.on_episode_end(envs=mask)
                     buf.on_episode_end(envs=idx)
+        for s in singles:
+            s.add(**one)
+            s.add_batch(**three)
 
     with monkeypatch.context() as m:
         for name in ("cpu", "item", "tolist", "numpy"):
@@ -287,6 +296,11 @@ def test_all_device_add_vec_never_synchronises(amd, monkeypatch):
             base = buf.next_index - E3
             want = [N.HEAD | N.END if (e == 1 or d["end"][2][e]) else N.HEAD for e in range(E3)]
             assert buf.episode_flags[base:base + E3].cpu().tolist() == want
+    for s in singles:                                      # one add and one add_batch of three per run
+        n = 8 if detects else 4
+        assert (s.stored, s.next_index) == (n, n) and s.episode_flags.cpu().tolist() == [0] * (n - 1) + [N.HEAD] + [0] * (SIZE - n)
+        got = s.store["pobs"][n - 4:n, :V.PSTATE].cpu().numpy()
+        assert np.array_equal(got, np.concatenate([d["pobs"][1][:1], d["pobs"][0]])), "the add's row, then the batch's three"
 
 
 # ------------------------------------------------------------------------------------------------ 4. both wrap paths of the strided walk

@@ -9,6 +9,8 @@ median and their range, printed and written to --out:
   kernel_gather_rows_fp32 / _u8      the plain frame gather on the obs field (100 launches after 10, device events), with the bytes each
                                      moves over its time: fp32 reads and writes B x 20 480 floats, u8 reads a quarter and writes the same
   kernel_gather_shift_fp32 / _u8     the shifted frame gather (pad 4), same counts
+  kernel_quantize_u8                 dgvit_quantize_rows_u8 on B rows of an fp32 device matrix into the byte ring, same counts: reads B x
+                                     20 480 floats and writes as many bytes
   sample_fp32 / sample_u8            the whole sample(B): seven launches and the index draw (20 calls after 5, device events)
   add_batch_fp32_floats / add_batch_u8_floats / add_batch_u8_bytes
                                      add_batch of 512 host frames (wall clock around the call and a synchronize, 5 calls after 2)
@@ -111,6 +113,11 @@ def main():
         L.check(lib.dgvit_gather_shift_frames_u8(p(s8), p(idx), p(out), None, B, H, W, H * W, H * W, ring, PAD, 0, 12345, None, st),
                 "dgvit_gather_shift_frames_u8")
 
+    frames32 = torch.rand(B, H * W, device="cuda", generator=g)
+
+    def k_quantize8():                                      # the exported entry point alone; the package stores through ring_store_frames
+        L.check(lib.dgvit_quantize_rows_u8(p(frames32), H * W, p(s8), B, H * W, H * W, ring, 0, st), "dgvit_quantize_rows_u8")
+
     k_rows32()
     want = out.clone()
     k_rows8()
@@ -124,6 +131,7 @@ def main():
 
     forms = [("kernel_gather_rows_fp32", k_rows32, 100, 10, _timed), ("kernel_gather_rows_u8", k_rows8, 100, 10, _timed),
              ("kernel_gather_shift_fp32", k_shift32, 100, 10, _timed), ("kernel_gather_shift_u8", k_shift8, 100, 10, _timed),
+             ("kernel_quantize_u8", k_quantize8, 100, 10, _timed),
              ("sample_fp32", lambda: buf32.sample(B), 20, 5, _timed), ("sample_u8", lambda: buf8.sample(B), 20, 5, _timed),
              ("add_batch_fp32_floats", lambda: buf32.add_batch(**small, **floats), 5, 2, _walled),
              ("add_batch_u8_floats", lambda: buf8.add_batch(**small, **floats), 5, 2, _walled),

@@ -8,9 +8,9 @@
 vector step (wall clock around the calls and a final synchronize, so the host's share is in it):
   add_vec_device      add_vec with every field a device tensor: two launches, no host visit
   add_vec_host        add_vec with every field a numpy array: one pinned staging matrix, one copy, the same two launches
-  add_batch_device    the single-environment route, add_batch of the same E transitions given as device tensors (every non-frame field,
-  add_batch_host      and every frame of an fp32 ring, goes through the host), and given as numpy arrays.  It lays E different episodes
-                      in consecutive slots, which n-step sampling would walk across: it is timed for its cost, not for its meaning
+  add_batch_device    the single-environment route, add_batch of the same E transitions given as device tensors (since DESIGN 3.36 the
+  add_batch_host      same two launches and no host visit), and given as numpy arrays.  It lays E different episodes in consecutive
+                      slots, which n-step sampling would walk across: it is timed for its cost, not for its meaning
 and, with device events around 1000 launches after 50 (200 samples after 10):
   kernel_store_frames dgvit_ring_store_frames alone, the two frame fields of the step
   copy_frames         its yardstick: tensor.copy_ of the same source bytes, two (E, H W) fp32 tensors into ring-shaped fp32 rows
