@@ -135,6 +135,7 @@ SIGNATURES = {
     "dgvit_grad_sqnorm_partials": (_I, [_P, _LL, _P, _I, _P]),
     "dgvit_grad_clip_coef": (_I, [_P, _F, _P, _P]),
     "dgvit_adam_step_scaled": (_I, [_P, _P, _P, _P, _LL, _F, _F, _F, _F, _F, _LL, _P, _P, _P]),
+    "dgvit_adam_step_groups": (_I, [_P, _P, _P, _P, _LL, _P, _P, _I, _P, _I, _P, _F, _F, _F, _I, _LL, _LL, _P, _I, _LL, _LL, _F, _P, _P]),
     "dgvit_scale_by_device_scalar": (_I, [_P, _LL, _P, _P]),
     # the SAC loss head (include/dgvit_hip.h: The SAC loss head)
     "dgvit_sac_critic_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _I, _P]),

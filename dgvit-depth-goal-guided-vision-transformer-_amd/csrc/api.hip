@@ -238,6 +238,14 @@ extern "C" int dgvit_adam_step_scaled(float* p, const float* g, float* m, float*
 extern "C" int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, void* stream) {
   return scale_by_device_scalar(x, n, scale_dev, (hipStream_t)stream);
 }
+extern "C" int dgvit_adam_step_groups(float* p, const float* g, float* m, float* v, long long n, const long long* seg_end4,
+                                      const unsigned char* seg_group, int nseg, const float* group_hyper, int ngroups, float* lr_out,
+                                      float beta1, float beta2, float eps, int decoupled, long long step, long long sched_step,
+                                      const long long* step_dev, int sched_kind, long long warmup_steps, long long total_steps,
+                                      float final_ratio, const float* grad_scale_dev, void* stream) {
+  return adam_step_groups(p, g, m, v, n, seg_end4, seg_group, nseg, group_hyper, ngroups, lr_out, beta1, beta2, eps, decoupled, step, sched_step,
+                          step_dev, sched_kind, warmup_steps, total_steps, final_ratio, grad_scale_dev, (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- SAC loss head (sac_loss.hip)
 extern "C" int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,

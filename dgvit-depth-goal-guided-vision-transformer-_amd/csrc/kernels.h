@@ -57,6 +57,11 @@ int grad_clip_coef(const double* partials, float max_norm, float* out, hipStream
 int adam_step_scaled(float*, const float*, float*, float*, long long, float, float, float, float, float, long long, const long long*,
                      const float* grad_scale_dev, hipStream_t);
 int scale_by_device_scalar(float* x, long long n, const float* scale_dev, hipStream_t);
+// Adam / AdamW with parameter groups and a device-side lr schedule, one launch per run (optim.hip)
+int adam_step_groups(float* p, const float* g, float* m, float* v, long long n, const long long* seg_end4, const unsigned char* seg_group,
+                     int nseg, const float* group_hyper, int ngroups, float* lr_out, float beta1, float beta2, float eps, int decoupled,
+                     long long step, long long sched_step, const long long* step_dev, int sched_kind, long long warmup_steps,
+                     long long total_steps, float final_ratio, const float* grad_scale_dev, hipStream_t);
 // the SAC loss head (sac_loss.hip): one launch per loss, alpha from device memory; done, weights, discount, log_alpha, td and
 // grads may be null; discount (B values) takes the place of gamma sample by sample
 int sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights, const float* discount,

@@ -9,6 +9,9 @@
 //   grad_clip_coef         : partials -> total norm and the clamped coefficient max_norm / (norm + 1e-6), both left on the device
 //   adam_step_scaled       : adam_step with the gradient multiplied by that device-side coefficient as it is read (still 28 B/parameter)
 //   scale_by_device_scalar : x <- x * *scale, the in-place form for a stand-alone clip (8 B/parameter)
+// Parameter groups and learning-rate schedules (torch.optim.AdamW, warm-up + cosine / linear decay):
+//   adam_step_groups       : the step over one run whose elements belong to groups with their own (lr, weight decay), L2 or decoupled
+//                            decay, the schedule factor computed on the device -- still one launch and 28 B/parameter
 #include "common.h"
 #include "kernels.h"
 
@@ -48,6 +51,106 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     for (int e = 0; e < 4; ++e) {
       if (SCALED) ge[e] = mul_rounded(gscale, ge[e]);
       const float gg = ge[e] + wd * pe[e];
+      me[e] = beta1 * me[e] + (1.f - beta1) * gg;
+      ve[e] = beta2 * ve[e] + (1.f - beta2) * gg * gg;
+      pe[e] -= lr_c * me[e] / (sqrtf(ve[e]) * inv_sqrt_bc2 + eps);
+    }
+    reinterpret_cast<float4*>(p)[i] = make_float4(pe[0], pe[1], pe[2], pe[3]);
+    reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
+    reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
+  }
+}
+
+// Parameter groups and a device-side learning-rate schedule in the same single pass.  The run [0, n4) is cut into nseg
+// segments (seg_end4: ascending ends in float4 units, seg_group: the group of each); a group is (lr, weight_decay).  Every workgroup
+// stages both segment tables and the per-group constants into LDS once; a lane then keeps a cursor k into the segment table: its index
+// only grows along the grid-stride walk, so the cursor only moves forward -- one LDS read (a broadcast: a wave's 64 consecutive float4s
+// nearly always share a segment) while the lane stays inside its segment, a binary search over the REMAINING segments when it left it.
+// The four global loads of an iteration are issued before the lookup, so the LDS round trips wait under the HBM latency.  Which element
+// gets which group depends on i alone: the result does not depend on the grid.
+//   f      : the schedule factor, by thread 0 in double from the number of steps already taken, rounded to fp32 once
+//   lr_t   : lr * f (one fp32 product); bias corrections ALWAYS by the device formula of adam_kernel's step_dev branch, from
+//            t = *step_dev or the host's step: an eager and a captured step run the same instructions on the same values
+//   L2     : adam_kernel's lines with the group's wd and lr_c            DECOUPLED : p *= 1 - lr_t * wd first, moments from the raw g
+constexpr int ADAM_MAX_SEGMENTS = 2048, ADAM_MAX_GROUPS = 256;
+template <bool SCALED, bool DECOUPLED>
+__global__ void __launch_bounds__(256) adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, long long n4, const long long* __restrict__ seg_end4,
+                                                          const unsigned char* __restrict__ seg_group, int nseg,
+                                                          const float* __restrict__ group_hyper, int ngroups, float* __restrict__ lr_out,
+                                                          float beta1, float beta2, float eps, long long step, long long sched_step,
+                                                          const long long* __restrict__ step_dev, int sched_kind, long long warmup_steps,
+                                                          long long total_steps, float final_ratio,
+                                                          const float* __restrict__ grad_scale_dev) {
+  __shared__ long long s_end[ADAM_MAX_SEGMENTS];
+  __shared__ unsigned char s_grp[ADAM_MAX_SEGMENTS];
+  // L2: lr_c, wd      DECOUPLED: lr_c, 1 - lr_t * wd.  20480 bytes of LDS in all: eight workgroups per CU, the whole grid resident
+  __shared__ float s_lrc[ADAM_MAX_GROUPS], s_wd[ADAM_MAX_GROUPS];
+  float gscale = 1.f;
+  if (SCALED) gscale = *grad_scale_dev;
+  const long long t_dev = step_dev ? *step_dev : step;
+  if (threadIdx.x == 0) {
+    const long long s = (step_dev ? t_dev : sched_step) - 1;   // steps already taken
+    double f;
+    if (s < warmup_steps) {
+      f = (double)(s + 1) / (double)warmup_steps;
+    } else {
+      const long long span = total_steps - warmup_steps;
+      double q = (double)(s - warmup_steps) / (double)(span > 1 ? span : 1);
+      q = q < 1.0 ? q : 1.0;
+      const double r = (double)final_ratio;
+      f = sched_kind == 1 ? r + (1.0 - r) * 0.5 * (1.0 + cospi(q)) : sched_kind == 2 ? r + (1.0 - r) * (1.0 - q) : 1.0;
+    }
+    s_lrc[0] = (float)f;   // (handed to the workgroup through a slot that is filled for good after the next barrier)
+  }
+  for (int k = threadIdx.x; k < nseg; k += 256) {
+    s_end[k] = seg_end4[k];
+    const int gr = seg_group[k];
+    s_grp[k] = (unsigned char)(gr < ngroups ? gr : ngroups - 1);   // (a table that breaks its contract still indexes inside the LDS)
+  }
+  __syncthreads();
+  const float f = s_lrc[0];
+  __syncthreads();
+  const float t = (float)t_dev;
+  const float bc1 = 1.f - powf(beta1, t);
+  const float inv_sqrt_bc2 = rsqrtf(1.f - powf(beta2, t));
+  if ((int)threadIdx.x < ngroups) {
+    const float lr_t = mul_rounded(group_hyper[2 * threadIdx.x], f);
+    const float wd = group_hyper[2 * threadIdx.x + 1];
+    s_lrc[threadIdx.x] = lr_t / bc1;
+    s_wd[threadIdx.x] = DECOUPLED ? (float)(1.0 - (double)lr_t * (double)wd) : wd;
+    if (lr_out && blockIdx.x == 0) lr_out[threadIdx.x] = lr_t;
+  }
+  __syncthreads();
+  const long long stride = (long long)gridDim.x * 256;
+  int k = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv0 = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    if (i >= s_end[k]) {   // left the segment: the first one that ends beyond i, among those after k
+      int lo = k + 1, hi = nseg - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (i < s_end[mid]) hi = mid; else lo = mid + 1;
+      }
+      k = lo < nseg ? lo : nseg - 1;
+    }
+    const int gr = s_grp[k];
+    const float lr_c = s_lrc[gr], wd = s_wd[gr];
+    float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv0.x, gv0.y, gv0.z, gv0.w};
+    float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (SCALED) ge[e] = mul_rounded(gscale, ge[e]);
+      float gg;
+      if (DECOUPLED) {
+        pe[e] = mul_rounded(pe[e], wd);
+        gg = ge[e];
+      } else {
+        gg = ge[e] + wd * pe[e];
+      }
       me[e] = beta1 * me[e] + (1.f - beta1) * gg;
       ve[e] = beta2 * ve[e] + (1.f - beta2) * gg * gg;
       pe[e] -= lr_c * me[e] / (sqrtf(ve[e]) * inv_sqrt_bc2 + eps);
@@ -191,6 +294,46 @@ int adam_step_scaled(float* p, const float* g, float* m, float* v, long long n, 
                        (float)(1.0 / sqrt(bc2)), eps, weight_decay, lr, step_dev, grad_scale_dev);
   }
   DGVIT_CHECK_LAUNCH("adam_step_scaled");
+  return DGVIT_OK;
+}
+
+// Adam / AdamW over one run with parameter groups and a learning-rate schedule evaluated on the device (adam_groups_kernel above).
+// Everything is refused here, before any launch, that the kernel could not survive or would silently misread.
+int adam_step_groups(float* p, const float* g, float* m, float* v, long long n, const long long* seg_end4, const unsigned char* seg_group,
+                     int nseg, const float* group_hyper, int ngroups, float* lr_out, float beta1, float beta2, float eps, int decoupled,
+                     long long step, long long sched_step, const long long* step_dev, int sched_kind, long long warmup_steps,
+                     long long total_steps, float final_ratio, const float* grad_scale_dev, hipStream_t stream) {
+  DGVIT_CHECK_ARG(p && g && m && v, "adam_step_groups: p, g, m and v must not be null");
+  DGVIT_CHECK_ARG(seg_end4 && seg_group, "adam_step_groups: seg_end4 and seg_group must not be null");
+  DGVIT_CHECK_ARG(group_hyper, "adam_step_groups: group_hyper must not be null");
+  DGVIT_CHECK_ARG(n > 0 && n % 4 == 0, "adam_step_groups: n=%lld must be a positive multiple of 4", n);
+  DGVIT_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v), "adam_step_groups: p, g, m and v must be 16-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(seg_end4) & 7) == 0, "adam_step_groups: seg_end4 must be 8-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(group_hyper) & 3) == 0, "adam_step_groups: group_hyper must be 4-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(lr_out) & 3) == 0, "adam_step_groups: lr_out must be 4-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) == 0, "adam_step_groups: grad_scale_dev must be 4-byte aligned");
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(step_dev) & 7) == 0, "adam_step_groups: step_dev must be 8-byte aligned");
+  DGVIT_CHECK_ARG(nseg >= 1 && nseg <= ADAM_MAX_SEGMENTS, "adam_step_groups: nseg=%d must be in 1..%d", nseg, ADAM_MAX_SEGMENTS);
+  DGVIT_CHECK_ARG(ngroups >= 1 && ngroups <= ADAM_MAX_GROUPS, "adam_step_groups: ngroups=%d must be in 1..%d", ngroups, ADAM_MAX_GROUPS);
+  DGVIT_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "adam_step_groups: beta1=%g must be in [0, 1)", (double)beta1);
+  DGVIT_CHECK_ARG(beta2 >= 0.f && beta2 < 1.f, "adam_step_groups: beta2=%g must be in [0, 1)", (double)beta2);
+  DGVIT_CHECK_ARG(step_dev || step >= 1, "adam_step_groups: step=%lld must be at least 1 without step_dev", step);
+  DGVIT_CHECK_ARG(step_dev || sched_step >= 1, "adam_step_groups: sched_step=%lld must be at least 1 without step_dev", sched_step);
+  DGVIT_CHECK_ARG(sched_kind >= 0 && sched_kind <= 2, "adam_step_groups: sched_kind=%d must be 0 (constant), 1 (cosine) or 2 (linear)", sched_kind);
+  DGVIT_CHECK_ARG(warmup_steps >= 0, "adam_step_groups: warmup_steps=%lld must not be negative", warmup_steps);
+  DGVIT_CHECK_ARG(sched_kind == 0 || total_steps >= warmup_steps, "adam_step_groups: total_steps=%lld must not be below warmup_steps=%lld",
+                  total_steps, warmup_steps);
+  DGVIT_CHECK_ARG(std::isfinite(final_ratio) && final_ratio >= 0.f && final_ratio <= 1.f, "adam_step_groups: final_ratio=%g must be in [0, 1]",
+                  (double)final_ratio);
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    auto kernel = grad_scale_dev ? (decoupled ? adam_groups_kernel<true, true> : adam_groups_kernel<true, false>)
+                                 : (decoupled ? adam_groups_kernel<false, true> : adam_groups_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, p, g, m, v, n / 4, seg_end4, seg_group, nseg, group_hyper, ngroups,
+                       lr_out, beta1, beta2, eps, step, sched_step, step_dev, sched_kind, warmup_steps, total_steps, final_ratio,
+                       grad_scale_dev);
+  }
+  DGVIT_CHECK_LAUNCH("adam_step_groups");
   return DGVIT_OK;
 }
 

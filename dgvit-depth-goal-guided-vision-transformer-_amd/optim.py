@@ -9,6 +9,11 @@ Gradient-norm clipping (``clip_grad_norm_(…, 10)`` of the reference's behaviou
 the same buffers: ``FlatAdam(max_grad_norm=…)`` folds it into the step (one streaming read for the norm, the coefficient stays on the
 device, Adam applies it while it reads the gradient), and ``clip_grad_norm_`` here is torch's function over the flat runs.
 
+``FlatAdamW``, parameter groups (``[{"params": …, "lr": …, "weight_decay": …}]``, ``no_decay_groups``) and ``LRSchedule`` (warm-up, cosine
+or linear decay) go through ``dgvit_adam_step_groups``: still one kernel per run -- it looks up each element's group in a segment table
+staged into LDS -- with the learning rates in device memory and the schedule evaluated in the kernel, so a captured step follows both
+(DESIGN 3.37).
+
 There is one owner of parameter storage per module: ``flatten_parameters(module)`` creates (or returns) the module's
 home and ``FlatAdam`` adopts it, so an optimiser and a Polyak update on the same network share the same buffer.
 Layout of a home: for every ``GoT`` encoder inside the module its trainable parameters in the C ABI's table order --
@@ -257,6 +262,155 @@ class _ClipScratch:
             _lib.check(rc, "dgvit_grad_clip_coef")
 
 
+def _check_non_negative(value, what: str) -> float:
+    """a finite number >= 0 (bool is not one), or ValueError"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (value >= 0) or not math.isfinite(value):
+        raise ValueError(f"{what} must be a finite number >= 0, got {value!r}")
+    return float(value)
+
+
+class LRSchedule:
+    """Learning-rate factor of a ``FlatAdam`` / ``FlatAdamW`` step as a function of the number ``s`` of optimiser steps already taken:
+    linear warm-up ``(s + 1) / warmup_steps`` for ``s < warmup_steps``, then with ``q = min((s - warmup_steps) / max(1, total_steps -
+    warmup_steps), 1)`` the factor is 1 (``"constant"``), ``r + (1 - r) (1 + cos(pi q)) / 2`` (``"cosine"``) or ``r + (1 - r)(1 - q)``
+    (``"linear"``) with ``r = final_ratio``; past ``total_steps`` it stays ``r``.  ``torch.optim.lr_scheduler.LambdaLR(opt,
+    schedule.factor)`` stepped after every optimiser step is the same schedule.  The optimiser's kernel evaluates this formula on the
+    device (in double, from its step counter), so a captured step follows it; ``factor`` is the same formula on the host.
+    ``total_steps`` is needed by the decaying kinds only."""
+    KINDS = {"constant": 0, "cosine": 1, "linear": 2}
+
+    def __init__(self, kind: str = "constant", warmup_steps: int = 0, total_steps=None, final_ratio: float = 0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind must be one of {sorted(self.KINDS)}, got {kind!r}")
+        if isinstance(warmup_steps, bool) or not isinstance(warmup_steps, int) or warmup_steps < 0:
+            raise ValueError(f"LRSchedule: warmup_steps must be an integer >= 0, got {warmup_steps!r}")
+        if total_steps is None:
+            if kind != "constant":
+                raise ValueError(f"LRSchedule: the {kind} schedule needs total_steps")
+        elif isinstance(total_steps, bool) or not isinstance(total_steps, int) or total_steps < warmup_steps:
+            raise ValueError(f"LRSchedule: total_steps must be an integer >= warmup_steps={warmup_steps}, got {total_steps!r}")
+        if isinstance(final_ratio, bool) or not isinstance(final_ratio, (int, float)) or not (0.0 <= final_ratio <= 1.0):
+            raise ValueError(f"LRSchedule: final_ratio must be in [0, 1], got {final_ratio!r}")
+        self.kind, self.warmup_steps, self.total_steps, self.final_ratio = kind, warmup_steps, total_steps, float(final_ratio)
+
+    def factor(self, s: int) -> float:
+        """the factor of the step taken after ``s`` earlier ones (``s = 0`` is the first step)"""
+        w, r = self.warmup_steps, self.final_ratio
+        if s < w:
+            return (s + 1) / w
+        if self.kind == "constant":
+            return 1.0
+        q = min((s - w) / max(1, self.total_steps - w), 1.0)
+        if self.kind == "cosine":
+            return r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * q))
+        return r + (1.0 - r) * (1.0 - q)
+
+    def state_dict(self):
+        return {"kind": self.kind, "warmup_steps": self.warmup_steps, "total_steps": self.total_steps, "final_ratio": self.final_ratio}
+
+    def _c_args(self):
+        total = self.total_steps if self.total_steps is not None else self.warmup_steps
+        return self.KINDS[self.kind], self.warmup_steps, total, self.final_ratio
+
+    def __repr__(self):
+        return (f"LRSchedule({self.kind!r}, warmup_steps={self.warmup_steps}, total_steps={self.total_steps}, "
+                f"final_ratio={self.final_ratio})")
+
+
+_CONSTANT = LRSchedule()
+MAX_SEGMENTS, MAX_GROUPS = 2048, 256     # include/dgvit_hip.h: dgvit_adam_step_groups
+_GROUP_KEYS = ("params", "lr", "weight_decay")
+
+
+def _group_items(params):
+    """the entries of one ``params`` argument (a module, a tensor, or an iterable of modules and tensors) as a list"""
+    return [params] if isinstance(params, (torch.nn.Module, torch.Tensor)) else list(params)
+
+
+def _parse_groups(params, lr: float, weight_decay: float, who: str):
+    """``params`` as FlatAdam takes it -> (list of (items, lr, weight_decay), whether group dicts were given).  Host work only: unknown
+    keys, bad values and a parameter in two groups are refused before anything touches a device."""
+    items = _group_items(params)
+    if not any(isinstance(g, dict) for g in items):
+        return [(items, lr, weight_decay)], False
+    if not all(isinstance(g, dict) for g in items):
+        raise TypeError(f"{who}: params must be modules / parameters, or a list of group dicts, not a mixture")
+    if len(items) > MAX_GROUPS:
+        raise ValueError(f"{who}: at most {MAX_GROUPS} parameter groups, got {len(items)}")
+    out, seen = [], set()
+    for k, g in enumerate(items):
+        other = sorted(set(g) - set(_GROUP_KEYS))
+        if other:
+            raise ValueError(f"{who}: group {k} has the key(s) {other}; a group sets 'params', 'lr' and 'weight_decay' only -- betas, eps "
+                             "and everything else are optimiser-wide here")
+        if "params" not in g:
+            raise ValueError(f"{who}: group {k} has no 'params'")
+        g_lr = _check_non_negative(g.get("lr", lr), f"{who}: group {k}: lr")
+        g_wd = _check_non_negative(g.get("weight_decay", weight_decay), f"{who}: group {k}: weight_decay")
+        members = _group_items(g["params"])
+        for it in members:
+            for p in (it.parameters() if isinstance(it, torch.nn.Module) else [it]):
+                if id(p) in seen:
+                    raise ValueError(f"{who}: some parameters appear in more than one parameter group")
+                seen.add(id(p))
+        out.append((members, g_lr, g_wd))
+    return out, True
+
+
+def _default_skip(name: str, p) -> bool:
+    last = name.rsplit(".", 1)[-1]
+    return last in ("pos_embedding", "cls_token", "goal_token")
+
+
+def no_decay_groups(module: torch.nn.Module, weight_decay: float, lr=None, skip=None):
+    """The usual AdamW recipe as two group dicts for ``FlatAdamW`` / ``FlatAdam``: the trainable parameters of ``module`` with
+    ``ndim >= 2`` (the GEMM weights) get ``weight_decay``; every other one -- biases, LayerNorm / RMSNorm gains -- and whatever
+    ``skip(name, p)`` selects gets none.  ``skip`` defaults to the position embedding and the goal (class) token by name.  ``lr`` (None:
+    the optimiser's) is set on both groups.  A module on the device whose parameters have no flat home yet is flattened here
+    (``flatten_parameters``), so that the groups are segments of the MODULE's home -- the layout the fused encoder backward writes its gradients in -- whatever order the
+    groups list the parameters in."""
+    weight_decay = _check_non_negative(weight_decay, "no_decay_groups: weight_decay")
+    if lr is not None:
+        lr = _check_non_negative(lr, "no_decay_groups: lr")
+    skip = _default_skip if skip is None else skip
+    decay, rest = [], []
+    for name, p in module.named_parameters():
+        if p.requires_grad:
+            (decay if p.ndim >= 2 and not skip(name, p) else rest).append(p)
+    if decay + rest and all(p.is_cuda for p in decay + rest) and any(
+            _HOME_OF.get(p) is None or not _HOME_OF[p][0].intact() for p in decay + rest):
+        home_of(module)       # (parameters that already live in an intact home, e.g. a parent module's, stay there)
+    groups = [{"params": decay, "weight_decay": weight_decay}, {"params": rest, "weight_decay": 0.0}]
+    if lr is not None:
+        for g in groups:
+            g["lr"] = lr
+    return [g for g in groups if g["params"]]
+
+
+class _SegmentTable:
+    """Device tables of one run for dgvit_adam_step_groups: the ends of its segments (float4 units from the run's start) and their
+    groups, adjacent slots of one group merged.  Built once per distinct run and kept: a captured graph holds the pointers."""
+
+    def __init__(self, home: _Home, idx, group_of_slot):
+        self.home = weakref.ref(home)
+        lo = home.offsets[idx[0]]
+        ends, groups = [], []
+        for i in idx:
+            end4 = (home.offsets[i] + _al4(home.params[i].numel()) - lo) // 4
+            if groups and groups[-1] == group_of_slot[i]:
+                ends[-1] = end4
+            else:
+                ends.append(end4)
+                groups.append(group_of_slot[i])
+        if len(ends) > MAX_SEGMENTS:
+            raise _lib.DgvitError(f"FlatAdam: a run of {len(ends)} segments (changes of parameter group along the flat buffer); "
+                                  f"dgvit_adam_step_groups takes at most {MAX_SEGMENTS}")
+        self.nseg = len(ends)
+        dev = home.flat.device
+        self.end4 = torch.tensor(ends, dtype=torch.int64).to(dev)
+        self.group = torch.tensor(groups, dtype=torch.uint8).to(dev)
+
+
 class FlatAdam:
     """``torch.optim.Adam`` semantics (amsgrad=False) with one HIP kernel per contiguous run of a flat parameter buffer.
 
@@ -278,38 +432,76 @@ class FlatAdam:
     clipped step).  ``max_grad_norm`` is a plain attribute read on every ``step()``; it is passed as a kernel argument, so a
     captured graph keeps the value it was captured with.  It is not part of ``state_dict()`` (it is not optimiser state in torch
     either).
+
+    Parameter groups and schedules.  ``params`` may also be a list of group dicts ``{"params": …, "lr": …,
+    "weight_decay": …}`` (``params`` of a group: a module, or parameters and leaf tensors; missing keys take the constructor's values;
+    betas and eps are optimiser-wide, any other key is refused; a parameter in two groups is refused), and ``schedule`` an
+    ``LRSchedule``.  With either, the step goes through ``dgvit_adam_step_groups``: still ONE launch per run of the flat buffer -- runs
+    are formed exactly as without groups; the kernel looks up each element's group in a segment table it stages into LDS -- with the
+    learning rates in a device table and the schedule factor computed in the kernel, so a step captured by ``GraphedStep`` follows
+    the schedule and ``set_lr``.  A schedule counts OPTIMISER steps (``step_count``; with ``capturable=True`` the device counter), not
+    the steps of a single parameter: a parameter that first gets a gradient at step 100 takes the learning rate of step 100.
+    ``param_groups`` lists the groups (``params``, ``lr``, ``weight_decay``) for inspection; change a learning rate with ``set_lr`` (an
+    eager step also picks up a value written into ``param_groups``; a replayed graph sees only ``set_lr``).  ``last_lr``: the
+    learning rates ``lr * factor`` the last step used, a ``(groups,)`` device tensor written by the kernel (None before the first
+    step).  ``last_step_launches``: how many C entry points the last ``step()`` called.  Without groups and schedule nothing
+    changes: ``dgvit_adam_step`` / ``dgvit_adam_step_scaled`` with ``lr`` by value, as before.
     """
 
+    _decoupled = False      # FlatAdamW: weight decay multiplies the parameter (torch.optim.AdamW) instead of joining the gradient
+
     def __init__(self, params: Union[torch.nn.Module, Iterable], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 capturable: bool = False, max_grad_norm=None):
+                 capturable: bool = False, max_grad_norm=None, schedule=None):
+        who = type(self).__name__
         if max_grad_norm is not None:
             _check_max_norm(max_grad_norm, "FlatAdam: max_grad_norm")
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise ValueError(f"{who}: schedule must be an LRSchedule or None, got {type(schedule).__name__}")
         self.max_grad_norm, self._clip, self.last_grad_norm = max_grad_norm, None, None
         self.capturable, self._step_dev = bool(capturable), None
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        items = [params] if isinstance(params, torch.nn.Module) else list(params)
+        parsed, grouped = _parse_groups(params, self.lr, self.weight_decay, who)     # host checks only: nothing touched a device yet
+        if self._decoupled or grouped or schedule is not None:
+            _check_non_negative(lr, f"{who}: lr")
+            _check_non_negative(weight_decay, f"{who}: weight_decay")
+        self.schedule = schedule
+        # the new entry point (dgvit_adam_step_groups) serves groups, schedules and decoupled decay; everything else runs as it always did
+        self._grouped = bool(self._decoupled or grouped or schedule is not None)
+        self._hyper = self._hyper_host = self._last_lr = self._last_lr_buf = None   # device (G, 2) table of (lr, weight_decay), its host mirror, (G,) lr * f
+        self._tables = {}                                          # (id(home), slots of a run) -> _SegmentTable
+        self.last_step_launches = 0
+        items = [it for members, _, _ in parsed for it in members]
         self.modules = [m for m in items if isinstance(m, torch.nn.Module)]
-        chosen, seen = [], set()
+        for p in items:
+            if not isinstance(p, torch.nn.Module) and not (isinstance(p, torch.Tensor) and p.is_leaf and p.dtype == torch.float32):
+                # nn.Parameter or a plain leaf such as DRL.py's log_alpha
+                raise TypeError(f"FlatAdam: expected modules, parameters or fp32 leaf tensors, got {type(p).__name__}")
         for m in self.modules:
             home_of(m)
-            for p in m.parameters():
+        chosen, seen, loose = [], set(), []
+        self.param_groups = []
+        for members, g_lr, g_wd in parsed:
+            mine = []
+            for it in members:
+                if isinstance(it, torch.nn.Module):
+                    for p in it.parameters():
+                        if p.requires_grad and id(p) not in seen:
+                            seen.add(id(p))
+                            mine.append(p)
+            for p in members:
+                if isinstance(p, torch.nn.Module):
+                    continue
                 if p.requires_grad and id(p) not in seen:
                     seen.add(id(p))
-                    chosen.append(p)
-        loose = []
-        for p in items:
-            if isinstance(p, torch.nn.Module):
-                continue
-            if not (isinstance(p, torch.Tensor) and p.is_leaf and p.dtype == torch.float32):   # nn.Parameter or a plain leaf such as DRL.py's log_alpha
-                raise TypeError(f"FlatAdam: expected modules, parameters or fp32 leaf tensors, got {type(p).__name__}")
-            if p.requires_grad and id(p) not in seen:
-                seen.add(id(p))
-                chosen.append(p)
-                ent = _HOME_OF.get(p)
-                if ent is None or not ent[0].intact():
-                    loose.append(p)
+                    mine.append(p)
+                    ent = _HOME_OF.get(p)
+                    if ent is None or not ent[0].intact():
+                        loose.append(p)
+            chosen.extend(mine)
+            self.param_groups.append({"params": mine, "lr": g_lr, "weight_decay": g_wd})
         if loose:
             _Home(loose)               # parameters handed over one by one that no module home owns yet
+        self._group_of = {id(p): k for k, g in enumerate(self.param_groups) for p in g["params"]}
         self.params = chosen
         self.step_count = 0
         # Like a new torch.optim.Adam, a new FlatAdam starts from empty state.  Moments and step counts normally live with the
@@ -371,6 +563,7 @@ class FlatAdam:
         if not runs:
             return
         self.step_count += 1
+        self.last_step_launches = 0
         step_ptr = ctypes.c_void_p(0)
         if self.capturable:
             if len({self._state(home).steps[idx[0]] for home, idx in runs}) != 1:
@@ -387,6 +580,9 @@ class FlatAdam:
                 self._clip = _ClipScratch(grads[0].device)
                 self.last_grad_norm = self._clip.norm
             self._clip.measure(lib, grads, max_norm)
+            self.last_step_launches += len(grads) + 1
+        if self._grouped:
+            self._sync_hyper(runs[0][0].flat.device)
         for k, (home, idx) in enumerate(runs):
             lo = home.offsets[idx[0]]
             n = home.offsets[idx[-1]] + _al4(home.params[idx[-1]].numel()) - lo
@@ -396,6 +592,10 @@ class FlatAdam:
             t = st.steps[idx[0]] + 1
             for i in idx:
                 st.steps[i] = t
+            self.last_step_launches += 1
+            if self._grouped:
+                self._step_groups(lib, home, idx, lo, n, g, m, v, t, step_ptr, grads is not None)
+                continue
             with torch.cuda.device(home.flat.device):
                 if grads is None:
                     rc = lib.dgvit_adam_step(ctypes.c_void_p(home.flat.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr()),
@@ -409,6 +609,65 @@ class FlatAdam:
             _lib.check(rc, "dgvit_adam_step" if grads is None else "dgvit_adam_step_scaled")
         # the kernel wrote the parameters through raw pointers: no autograd version counter moved
         F_.notify_parameters_changed(self.params)
+
+    def _sync_hyper(self, device=None) -> None:
+        """Bring the device table of (lr, weight_decay) per group in line with ``param_groups``: allocated on first use (and then kept:
+        a captured graph holds its address), written entry by entry with stream-ordered fills -- no synchronisation, no copy from
+        pageable host memory.  Without a device and before the first step there is nothing to write yet."""
+        want = [(float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups]
+        if self._hyper is None:
+            if device is None:
+                return
+            self._hyper = torch.empty((len(want), 2), dtype=torch.float32, device=device)
+            self._last_lr_buf = torch.zeros(len(want), dtype=torch.float32, device=device)
+            self._hyper_host = [(None, None)] * len(want)
+        for k, (have, new) in enumerate(zip(self._hyper_host, want)):
+            for j in (0, 1):
+                if have[j] != new[j]:
+                    self._hyper[k, j].fill_(new[j])
+        self._hyper_host = want
+
+    def _step_groups(self, lib, home, idx, lo, n, g, m, v, t, step_ptr, scaled) -> None:
+        """one run through dgvit_adam_step_groups"""
+        if home.flat.device != self._hyper.device:
+            raise _lib.DgvitError("FlatAdam with parameter groups or a schedule needs all its parameters on one device")
+        key = (id(home), tuple(idx))
+        tab = self._tables.get(key)
+        if tab is None or tab.home() is not home:
+            tab = self._tables[key] = _SegmentTable(home, idx, {i: self._group_of[id(home.params[i])] for i in idx})
+        kind, warmup, total, final_ratio = (self.schedule or _CONSTANT)._c_args()
+        with torch.cuda.device(home.flat.device):
+            rc = lib.dgvit_adam_step_groups(
+                ctypes.c_void_p(home.flat.data_ptr() + 4 * lo), ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(m.data_ptr() + 4 * lo),
+                ctypes.c_void_p(v.data_ptr() + 4 * lo), n, ctypes.c_void_p(tab.end4.data_ptr()), ctypes.c_void_p(tab.group.data_ptr()),
+                tab.nseg, ctypes.c_void_p(self._hyper.data_ptr()), len(self.param_groups), ctypes.c_void_p(self._last_lr_buf.data_ptr()),
+                self.betas[0], self.betas[1], self.eps, int(self._decoupled), t, self.step_count, step_ptr, kind, warmup, total,
+                final_ratio, ctypes.c_void_p(self._clip.coef.data_ptr()) if scaled else ctypes.c_void_p(0), _stream())
+        _lib.check(rc, "dgvit_adam_step_groups")
+        self._last_lr = self._last_lr_buf
+
+    @property
+    def last_lr(self):
+        return self._last_lr
+
+    def set_lr(self, value, group=None) -> None:
+        """Set the learning rate of group ``group`` (None: of every group, and the optimiser-wide default): the host mirror
+        ``param_groups[i]["lr"]`` and, stream-ordered, the device table the kernel reads -- the next eager step and the next replay
+        of a captured step use it.  (Without groups and schedule the step passes ``lr`` by value: a captured one keeps the old.)"""
+        who = type(self).__name__
+        value = _check_non_negative(value, f"{who}.set_lr: lr")
+        if group is None:
+            which = range(len(self.param_groups))
+            self.lr = value
+        else:
+            if isinstance(group, bool) or not isinstance(group, int) or not 0 <= group < len(self.param_groups):
+                raise ValueError(f"{who}.set_lr: group must be an index below {len(self.param_groups)}, got {group!r}")
+            which = [group]
+            if len(self.param_groups) == 1:
+                self.lr = value
+        for k in which:
+            self.param_groups[k]["lr"] = value
+        self._sync_hyper()
 
     def _homes(self):
         out, seen = [], set()
@@ -441,12 +700,28 @@ class FlatAdam:
                 state.append({"step": st.steps[i], "exp_avg": st.exp_avg[o:o + n].view_as(p).clone(),
                               "exp_avg_sq": st.exp_avg_sq[o:o + n].view_as(p).clone()})
         return {"step": self.step_count, "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
-                "state": state}
+                "state": state, "decoupled": bool(self._decoupled),
+                "schedule": self.schedule.state_dict() if self.schedule is not None else None,
+                "groups": [{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in self.param_groups]}
 
     def load_state_dict(self, sd) -> None:
         if len(sd["state"]) != len(self.params):
             raise ValueError("optimizer state does not match this optimiser's parameters")
+        if "groups" in sd and len(sd["groups"]) != len(self.param_groups):
+            raise ValueError(f"optimizer state has {len(sd['groups'])} parameter groups, this optimiser has {len(self.param_groups)}")
+        if bool(sd.get("decoupled", self._decoupled)) != bool(self._decoupled):
+            raise ValueError("optimizer state was saved with the other kind of weight decay (FlatAdam: L2, FlatAdamW: decoupled)")
         self.step_count = int(sd["step"])
+        if "groups" in sd:               # (a dict saved before there were groups leaves groups and schedule as constructed)
+            for mine, saved in zip(self.param_groups, sd["groups"]):
+                mine["lr"] = _check_non_negative(saved["lr"], "load_state_dict: lr")
+                mine["weight_decay"] = _check_non_negative(saved["weight_decay"], "load_state_dict: weight_decay")
+            if len(self.param_groups) == 1:
+                self.lr, self.weight_decay = self.param_groups[0]["lr"], self.param_groups[0]["weight_decay"]
+            self._sync_hyper()
+        if sd.get("schedule") is not None:
+            self.schedule = LRSchedule(**sd["schedule"])
+            self._grouped = True
         for p, st in zip(self.params, sd["state"]):
             home, i = _HOME_OF[p]
             mine = self._state(home)
@@ -462,6 +737,18 @@ class FlatAdam:
                 v[o:o + n].view_as(p).copy_(st["exp_avg_sq"])
         if self._step_dev is not None:
             self._step_dev.fill_(max((self._state(_HOME_OF[p][0]).steps[_HOME_OF[p][1]] for p in self.params), default=0))
+
+
+class FlatAdamW(FlatAdam):
+    """``torch.optim.AdamW`` semantics and defaults (decoupled weight decay: ``p *= 1 - lr_t * weight_decay`` before the Adam update, the
+    moments from the raw gradient) on the flat buffers.  Everything else is ``FlatAdam``: parameter groups, ``schedule``, ``set_lr``,
+    ``capturable``, ``max_grad_norm``; the step always goes through ``dgvit_adam_step_groups``, one launch per run."""
+    _decoupled = True
+
+    def __init__(self, params: Union[torch.nn.Module, Iterable], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 capturable: bool = False, max_grad_norm=None, schedule=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
+                         max_grad_norm=max_grad_norm, schedule=schedule)
 
 
 def _flat_pair(target, source):

@@ -595,6 +595,37 @@ int dgvit_adam_step_scaled(float* p, const float* g, float* m, float* v, long lo
 int dgvit_scale_by_device_scalar(float* x, long long n, const float* scale_dev, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Parameter groups and learning-rate schedules: torch.optim.Adam / AdamW over ONE run of a flat buffer whose elements belong to groups
+ * with their own (lr, weight_decay), with warm-up and cosine / linear decay evaluated on the device -- one launch, graph-capturable, a
+ * replayed graph follows the schedule and a learning rate changed in device memory.  Flat buffers as above.
+ *
+ *   seg_end4 (DEVICE, nseg long longs, 8-byte aligned): the end of segment k in float4 units relative to p, strictly ascending, the last
+ *     one equal to n / 4.  seg_group (DEVICE, nseg bytes): the group of segment k, < ngroups.  1 <= nseg <= 2048.
+ *   group_hyper (DEVICE, 2 * ngroups floats): (lr, weight_decay) of group 0, group 1, ...  1 <= ngroups <= 256.
+ *   lr_out (DEVICE, ngroups floats, may be NULL): receives lr * f per group, the learning rates this step used.
+ *   step / step_dev: as dgvit_adam_step (t = *step_dev when given, else step >= 1).  The bias corrections are ALWAYS computed in the
+ *     kernel, lr_t / (1 - powf(beta1, t)) and rsqrtf(1 - powf(beta2, t)), so a call with a host step and one with a device counter
+ *     give the same bits.
+ *   The schedule factor f, in double, rounded to fp32 once: s = (step_dev ? *step_dev : sched_step) - 1 steps were already taken;
+ *     s < warmup_steps: f = (s + 1) / warmup_steps; otherwise q = min((s - warmup_steps) / max(1, total_steps - warmup_steps), 1) and
+ *     sched_kind 0 (constant): f = 1     1 (cosine): f = r + (1 - r) (1 + cos(pi q)) / 2     2 (linear): f = r + (1 - r)(1 - q)
+ *     with r = final_ratio in [0, 1]; past total_steps f stays r.  total_steps >= warmup_steps >= 0 (kind 0 ignores total_steps).
+ *   Per element, with its group's lr_t = lr * f and wd, g first multiplied by *grad_scale_dev (may be NULL) as dgvit_adam_step_scaled does:
+ *     decoupled == 0: gg = g + wd p;  m = b1 m + (1 - b1) gg;  v = b2 v + (1 - b2) gg gg;  p -= lr_c m / (sqrt(v) inv_sqrt_bc2 + eps)
+ *     decoupled != 0: p = p (1 - lr_t wd) (rounded on its own), then the same lines with gg = g                       (torch.optim.AdamW)
+ *   With one group, decoupled == 0 and sched_kind == 0 the result is bit-identical to dgvit_adam_step[_scaled] called with a step_dev.
+ * Bad arguments (null or misaligned pointers, n, nseg, ngroups, betas outside [0, 1), step < 1 without step_dev, sched_kind,
+ * warmup_steps < 0, total_steps < warmup_steps for kinds 1 and 2, final_ratio outside [0, 1]) are refused before any launch.
+ * -------------------------------------------------------------------------------------------- */
+int dgvit_adam_step_groups(float* p, const float* g, float* m, float* v, long long n,
+                           const long long* seg_end4, const unsigned char* seg_group, int nseg,
+                           const float* group_hyper, int ngroups, float* lr_out,
+                           float beta1, float beta2, float eps, int decoupled,
+                           long long step, long long sched_step, const long long* step_dev,
+                           int sched_kind, long long warmup_steps, long long total_steps, float final_ratio,
+                           const float* grad_scale_dev, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The SAC loss head: the arithmetic of SAC.learn between the network forwards and the backwards (DRL.py:384-425), one launch per
  * loss with its gradient, nothing synchronises, graph-capturable.  fp32; q* are (B, A) row-major, reward / done / weights / log_pi /
  * next_log_pi hold B values; 1 <= B, 1 <= A <= 16, B * A <= 2^20.  The temperature alpha is expf(log_alpha[0]) read on the DEVICE
