@@ -211,6 +211,15 @@ DIAG_SIGNATURES = {
     "dgvit_attention_backward_queries": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_set_gemm_bf16_mfma16": (None, [_I]),
     "dgvit_set_gemm_bf16_stamps": (None, [_P]),
+    # the row kernels with row_step / nullable outputs / the queued reduction (include/dgvit_hip_diag.h)
+    "dgvit_diag_layernorm_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dgvit_diag_layernorm_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
+    "dgvit_diag_layernorm_forward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dgvit_diag_layernorm_backward_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
+    "dgvit_diag_residual_add_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "dgvit_diag_transpose_cast_f32_bf16": (_I, [_P, _P, _I, _I, _P]),
+    "dgvit_diag_colsum_scratch_floats": (_LL, [_I, _I]),
+    "dgvit_diag_colsum": (_I, [_P, _LL, _P, _P, _LL, _I, _I, _I, _P]),
 }
 PROFILE_KINDS = 4
 

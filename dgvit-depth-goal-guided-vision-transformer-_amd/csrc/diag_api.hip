@@ -2,6 +2,7 @@
 #define DGVIT_KNOB_DEFINE   // knobs.h: this translation unit defines every knob with its default
 #include "../../include/dgvit_hip_diag.h"
 #include "schedule.h"
+#include "bf16.h"
 
 #ifndef DGVIT_DIAG
 #error "diag_api.hip belongs to the diagnostic library only (-DDGVIT_DIAG)"
@@ -55,3 +56,65 @@ extern "C" int dgvit_attention_backward_queries(const float* qkv, const float* o
 extern "C" void dgvit_set_gemm_bf16_group_m(int rows) { g_gemm_bf16_group_m = rows > 0 ? rows : g_gemm_bf16_group_m_default; }
 extern "C" void dgvit_set_gemm_bf16_stamps(long long* stamps) { g_gemm_bf16_stamps = stamps; }
 extern "C" void dgvit_set_gemm_bf16_l2_budget_kb(int kb) { g_gemm_bf16_l2_budget_kb = kb > 0 ? kb : 0; }
+
+// ---- the row kernels with every argument the encoder schedules use (tests/test_gpu_row_kernels.py); the product ABI fixes row_step = 1,
+// both parameter gradients and a direct reduction
+extern "C" int dgvit_diag_layernorm_forward(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                                            int rows, int D, int row_step, void* stream) {
+  return layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, D, 1e-5f, row_step, (hipStream_t)stream);
+}
+extern "C" int dgvit_diag_layernorm_backward(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                             const float* dres, float* dx, float* dgamma, float* dbeta, float* scratch,
+                                             long long scratch_floats, int rows, int D, int row_step, int grouped, void* stream) {
+  if (rows <= 0 || D <= 0 || scratch_floats < (long long)layernorm_bwd_blocks(rows) * 2 * D)
+    return dgvit_set_error(DGVIT_ERR_WORKSPACE, "diag_layernorm_backward: scratch too small");
+  DGVIT_CHECK_ARG(row_step >= 1, "diag_layernorm_backward: bad row step");
+  hipStream_t st = (hipStream_t)stream;
+  if (!grouped) return layernorm_bwd(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, scratch, rows, D, row_step, st);
+  ReduceGroup grp;     // as a layer of dgvit_got_backward queues it: the reduction runs in the group's flush
+  reduce_group_init(grp);
+  TRY(layernorm_bwd(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, scratch, rows, D, row_step, st, &grp));
+  return reduce_group_flush(grp, st);
+}
+// the dispatch of encoder_bf16.hip: no delta -> layernorm_fwd_bf16; delta with xout and statistics -> add_layernorm_fwd_bf16 (the
+// training schedule and the pruned last block); delta2, or delta without xout / statistics -> add2_layernorm_fwd_bf16 (the no-grad
+// schedule: contiguous rows, no statistics)
+extern "C" int dgvit_diag_layernorm_forward_bf16(const float* x, const unsigned short* delta, const unsigned short* delta2, float* xout,
+                                                 const float* gamma, const float* beta, unsigned short* y, float* mean, float* rstd,
+                                                 int rows, int D, int row_step, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  DGVIT_CHECK_ARG(row_step >= 1 && (mean == nullptr) == (rstd == nullptr), "diag_layernorm_forward_bf16: bad row step, or one of mean / rstd without the other");
+  DGVIT_CHECK_ARG(delta || (!delta2 && !xout), "diag_layernorm_forward_bf16: delta2 / xout without delta");
+  if (!delta) return layernorm_fwd_bf16(x, gamma, beta, y, mean, rstd, rows, D, 1e-5f, row_step, st);
+  if (!delta2 && xout && mean) return add_layernorm_fwd_bf16(x, delta, xout, gamma, beta, y, mean, rstd, rows, D, 1e-5f, row_step, st);
+  DGVIT_CHECK_ARG(row_step == 1 && !mean, "diag_layernorm_forward_bf16: the joint form has contiguous rows and no statistics");
+  return add2_layernorm_fwd_bf16(x, delta, delta2, xout, gamma, beta, y, rows, D, 1e-5f, st);
+}
+extern "C" int dgvit_diag_layernorm_backward_bf16(const unsigned short* dy, const float* x, const float* mean, const float* rstd,
+                                                  const float* gamma, const float* dres, float* dx, unsigned short* dxb, float* dgamma,
+                                                  float* dbeta, float* scratch, long long scratch_floats, int rows, int D, int row_step,
+                                                  void* stream) {
+  if (rows <= 0 || D <= 0 || scratch_floats < (long long)layernorm_bwd_blocks(rows) * 2 * D)
+    return dgvit_set_error(DGVIT_ERR_WORKSPACE, "diag_layernorm_backward_bf16: scratch too small");
+  DGVIT_CHECK_ARG(row_step >= 1, "diag_layernorm_backward_bf16: bad row step");
+  return layernorm_bwd_bf16(dy, x, mean, rstd, gamma, dres, dx, dxb, dgamma, dbeta, scratch, rows, D, row_step, (hipStream_t)stream);
+}
+extern "C" int dgvit_diag_residual_add_bf16(const float* x, const unsigned short* delta, float* xout, int rows, int D, int row_step,
+                                            void* stream) {
+  DGVIT_CHECK_ARG(row_step >= 1, "diag_residual_add_bf16: bad row step");
+  return residual_add_bf16(x, delta, xout, rows, D, row_step, (hipStream_t)stream);
+}
+extern "C" int dgvit_diag_transpose_cast_f32_bf16(const float* src, unsigned short* dst, int rows, int cols, void* stream) {
+  return transpose_cast_f32_bf16(src, dst, rows, cols, (hipStream_t)stream);
+}
+extern "C" long long dgvit_diag_colsum_scratch_floats(int rows, int cols) {
+  if (rows <= 0 || cols <= 0) return -1;
+  return (long long)colsum_blocks(rows) * cols;
+}
+extern "C" int dgvit_diag_colsum(const float* a, long long lda, float* out, float* scratch, long long scratch_floats, int rows, int cols,
+                                 int rgrp, void* stream) {
+  if (rows <= 0 || cols <= 0 || scratch_floats < (long long)colsum_blocks(rows) * cols)
+    return dgvit_set_error(DGVIT_ERR_WORKSPACE, "diag_colsum: scratch too small");
+  DGVIT_CHECK_ARG(lda >= cols && rgrp >= 0, "diag_colsum: lda=%lld < cols=%d, or a negative row group", lda, cols);
+  return colsum(a, lda, out, scratch, rows, cols, rgrp, (hipStream_t)stream);
+}

@@ -148,7 +148,9 @@ __global__ void __launch_bounds__(256) rmsnorm_fwd_kernel(const float* __restric
   for (int c = lane; c < D; c += 64) y[(long long)row * D + c] = xr[c] / n * sc * g[c];
 }
 
-// dx = u/n - x * (u.x)/n^3 with u = dy*g*sqrt(D)  (second term dropped when the norm was clamped);
+// dx = (u - xh * (u.xh)) / n with u = dy*g*sqrt(D), xh = x/n  (second term dropped when the norm was clamped).  Formed from xh and
+// p = (u.x)/n, never from n^3: that overflows fp32 for n above 7e12 (k = (u.x)/n^3 became 0 and the projection term vanished);
+// |xh| <= 1 and |p| <= |u| keep every intermediate in range wherever sqrt(q) is finite.
 // partial[blk][c] = sum_rows dy * x/n * sqrt(D)
 __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, long long ldx,
                                                           const float* __restrict__ g, float* __restrict__ dx, long long lddx,
@@ -171,10 +173,10 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const float* __restric
     const float nr = sqrtf(q);
     const bool clamped = nr < 1e-12f;
     const float n = clamped ? 1e-12f : nr;
-    const float k = clamped ? 0.f : ux / (n * n * n);
+    const float p = clamped ? 0.f : ux / n;
     for (int c = lane; c < D; c += 64) {
       const float xv = xr[c], dv = dr[c];
-      dx[row * lddx + c] = dv * g[c] * sc / n - xv * k;
+      dx[row * lddx + c] = (dv * g[c] * sc - xv / n * p) / n;
       red[wave * D + c] += dv * xv / n * sc;
     }
   }

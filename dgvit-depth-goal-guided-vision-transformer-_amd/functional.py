@@ -1101,3 +1101,117 @@ def op_attention_probs_bf16(qkv, lse, heads, dim_head=64, rows="goal"):
     _lib.check(lib.dgvit_attention_probs_bf16(_ptr(qkv), _ptr(lse), _ptr(probs), B, N, heads, dim_head, r, _stream()),
                "dgvit_attention_probs_bf16")
     return probs
+
+
+# ------------------------------------------------------------------------------------------------ row kernels, diagnostic library only
+# (include/dgvit_hip_diag.h: call these inside ``with diagnostic_library():``).  The tensors are the PHYSICAL buffers: with row_step
+# rs, logical row r is row r * rs of x / y / dy / dx / delta / xout (each at least ((rows - 1) * rs + 1) * D elements); mean / rstd are
+# dense.  No argument is copied or made contiguous -- the pointers go to the library as they are -- and outputs the caller passes in
+# are written in place (canary buffers, NULL outputs).
+def _diag_lib(name):
+    lib = _lib.load()
+    if not hasattr(lib, name):
+        raise DgvitError(f"{name} is an entry point of the diagnostic library: call it inside `with diagnostic_library():`")
+    return lib
+
+
+def _raw(t, name, dtype=torch.float32):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise DgvitError(f"{name}: expected a contiguous {dtype} tensor on a ROCm device (no CPU fallback)")
+    return t
+
+
+def op_diag_layernorm_fwd(x, gamma, beta, rows, D, row_step=1, *, y=None, mean=None, rstd=None):
+    lib = _diag_lib("dgvit_diag_layernorm_forward")
+    x, gamma, beta = _raw(x, "x"), _raw(gamma, "gamma"), _raw(beta, "beta")
+    y = torch.empty_like(x) if y is None else _raw(y, "y")
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device) if mean is None else _raw(mean, "mean")
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if rstd is None else _raw(rstd, "rstd")
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_diag_layernorm_forward(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, D, row_step, _stream())
+    _lib.check(rc, "dgvit_diag_layernorm_forward")
+    return y, mean, rstd
+
+
+def _ln_bwd_scratch(lib, rows, D, dev):
+    n = max(int(lib.dgvit_layernorm_backward_scratch_floats(rows, D)), 4)
+    return torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+
+
+def op_diag_layernorm_bwd(dy, x, mean, rstd, gamma, rows, D, row_step=1, *, dres=None, dx=None, dgamma=None, dbeta=None, grouped=False):
+    """dgamma / dbeta: a tensor to write, or None for a NULL pointer (frozen parameter).  Returns dx."""
+    lib = _diag_lib("dgvit_diag_layernorm_backward")
+    dy, x = _raw(dy, "dy"), _raw(x, "x")
+    dx = torch.empty_like(x) if dx is None else _raw(dx, "dx")
+    sc = _ln_bwd_scratch(lib, rows, D, x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_diag_layernorm_backward(_ptr(dy), _ptr(x), _ptr(_raw(mean, "mean")), _ptr(_raw(rstd, "rstd")), _ptr(_raw(gamma, "gamma")),
+                                               _ptr(_raw(dres, "dres")), _ptr(dx), _ptr(_raw(dgamma, "dgamma")), _ptr(_raw(dbeta, "dbeta")),
+                                               _ptr(sc), sc.numel(), rows, D, row_step, int(bool(grouped)), _stream())
+    _lib.check(rc, "dgvit_diag_layernorm_backward")
+    return dx
+
+
+def op_diag_layernorm_fwd_bf16(x, gamma, beta, rows, D, row_step=1, *, delta=None, delta2=None, xout=None, y=None, mean=None, rstd=None):
+    """The bf16 encoder's LayerNorm dispatch (plain / add / joint add).  xout, mean, rstd: a tensor to write or None for NULL.  Returns y."""
+    lib = _diag_lib("dgvit_diag_layernorm_forward_bf16")
+    x = _raw(x, "x")
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if y is None else _raw(y, "y", torch.bfloat16)
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_diag_layernorm_forward_bf16(_ptr(x), _ptr(_raw(delta, "delta", torch.bfloat16)), _ptr(_raw(delta2, "delta2", torch.bfloat16)),
+                                                   _ptr(_raw(xout, "xout")), _ptr(_raw(gamma, "gamma")), _ptr(_raw(beta, "beta")), _ptr(y),
+                                                   _ptr(_raw(mean, "mean")), _ptr(_raw(rstd, "rstd")), rows, D, row_step, _stream())
+    _lib.check(rc, "dgvit_diag_layernorm_forward_bf16")
+    return y
+
+
+def op_diag_layernorm_bwd_bf16(dy, x, mean, rstd, gamma, rows, D, row_step=1, *, dres=None, dx=None, dxb=None, dgamma=None, dbeta=None):
+    """dy bf16; dxb (bf16 copy of dx), dgamma, dbeta: a tensor to write or None for NULL.  Returns dx."""
+    lib = _diag_lib("dgvit_diag_layernorm_backward_bf16")
+    dy, x = _raw(dy, "dy", torch.bfloat16), _raw(x, "x")
+    dx = torch.empty_like(x) if dx is None else _raw(dx, "dx")
+    sc = _ln_bwd_scratch(lib, rows, D, x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_diag_layernorm_backward_bf16(_ptr(dy), _ptr(x), _ptr(_raw(mean, "mean")), _ptr(_raw(rstd, "rstd")), _ptr(_raw(gamma, "gamma")),
+                                                    _ptr(_raw(dres, "dres")), _ptr(dx), _ptr(_raw(dxb, "dxb", torch.bfloat16)),
+                                                    _ptr(_raw(dgamma, "dgamma")), _ptr(_raw(dbeta, "dbeta")), _ptr(sc), sc.numel(), rows, D,
+                                                    row_step, _stream())
+    _lib.check(rc, "dgvit_diag_layernorm_backward_bf16")
+    return dx
+
+
+def op_diag_residual_add_bf16(x, delta, rows, D, row_step=1, *, xout=None):
+    lib = _diag_lib("dgvit_diag_residual_add_bf16")
+    x, delta = _raw(x, "x"), _raw(delta, "delta", torch.bfloat16)
+    xout = torch.empty_like(x) if xout is None else _raw(xout, "xout")
+    with torch.cuda.device(x.device):
+        rc = lib.dgvit_diag_residual_add_bf16(_ptr(x), _ptr(delta), _ptr(xout), rows, D, row_step, _stream())
+    _lib.check(rc, "dgvit_diag_residual_add_bf16")
+    return xout
+
+
+def op_diag_transpose_cast_bf16(src, *, dst=None):
+    """(rows, cols) fp32 -> (cols, rows) bf16"""
+    lib = _diag_lib("dgvit_diag_transpose_cast_f32_bf16")
+    src = _raw(src, "src")
+    rows, cols = src.shape
+    dst = torch.empty(cols, rows, dtype=torch.bfloat16, device=src.device) if dst is None else _raw(dst, "dst", torch.bfloat16)
+    with torch.cuda.device(src.device):
+        rc = lib.dgvit_diag_transpose_cast_f32_bf16(_ptr(src), _ptr(dst), rows, cols, _stream())
+    _lib.check(rc, "dgvit_diag_transpose_cast_f32_bf16")
+    return dst
+
+
+def op_diag_colsum(a, lda, rows, cols, rgrp=0, *, out=None):
+    """out[n] = sum_t a[row(t) * lda + n]; ``a`` is the flat physical buffer (any 4-byte aligned start: a view works)."""
+    lib = _diag_lib("dgvit_diag_colsum")
+    a = _raw(a, "a")
+    out = torch.empty(cols, dtype=torch.float32, device=a.device) if out is None else _raw(out, "out")
+    n = max(int(lib.dgvit_diag_colsum_scratch_floats(rows, cols)), 4)
+    sc = torch.full((n,), float("nan"), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.dgvit_diag_colsum(_ptr(a), lda, _ptr(out), _ptr(sc), sc.numel(), rows, cols, rgrp, _stream())
+    _lib.check(rc, "dgvit_diag_colsum")
+    return out

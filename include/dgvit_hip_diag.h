@@ -116,6 +116,37 @@ void dgvit_set_gemm_bf16_mfma16(int on);
  * to this device buffer (256 workgroups at most); NULL (default) = shipped kernels, no stamp executes. */
 void dgvit_set_gemm_bf16_stamps(long long* stamps);
 
+/* The row kernels (LayerNorm, bf16 helpers, fp32 column sums) with the arguments only the encoder schedules pass; the product ABI
+ * (dgvit_layernorm_forward / _backward, ..._forward_bf16) fixes row_step = 1, both parameter gradients and a direct reduction.
+ * row_step: logical row r of x / y / dy / dx / delta / xout lives at physical row r * row_step (token 0 of every frame in the pruned last
+ * block); mean / rstd are dense.  The backward scratch is dgvit_layernorm_backward_scratch_floats(rows, D) for both precisions.
+ * dgamma / dbeta may be NULL (frozen parameter); grouped != 0 queues the parameter-gradient reduction into a reduce group and flushes
+ * it, as a layer of dgvit_got_backward does (same bits as the direct reduction). */
+int dgvit_diag_layernorm_forward(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int rows, int D,
+                                 int row_step, void* stream);
+int dgvit_diag_layernorm_backward(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dres,
+                                  float* dx, float* dgamma, float* dbeta, float* scratch, long long scratch_floats, int rows, int D,
+                                  int row_step, int grouped, void* stream);
+/* bf16 LayerNorm forward, dispatched as the bf16 encoder does: delta == NULL: y = LN(x); delta with xout, mean and rstd: xout = x + delta,
+ * y = LN(xout) (any row_step); otherwise the joint form of the no-grad schedule: v = (x + delta) [+ delta2], xout (unless NULL) = v,
+ * y = LN(v), row_step 1, mean == rstd == NULL.  mean and rstd are given or omitted together. */
+int dgvit_diag_layernorm_forward_bf16(const float* x, const unsigned short* delta, const unsigned short* delta2, float* xout,
+                                      const float* gamma, const float* beta, unsigned short* y, float* mean, float* rstd, int rows, int D,
+                                      int row_step, void* stream);
+/* bf16 LayerNorm backward: dy bf16, dx fp32, dxb (may be NULL) its bf16 copy */
+int dgvit_diag_layernorm_backward_bf16(const unsigned short* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                       const float* dres, float* dx, unsigned short* dxb, float* dgamma, float* dbeta, float* scratch,
+                                       long long scratch_floats, int rows, int D, int row_step, void* stream);
+/* xout = x + delta on `rows` rows of D floats, row_step as above (the last residual add of the bf16 encoder) */
+int dgvit_diag_residual_add_bf16(const float* x, const unsigned short* delta, float* xout, int rows, int D, int row_step, void* stream);
+/* dst (cols x rows, bf16) = src (rows x cols, fp32)^T; rows and cols multiples of 8 */
+int dgvit_diag_transpose_cast_f32_bf16(const float* src, unsigned short* dst, int rows, int cols, void* stream);
+/* out[n] = sum over t < rows of a[row(t)][n], row(t) = t, or t + t / rgrp + 1 for rgrp > 0 (the patch rows of frames of rgrp + 1 tokens:
+ * the positional embedding's gradient skips every frame's token 0); a's rows are lda floats apart */
+long long dgvit_diag_colsum_scratch_floats(int rows, int cols);
+int dgvit_diag_colsum(const float* a, long long lda, float* out, float* scratch, long long scratch_floats, int rows, int cols, int rgrp,
+                      void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
