@@ -119,6 +119,10 @@ SIGNATURES = {
     "dgvit_ring_store_frames": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _P, _I, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_ring_store_small": (_I, [dgvit_small_fields, _P, _P, _I, _LL, _LL, _LL, _P]),
     "dgvit_nstep_walk_strided": (_I, [_P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _LL, _LL, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
+    # the ring that stores each frame once (include/dgvit_hip.h: The ring that stores each frame once)
+    "dgvit_ring_plan_next": (_I, [_P, _P, _P, _P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_ring_store_frames_shared": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _P, _I, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_ring_next_rows": (_I, [_P, _P, _P, _LL, _LL, _P]),
     "dgvit_per_tree_floats": (_LL, [_LL]),
     "dgvit_per_init": (_I, [_P, _LL, _P]),
     "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),

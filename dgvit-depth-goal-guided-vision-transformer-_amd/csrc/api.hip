@@ -325,6 +325,21 @@ extern "C" int dgvit_nstep_walk_strided(const float* rew, long long rew_ld, cons
   return nstep_walk_strided(rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, stride, n, gamma, ret_out, done_out,
                             discount_out, next_small_out, steps_out, tail_out, (hipStream_t)stream);
 }
+// the ring that stores each frame once (replay_ring.hip)
+extern "C" int dgvit_ring_plan_next(int* next_row, long long* state, int* moves, const float* done, long long done_ld,
+                                    const unsigned char* flags, long long n, long long nrows, long long start, long long envs, long long pool,
+                                    void* stream) {
+  return ring_plan_next(next_row, state, moves, done, done_ld, flags, n, nrows, start, envs, pool, (hipStream_t)stream);
+}
+extern "C" int dgvit_ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8,
+                                              long long src1_ld, void* arena, const int* moves, int ring_u8, long long ring_ld, long long n,
+                                              long long cols, long long nrows, long long start, long long envs, long long pool, void* stream) {
+  return ring_store_frames_shared(src0, src0_u8, src0_ld, src1, src1_u8, src1_ld, arena, moves, ring_u8, ring_ld, n, cols, nrows, start, envs,
+                                  pool, (hipStream_t)stream);
+}
+extern "C" int dgvit_ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, void* stream) {
+  return ring_next_rows(next_row, idx, out, nsel, nrows, (hipStream_t)stream);
+}
 // prioritized replay (replay.hip)
 extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }
 extern "C" int dgvit_per_init(float* tree, long long capacity, void* stream) { return per_init(tree, capacity, (hipStream_t)stream); }

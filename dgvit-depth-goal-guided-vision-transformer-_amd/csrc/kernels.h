@@ -106,6 +106,14 @@ int nstep_walk_strided(const float* rew, long long rew_ld, const float* done, lo
                        const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows, long long stride,
                        int n, double gamma, float* ret_out, float* done_out, float* discount_out, float* next_small_out, int* steps_out,
                        long long* tail_out, hipStream_t stream);
+// the ring that stores each frame once: the bookkeeping of a store, its frames into the one arena, and the arena rows of sampled slots'
+// next_obs (include/dgvit_hip.h: The ring that stores each frame once)
+int ring_plan_next(int* next_row, long long* state, int* moves, const float* done, long long done_ld, const unsigned char* flags, long long n,
+                   long long nrows, long long start, long long envs, long long pool, hipStream_t stream);
+int ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* arena,
+                             const int* moves, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
+                             long long envs, long long pool, hipStream_t stream);
+int ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, hipStream_t stream);
 // replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
 long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
 int per_init(float* tree, long long capacity, hipStream_t stream);

@@ -14,6 +14,10 @@
 //                             environments -- from device memory, fp32 or uint8 source, either ring
 //   ring_store_small        : their five small fields and, for one step, its marks (HEAD | END per environment) in one launch
 //   nstep_walk_strided      : nstep_walk along one environment's slots, (i + k E) mod nrows
+//   ring_plan_next          : the ring that stores each frame once: which arena row holds each slot's next_obs after a store,
+//                             the FIFO of the terminal pool, and the store's move list -- one wave, 64 rows a round
+//   ring_store_frames_shared: the obs rows, the moves into the pool and the pending rows of that store in one launch
+//   ring_next_rows          : out[i] = next_row[idx[i]], the index tensor of the next_obs gather over the arena
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
 // the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
@@ -352,6 +356,148 @@ __global__ void __launch_bounds__(256) ring_store_small_kernel(dgvit_small_field
   }
 }
 
+// ---- the ring that stores each frame once: one frame arena of nrows + E + P rows -- the obs ring, one pending row per lane
+// (the next_obs of the lane's newest transition) and a FIFO pool of P rows for the next_obs of transitions that ended an episode.
+// next_row[s] is the arena row that holds slot s's next_obs (-1: never written); state = {head, tail, lost}, counters that only grow.
+
+// The bookkeeping of a store of n slots at `start`, ONE wave.  Per round of 64 rows lane k takes row 64 r + k: it loads what its row depends on -- next_row of the slot it overwrites, and next_row, done and flags of its lane predecessor p =
+// (s - E) mod nrows -- then every lane runs the same 64 steps of integer arithmetic on the ballots (the FIFO: a freed entry advances
+// head, a terminal predecessor takes entry tail % P or, pool full, is lost), keeps the outcome of its own row, and writes it.  Nothing a
+// row loads is written by another row of the same launch: next_row[s] is written by row j itself and by row j + E (whose predecessor it
+// is), next_row[p] of a row j < E lies outside the store -- unless the store covers the whole ring: such a predecessor is one of the
+// call's own last rows, already overwritten, and does not count; done and flags are the ring's, final since dgvit_ring_store_small.
+// Row j leaves next_row[s] to row j + E where there is one.
+__global__ void __launch_bounds__(64) ring_plan_next_kernel(int* __restrict__ next_row, long long* __restrict__ state, int* __restrict__ moves,
+                                                            const float* __restrict__ done, long long done_ld,
+                                                            const unsigned char* __restrict__ flags, long long n, long long nrows,
+                                                            long long start, long long E, long long P) {
+  const int lane = threadIdx.x;
+  long long head = state[0], tail = state[1], lost = state[2];
+  long long slot_of_tail = tail % P;   // the pool entry the next allocation takes
+  const long long pool = nrows + E;
+  for (long long base = 0; base < n; base += 64) {   // wave-uniform
+    const long long j = base + lane;
+    const bool live = j < n;
+    long long s = 0, p = 0;
+    bool frees = false, has_pred = false, terminal = false;
+    if (live) {
+      s = start + j;
+      if (s >= nrows) s -= nrows;
+      p = s - E;
+      if (p < 0) p += nrows;
+      frees = next_row[s] >= pool;
+      has_pred = nrows > E && (j >= E || (n < nrows && next_row[p] >= 0));
+      terminal = has_pred && (done[p * done_ld] != 0.f || (flags[p] & RING_END) != 0);
+    }
+    const unsigned long long fmask = __ballot(frees), tmask = __ballot(terminal);
+    long long mine = -1;               // the pool entry of this lane's predecessor; -2: lost
+    const int rows = (int)(n - base < 64 ? n - base : 64);
+    for (int k = 0; k < rows; ++k) {   // the same arithmetic in every lane
+      if ((fmask >> k) & 1) ++head;
+      if ((tmask >> k) & 1) {
+        long long got = -2;
+        if (tail - head < P) {
+          got = slot_of_tail;
+          ++tail;
+          if (++slot_of_tail == P) slot_of_tail = 0;
+        } else {
+          ++lost;
+        }
+        if (k == lane) mine = got;
+      }
+    }
+    if (live) {
+      if (j + E >= n) next_row[s] = (int)(nrows + s % E);   // the lane's pending row
+      moves[j] = mine >= 0 ? (int)(pool + mine) : -1;
+      if (has_pred) next_row[p] = terminal ? (mine >= 0 ? (int)(pool + mine) : (int)p) : (int)s;
+    }
+  }
+  if (lane == 0) {
+    state[0] = head;
+    state[1] = tail;
+    state[2] = lost;
+  }
+}
+
+// one group of 4 pixels, row r of a source into group `at` of the arena: the three conversions of ring_store_frames_kernel, which keeps
+// its own copy -- the two-matrix ring's kernels are not touched by the shared ring
+template <bool RING_U8>
+__device__ __forceinline__ void store_group(const frame_src& s, long long r, int c, int cols, void* __restrict__ arena, long long at) {
+  const int p0 = 4 * c;
+  const bool whole = s.vec && p0 + 4 <= cols;
+  if (RING_U8 && s.u8) {        // codes as they are
+    const unsigned char* __restrict__ b = static_cast<const unsigned char*>(s.p) + r * s.ld + p0;
+    uint32_t w = 0;
+    if (whole) {
+      w = *reinterpret_cast<const uint32_t*>(b);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (p0 + e < cols) w |= (uint32_t)b[e] << (8 * e);
+    }
+    static_cast<uint32_t*>(arena)[at] = w;
+    return;
+  }
+  const float* __restrict__ f = static_cast<const float*>(s.p) + r * s.ld + p0;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (whole) {
+    const float4 t = *reinterpret_cast<const float4*>(f);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (p0 + e < cols) v[e] = f[e];
+  }
+  if (RING_U8)
+    static_cast<uint32_t*>(arena)[at] = quant_u8(v[0]) | (quant_u8(v[1]) << 8) | (quant_u8(v[2]) << 16) | (quant_u8(v[3]) << 24);
+  else
+    static_cast<float4*>(arena)[at] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// The frames of a store into the arena, after its bookkeeping.  blockIdx.y == 0: the obs rows into the ring, as ring_store_frames.
+// blockIdx.y == 1, thread = group c of row r: the move of row r (the next_obs of r's terminal predecessor into its pool row -- out of the
+// lane's pending row for r < E, out of the call's own next_obs row r - E otherwise) and then, for r < E, the next_obs of the lane's LAST
+// row of the call into the pending row.  The read of a pending group and the write over it are this one thread's, in this order; pool rows
+// are written by moves alone and no two moves of a launch share one (ring_plan_next_kernel); sources are never written.
+template <bool RING_U8>
+__global__ void __launch_bounds__(256) ring_store_frames_shared_kernel(frame_src s0, frame_src s1, void* __restrict__ arena,
+                                                                       const int* __restrict__ moves, long long total4, int row4, int cols,
+                                                                       long long nrows, long long start, long long n, long long E,
+                                                                       long long arena_rows) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long long r = i / row4;
+  const int c = (int)(i - r * row4);
+  if (blockIdx.y == 0) {
+    long long d = start + r;    // start < nrows and r < n <= nrows: one subtraction wraps the ring
+    if (d >= nrows) d -= nrows;
+    store_group<RING_U8>(s0, r, c, cols, arena, d * row4 + c);
+    return;
+  }
+  const long long m = moves[r];
+  const bool move = m >= nrows + E && m < arena_rows;   // a pool row, whatever the table holds
+  if (r >= E) {
+    if (move) store_group<RING_U8>(s1, r - E, c, cols, arena, m * row4 + c);
+    return;
+  }
+  const long long pending = (nrows + r) * row4 + c;     // E divides start: row r < E is lane r
+  if (move) {
+    if (RING_U8) static_cast<uint32_t*>(arena)[m * row4 + c] = static_cast<const uint32_t*>(arena)[pending];
+    else static_cast<float4*>(arena)[m * row4 + c] = static_cast<const float4*>(arena)[pending];
+  }
+  store_group<RING_U8>(s1, r + (n - 1 - r) / E * E, c, cols, arena, pending);
+}
+
+// out[i] = next_row[idx[i]], the arena row of the slot's next_obs; a slot never written gives itself, a row of zeros
+__global__ void __launch_bounds__(256) ring_next_rows_kernel(const int* __restrict__ next_row, const long long* __restrict__ idx,
+                                                             long long* __restrict__ out, long long nsel, long long nrows) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nsel) return;
+  const long long s = ring_row(idx[i], nrows);
+  const long long r = next_row[s];
+  out[i] = r < 0 ? s : r;
+}
+
 // both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
 template <typename T>
 int launch_gather_shift(const char* name, const T* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
@@ -570,6 +716,79 @@ int ring_store_small(const dgvit_small_fields& fields, unsigned char* flags, con
   hipLaunchKernelGGL(ring_store_small_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, fields, (int)tot4, flags, episode_end, end_f32, n,
                      nrows, start);
   DGVIT_CHECK_LAUNCH("ring_store_small");
+  return DGVIT_OK;
+}
+
+namespace {
+
+// the lanes and the pool of a shared ring, and a store's place in them: what ring_plan_next and ring_store_frames_shared ask alike
+int check_shared(const char* name, long long n, long long nrows, long long start, long long envs, long long pool) {
+  if (const int rc = check_slots(name, n, nrows, start)) return rc;
+  DGVIT_CHECK_ARG(envs >= 1 && envs <= nrows && nrows % envs == 0, "%s: envs=%lld must be in [1, nrows] and divide nrows=%lld", name, envs, nrows);
+  DGVIT_CHECK_ARG(n % envs == 0 && start % envs == 0, "%s: n=%lld and start=%lld must be multiples of envs=%lld", name, n, start, envs);
+  DGVIT_CHECK_ARG(pool >= 1 && pool <= nrows, "%s: pool=%lld must be in [1, nrows] = [1, %lld]", name, pool, nrows);
+  DGVIT_CHECK_ARG(nrows + envs + pool < (1ll << 31), "%s: the arena's nrows + envs + pool = %lld rows must be below 2^31", name,
+                  nrows + envs + pool);
+  return DGVIT_OK;
+}
+
+}  // namespace
+
+int ring_plan_next(int* next_row, long long* state, int* moves, const float* done, long long done_ld, const unsigned char* flags, long long n,
+                   long long nrows, long long start, long long envs, long long pool, hipStream_t stream) {
+  DGVIT_CHECK_ARG(next_row && state && moves && done && flags, "ring_plan_next: next_row, state, moves, done and flags must not be null");
+  if (const int rc = check_shared("ring_plan_next", n, nrows, start, envs, pool)) return rc;
+  DGVIT_CHECK_ARG(done_ld > 0, "ring_plan_next: done_ld=%lld must be positive", done_ld);
+  DGVIT_CHECK_ARG(al4p(next_row) && al4p(moves) && al4p(done) && al8p(state),
+                  "ring_plan_next: next_row, moves and done must be 4-byte aligned, state 8-byte aligned");
+  hipLaunchKernelGGL(ring_plan_next_kernel, dim3(1), dim3(64), 0, stream, next_row, state, moves, done, done_ld, flags, n, nrows, start, envs,
+                     pool);
+  DGVIT_CHECK_LAUNCH("ring_plan_next");
+  return DGVIT_OK;
+}
+
+int ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* arena,
+                             const int* moves, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
+                             long long envs, long long pool, hipStream_t stream) {
+  DGVIT_CHECK_ARG(src0 && src1 && arena && moves, "ring_store_frames_shared: src0, src1, arena and moves must not be null");
+  DGVIT_CHECK_ARG((src0_u8 | src1_u8 | ring_u8) >> 1 == 0, "ring_store_frames_shared: src0_u8=%d, src1_u8=%d and ring_u8=%d must be 0 or 1",
+                  src0_u8, src1_u8, ring_u8);
+  DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "ring_store_frames_shared: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring",
+                  src0_u8, src1_u8);
+  if (const int rc = check_shared("ring_store_frames_shared", n, nrows, start, envs, pool)) return rc;
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_store_frames_shared: cols=%lld must be in [1, 2^25]", cols);
+  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
+                  "ring_store_frames_shared: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring_ld,
+                  ring_u8 ? 16 : 4, cols);
+  DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "ring_store_frames_shared: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld",
+                  src0_ld, src1_ld, cols);
+  DGVIT_CHECK_ARG(al16(arena) && al4p(moves) && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)),
+                  "ring_store_frames_shared: the arena must be 16-byte, moves and fp32 sources 4-byte aligned");
+  const int row4 = (int)(ring_ld / 4);   // groups of 4 pixels per arena row, a dword of bytes or a float4
+  const long long total4 = n * row4, blocks = (total4 + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_store_frames_shared: n=%lld rows of ring_ld=%lld are more than one launch covers", n, ring_ld);
+  const auto source = [](const void* p, int u8, long long ld) {
+    const bool vec = u8 ? (ld % 4 == 0 && al4p(p)) : (ld % 4 == 0 && al16(p));
+    return frame_src{p, ld, u8, (int)vec};
+  };
+  const frame_src s0 = source(src0, src0_u8, src0_ld), s1 = source(src1, src1_u8, src1_ld);
+  if (ring_u8)
+    hipLaunchKernelGGL(ring_store_frames_shared_kernel<true>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, arena, moves, total4, row4,
+                       (int)cols, nrows, start, n, envs, nrows + envs + pool);
+  else
+    hipLaunchKernelGGL(ring_store_frames_shared_kernel<false>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, arena, moves, total4,
+                       row4, (int)cols, nrows, start, n, envs, nrows + envs + pool);
+  DGVIT_CHECK_LAUNCH("ring_store_frames_shared");
+  return DGVIT_OK;
+}
+
+int ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, hipStream_t stream) {
+  DGVIT_CHECK_ARG(next_row && idx && out, "ring_next_rows: next_row, idx and out must not be null");
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31) && nrows > 0, "ring_next_rows: nsel=%lld must be in [1, 2^31) and nrows=%lld positive", nsel,
+                  nrows);
+  DGVIT_CHECK_ARG(al4p(next_row) && al8p(idx) && al8p(out), "ring_next_rows: next_row must be 4-byte, idx and out 8-byte aligned");
+  hipLaunchKernelGGL(ring_next_rows_kernel, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, stream, next_row, idx, out, nsel, nrows);
+  DGVIT_CHECK_LAUNCH("ring_next_rows");
   return DGVIT_OK;
 }
 

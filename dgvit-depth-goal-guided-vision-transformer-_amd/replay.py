@@ -13,7 +13,8 @@ Consecutive ring slots are consecutive environment steps, so ``sample(..., n_ste
 ``Nstep`` option -- by a walk along the ring at sample time: nothing extra is stored and n and gamma may change from call
 to call.  What a walk may not cross is kept in ``episode_flags``, one byte per slot on the device.  With ``num_envs=E`` the ring holds E
 parallel environments, a vector step in E consecutive slots, and an environment's steps lie E slots apart: ``add_vec``
-stores such a step from device tensors without visiting the host.
+stores such a step from device tensors without visiting the host.  ``shared_next_obs=True`` stores each frame once: a transition's
+``next_obs`` is its successor's ``obs`` row, and only the frames without a successor slot are kept apart.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -65,6 +66,20 @@ def _num_envs(num_envs, size):
     return int(num_envs)
 
 
+def _shared_next(shared, terminal_frames, size, num_envs):
+    """``shared_next_obs`` and ``terminal_frames`` after their checks (``size`` and ``num_envs`` have passed theirs) -> (bool, P or None):
+    host-only, runs before anything touches a device"""
+    if not isinstance(shared, (bool, np.bool_)):
+        raise ValueError(f"shared_next_obs must be a bool, got {shared!r}")
+    if terminal_frames is None:
+        return bool(shared), num_envs * -(-(size // num_envs) // 2) if shared else None   # every other slot of every lane
+    if not shared:
+        raise ValueError(f"terminal_frames={terminal_frames!r} sizes the terminal pool of a shared ring: pass shared_next_obs=True with it")
+    if isinstance(terminal_frames, bool) or not isinstance(terminal_frames, (int, np.integer)) or not 1 <= int(terminal_frames) <= size:
+        raise ValueError(f"terminal_frames must be None or an int in [1, size] = [1, {size}], got {terminal_frames!r}")
+    return True, int(terminal_frames)
+
+
 SMALL_FIELDS = ("pobs", "act", "rew", "next_pobs", "done")   # what one dgvit_ring_store_small launch stores
 
 
@@ -93,12 +108,29 @@ class DeviceReplayBuffer:
     of E, environment e in slot ``base + e``.  The successor of slot s in its episode is ``(s + E) % size``, and because E divides ``size``
     the lane ``s % E`` survives the wrap; ``sample(n_step=...)`` walks with that stride, ``idx % num_envs`` is a sampled slot's
     environment, and ``stored`` / ``next_index`` keep counting slots.  HEAD then marks the E newest slots.  With E > 1 ``add`` and
-    ``add_batch`` are refused (a demonstration episode has no lane) and ``on_episode_end`` takes the environments that ended."""
+    ``add_batch`` are refused (a demonstration episode has no lane) and ``on_episode_end`` takes the environments that ended.
+
+    Each frame once.  ``shared_next_obs=True`` (keyword-only; default False, which changes nothing) keeps ONE frame arena,
+    ``self.arena``, of ``arena_rows = size + num_envs + terminal_frames`` rows in the ring's frame format in the place of the two frame
+    matrices.  The contract: inside an episode, the ``obs`` of a lane's step t + 1 is the frame that was ``next_obs`` of its step t --
+    what every environment loop passes anyway.  That ``next_obs`` is then not kept: the successor's ``obs`` row is it.  Rows [0, size)
+    of the arena are the ``obs`` ring (``store["obs"]`` is that view, and ``store`` has no ``"next_obs"``), rows [size, size + E) one
+    *pending* row per lane with the ``next_obs`` of the lane's newest transition, and the last ``terminal_frames`` rows a FIFO pool for
+    the ``next_obs`` of transitions that ended an episode -- END flag or ``done != 0``, where the n-step walk stops too -- and are still
+    in the ring.  ``add``, ``add_batch`` and ``add_vec`` keep their keywords (``next_obs`` is still passed), ``sample`` returns the same
+    batches, and the constructor starts ``track_episodes()``.  ``terminal_frames=P`` (an int in [1, size]) sizes the pool; when more
+    than P ended transitions are in the ring at once the newest of them lose their last frame (``lost_terminal_frames()``).  The
+    default is ``E * ceil(size / E / 2)``, every other slot of every lane: it cannot overflow while episodes last two steps or more,
+    because two neighbouring slots of a lane are then never both an episode's last.  Where episodes are known to be long, a smaller
+    pool saves more: ``size // L`` entries and some slack serve episodes of L steps.  The frames take (size + E + P) rows against
+    2 size."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2,
-                 device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32, num_envs=1):
+                 device="cuda", seed: Optional[int] = None, *, frame_dtype=torch.float32, num_envs=1, shared_next_obs=False,
+                 terminal_frames=None):
         self.frame_dtype = _frame_dtype(frame_dtype)
         self.num_envs = _num_envs(num_envs, size)
+        self.shared_next_obs, self.terminal_frames = _shared_next(shared_next_obs, terminal_frames, int(size), self.num_envs)
         self.size, self.device = int(size), torch.device(device)
         if self.device.type != "cuda":
             raise _lib.DgvitError("DeviceReplayBuffer lives in HBM; pass a ROCm device")
@@ -108,7 +140,19 @@ class DeviceReplayBuffer:
                        "act": (act_dim,), "rew": (1,), "done": (1,)}
         # every field is a (size, row) fp32 matrix whose row length is padded to a multiple of 4 floats (float4 gather)
         self.rows = {k: _al4(n) for k, n in self.fields.items()}
-        if self.frame_dtype is torch.uint8:      # a frame's ring row is al16(H*W) bytes; the rows sample() returns stay al4(H*W) floats
+        self.arena = self.arena_rows = None
+        if self.shared_next_obs:                 # one arena of size + E + P frame rows; store["obs"] is its first `size` rows
+            u8 = self.frame_dtype is torch.uint8
+            if u8:
+                self.row_bytes = _al16(self.fields["obs"])
+            self.arena_rows = self.size + self.num_envs + self.terminal_frames
+            self.arena = torch.zeros(self.arena_rows, self.row_bytes if u8 else self.rows["obs"], dtype=self.frame_dtype, device=self.device)
+            self.store = {k: self.arena[:self.size] if k == "obs" else torch.zeros(self.size, r, dtype=torch.float32, device=self.device)
+                          for k, r in self.rows.items() if k != "next_obs"}
+            self.next_row = torch.full((self.size,), -1, dtype=torch.int32, device=self.device)    # the arena row of each slot's next_obs
+            self._pool_state = torch.zeros(3, dtype=torch.int64, device=self.device)               # head, tail, lost of the pool's FIFO
+            self._step_moves = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)   # a step's move list, rewritten per store
+        elif self.frame_dtype is torch.uint8:    # a frame's ring row is al16(H*W) bytes; the rows sample() returns stay al4(H*W) floats
             self.row_bytes = _al16(self.fields["obs"])
             self.store = {k: torch.zeros(self.size, self.row_bytes, dtype=torch.uint8, device=self.device) if k in FRAME_FIELDS
                           else torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
@@ -119,6 +163,14 @@ class DeviceReplayBuffer:
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
             self.gen.manual_seed(int(seed))
+        if self.shared_next_obs:                 # the bookkeeping reads END from the first slot on
+            self.track_episodes()
+
+    def lost_terminal_frames(self) -> int:
+        """How many transitions that ended an episode found the terminal pool full when their successor was stored (a shared ring; 0 on
+        any other).  Such a slot returns its own ``obs`` as ``next_obs``.  A non-zero value means that ``terminal_frames`` is too small
+        for the episode lengths: more than that many ended transitions were in the ring at once.  A device read: it synchronises."""
+        return int(self._pool_state[2].item()) if self.shared_next_obs else 0
 
     def get_stored_size(self) -> int:
         return self.stored
@@ -204,7 +256,9 @@ class DeviceReplayBuffer:
         (DRL.py:379-386).  Which fields the matrix holds is the call's, so its column offsets are too.  Then dgvit_ring_store_frames for
         ``obs`` and ``next_obs`` and dgvit_ring_store_small for the other five fields, both wrapping the ring per row.  The marks of one
         step (n == num_envs: ``add``, ``add_vec``) are the second launch's; a longer run of one episode's slots (``add_batch``) is marked
-        by dgvit_ring_mark, only its last slot the HEAD, and only when episodes are tracked."""
+        by dgvit_ring_mark, only its last slot the HEAD, and only when episodes are tracked.  A ``shared_next_obs`` ring stores its frames
+        last and in another way: dgvit_ring_plan_next, the bookkeeping of ``next_row`` and the terminal pool, which reads ``done`` and END of
+        the slots before the new ones from the ring, and dgvit_ring_store_frames_shared into the one arena."""
         off, row = {}, 0
         for k, v in rows.items():
             if not torch.is_tensor(v):
@@ -245,13 +299,24 @@ class DeviceReplayBuffer:
         step = n == self.num_envs
         with torch.cuda.device(self.device):
             (p0, c0, ld0), (p1, c1, ld1) = source("obs"), source("next_obs")
-            rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
-                                             self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, st)
-            _lib.check(rc, "dgvit_ring_store_frames")
+            if not self.shared_next_obs:
+                rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
+                                                 self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, st)
+                _lib.check(rc, "dgvit_ring_store_frames")
             rc = lib.dgvit_ring_store_small(small, _ptr(self.episode_flags if step else None), end_ptr, end_f32, n, self.size, i, st)
             _lib.check(rc, "dgvit_ring_store_small")
             if self.episode_flags is not None and not step:
                 _lib.check(lib.dgvit_ring_mark(_ptr(self.episode_flags), self.size, i, n, st), "dgvit_ring_mark")
+            if self.shared_next_obs:             # the frames go last: where they go depends on done and END of the slots before
+                E, P = self.num_envs, self.terminal_frames
+                moves = self._step_moves if step else torch.empty(n, dtype=torch.int32, device=self.device)
+                rc = lib.dgvit_ring_plan_next(_ptr(self.next_row), _ptr(self._pool_state), _ptr(moves), _ptr(self.store["done"]),
+                                              self.rows["done"], _ptr(self.episode_flags), n, self.size, i, E, P, st)
+                _lib.check(rc, "dgvit_ring_plan_next")
+                rc = lib.dgvit_ring_store_frames_shared(p0, c0, ld0, p1, c1, ld1, _ptr(self.arena), _ptr(moves), int(u8),
+                                                        self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, E, P,
+                                                        st)
+                _lib.check(rc, "dgvit_ring_store_frames_shared")
         self.next_index = (i + n) % self.size
         self.stored = min(self.stored + n, self.size)
         self._on_store(i, n)
@@ -283,7 +348,7 @@ class DeviceReplayBuffer:
         codes_ok = self.frame_dtype is torch.uint8 and k in FRAME_FIELDS
         on_device = torch.is_tensor(v) and v.device.type != "cpu"
         if on_device:
-            home = self.store[k].device
+            home = self.store["obs"].device      # every field's: a shared ring has no store["next_obs"]
             if v.device != home:
                 raise ValueError(f"{k}: the tensor is on {v.device}, the ring on {home}")
             v = v.detach()
@@ -361,7 +426,11 @@ class DeviceReplayBuffer:
         the call starts ``track_episodes()`` if nothing has; inside one the flags must exist already, and a replayed graph follows
         the ring as later ``add()``s move it.  ``n_step=None`` is the one-step path above, launch for launch.  On a ring with
         ``num_envs=E > 1`` the walk follows the slot's own environment, ``(i + k E) % size``, and nothing else changes: ``indexes`` are
-        slots, ``indexes % num_envs`` their environments."""
+        slots, ``indexes % num_envs`` their environments.
+
+        On a ``shared_next_obs=True`` ring ``next_obs`` comes out of the arena with the same gather, at the rows ``next_row`` names for
+        the sampled slots (the walk's last ones for ``n_step``): one small launch more, dgvit_ring_next_rows, and nothing else changes --
+        a replayed graph follows later ``add()``s because the table lives on the device."""
         n_step, gamma = _n_step(n_step), _unit("gamma", gamma)
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
         if n_step is not None:
@@ -385,16 +454,20 @@ class DeviceReplayBuffer:
                     out[k] = walk.pop(k)
                     continue
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
+                src, nrows, rows_at = self.store.get(k), self.size, at
+                if k == "next_obs" and self.shared_next_obs:   # the same gathers over the arena, at the rows next_row names
+                    src, nrows, rows_at = self.arena, self.arena_rows, torch.empty(B, dtype=torch.int64, device=self.device)
+                    _lib.check(lib.dgvit_ring_next_rows(_ptr(self.next_row), _ptr(at), _ptr(rows_at), B, self.size, st), "dgvit_ring_next_rows")
                 if pad and k in FRAME_FIELDS:
                     shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
-                    _gather_shift(self.store[k], at, buf, shifts, self.shapes[k], self.size, pad, int(k == "next_obs"), self.shift_seed)
+                    _gather_shift(src, rows_at, buf, shifts, self.shapes[k], nrows, pad, int(k == "next_obs"), self.shift_seed)
                     if return_shifts:
                         out[k + "_shift"] = shifts
                 elif u8 and k in FRAME_FIELDS:
-                    rc = lib.dgvit_gather_rows_u8(_ptr(self.store[k]), _ptr(at), _ptr(buf), B, n, self.row_bytes, r, self.size, st)
+                    rc = lib.dgvit_gather_rows_u8(_ptr(src), _ptr(rows_at), _ptr(buf), B, n, self.row_bytes, r, nrows, st)
                     _lib.check(rc, "dgvit_gather_rows_u8")
                 else:
-                    rc = lib.dgvit_gather_rows(_ptr(self.store[k]), _ptr(at), _ptr(buf), B, r, self.size, st)
+                    rc = lib.dgvit_gather_rows(_ptr(src), _ptr(rows_at), _ptr(buf), B, r, nrows, st)
                     _lib.check(rc, "dgvit_gather_rows")
                 out[k] = buf[:, :n].reshape(B, *self.shapes[k])
         if return_shifts and not pad:
@@ -462,15 +535,17 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",
-                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32, num_envs=1):
+                 seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32, num_envs=1,
+                 shared_next_obs=False, terminal_frames=None):
         _frame_dtype(frame_dtype)
-        _num_envs(num_envs, size)
+        _shared_next(shared_next_obs, terminal_frames, int(size), _num_envs(num_envs, size))
         self.alpha = _unit("alpha", alpha)
         if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not 0.0 <= float(eps) < float("inf"):
             raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
         self.eps = float(eps)
         self._levels, floats = per_tree_layout(int(size))
-        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed, frame_dtype=frame_dtype, num_envs=num_envs)
+        super().__init__(size, obs_shape, pstate_dim, act_dim, device, seed, frame_dtype=frame_dtype, num_envs=num_envs,
+                         shared_next_obs=shared_next_obs, terminal_frames=terminal_frames)
         lib = _lib.load()
         if lib.dgvit_per_tree_floats(self.size) != floats:
             raise _lib.DgvitError("dgvit_per_tree_floats disagrees with replay.per_tree_layout; rebuild the library")

@@ -493,6 +493,47 @@ int dgvit_nstep_walk_strided(const float* rew, long long rew_ld, const float* do
                              float* next_small_out, int* steps_out, long long* tail_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The ring that stores each frame once (dgvit_amd.replay: DeviceReplayBuffer(shared_next_obs=True)).  Inside an episode
+ * the obs of a lane's step t + 1 is the next_obs of its step t, so ONE frame arena of nrows + envs + pool rows (ring format: fp32 rows
+ * of ring_ld floats or uint8 rows of ring_ld bytes) replaces the two frame matrices:
+ *   rows [0, nrows)                         the obs ring
+ *   rows [nrows, nrows + envs)              one pending row per lane: the next_obs of the lane's newest transition
+ *   rows [nrows + envs, nrows + envs + pool) the terminal pool, a FIFO: the next_obs of transitions that ended an episode
+ * next_row (nrows int32; -1 = never written) names the arena row of every slot's next_obs; state is three int64 {head, tail, lost},
+ * counters that only grow: pool entries tail - head are live, entry k lies in pool row k % pool.  Both start as -1s and zeros.
+ *
+ * dgvit_ring_plan_next: the bookkeeping of a store of n slots at `start`, after dgvit_ring_store_small (and dgvit_ring_mark) of the
+ *   same slots, so that done (read at done[s * done_ld]) and flags of a predecessor are the ring's.  For j = 0 .. n - 1 in this order,
+ *   s = (start + j) % nrows, p = (s - envs) mod nrows:
+ *     1. next_row[s] inside the pool: ++head (the overwritten slot's entry is free)
+ *     2. next_row[s] = nrows + s % envs, the lane's pending row
+ *     3. p counts when nrows > envs, next_row[p] != -1 and p is not one of the call's own later rows (n == nrows, j < envs: that
+ *        transition is already overwritten); it is terminal when done[p] != 0 or flags[p] has END
+ *     4. p not terminal:                 next_row[p] = s                       moves[j] = -1
+ *     5. p terminal, tail - head < pool: next_row[p] = nrows + envs + tail % pool = moves[j], ++tail
+ *     6. p terminal, the pool full:      next_row[p] = p, ++lost                moves[j] = -1   (the slot's own obs stands in)
+ *   moves (n int32) tells dgvit_ring_store_frames_shared which rows carry a frame into the pool.  One launch of one wave, 64 rows a
+ *   round: the loads and stores of a round are parallel, the FIFO's counters are advanced in row order; no atomics; deterministic.
+ *   envs divides nrows, n and start; 1 <= pool <= nrows; nrows + envs + pool < 2^31.
+ * dgvit_ring_store_frames_shared: the frames of the same store in ONE launch, sources and conversions as dgvit_ring_store_frames:
+ *     arena[(start + i) % nrows]  = src0[i]                                        the obs rows
+ *     arena[moves[j]]             = j < envs ? arena[nrows + j] : src1[j - envs]   where moves[j] is a pool row: the terminal
+ *                                                                                  predecessor's next_obs, out of the pending row or
+ *                                                                                  out of the call's own rows
+ *     arena[nrows + l]            = src1[last row of lane l in the call]           l < envs, after the move out of that row
+ *   A move out of a pending row and the write over it are one thread's per pixel group, in that order.
+ * dgvit_ring_next_rows: out[i] (int64) = next_row[clamp(idx[i], 0, nrows-1)], the index tensor of the next_obs gather over the arena
+ *   (dgvit_gather_rows[_u8], dgvit_gather_shift_frames[_u8] with nrows = the arena's rows); a slot never written gives itself.
+ * None of the three synchronises; all are capturable.
+ * -------------------------------------------------------------------------------------------- */
+int dgvit_ring_plan_next(int* next_row, long long* state, int* moves, const float* done, long long done_ld, const unsigned char* flags,
+                         long long n, long long nrows, long long start, long long envs, long long pool, void* stream);
+int dgvit_ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld,
+                                   void* arena, const int* moves, int ring_u8, long long ring_ld, long long n, long long cols,
+                                   long long nrows, long long start, long long envs, long long pool, void* stream);
+int dgvit_ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
  * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
  *
