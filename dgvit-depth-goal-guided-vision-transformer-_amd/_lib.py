@@ -47,7 +47,14 @@ class dgvit_small_fields(Structure):
                 ("cols", c_int * SMALL_FIELDS), ("ring_ld", c_int * SMALL_FIELDS)]
 
 
-GRAD_NORM_PARTIALS = 512   # include/dgvit_hip.h: DGVIT_GRAD_NORM_PARTIALS (doubles of scratch for dgvit_grad_sqnorm_partials)
+class dgvit_ring_view(Structure):
+    """include/dgvit_hip.h: the ring as dgvit_ring_export reads it, passed by value"""
+    _fields_ = [("obs", c_void_p), ("next_obs", c_void_p), ("next_row", c_void_p), ("small", c_void_p * SMALL_FIELDS), ("flags", c_void_p),
+                ("leaves", c_void_p), ("frame_ld", c_longlong), ("next_rows", c_longlong), ("small_cols", c_int * SMALL_FIELDS),
+                ("small_ld", c_int * SMALL_FIELDS), ("frame_u8", c_int)]
+
+
+GRAD_NORM_PARTIALS = 512  # include/dgvit_hip.h: DGVIT_GRAD_NORM_PARTIALS (doubles of scratch for dgvit_grad_sqnorm_partials)
 NUM_GLOBAL_PARAMS = 4
 PARAMS_PER_LAYER = 11
 ABI_VERSION = 7
@@ -123,6 +130,9 @@ SIGNATURES = {
     "dgvit_ring_plan_next": (_I, [_P, _P, _P, _P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_ring_store_frames_shared": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _P, _I, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_ring_next_rows": (_I, [_P, _P, _P, _LL, _LL, _P]),
+    # the ring as a file (include/dgvit_hip.h: The ring as a file)
+    "dgvit_ring_export": (_I, [dgvit_ring_view, _P, _LL, _LL, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_per_set_leaves": (_I, [_P, _LL, _LL, _LL, _P, _P]),
     "dgvit_per_tree_floats": (_LL, [_LL]),
     "dgvit_per_init": (_I, [_P, _LL, _P]),
     "dgvit_per_set_range": (_I, [_P, _LL, _LL, _LL, _P]),

@@ -340,6 +340,14 @@ extern "C" int dgvit_ring_store_frames_shared(const void* src0, int src0_u8, lon
 extern "C" int dgvit_ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, void* stream) {
   return ring_next_rows(next_row, idx, out, nsel, nrows, (hipStream_t)stream);
 }
+// the ring as a file (replay_ring.hip, replay.hip)
+extern "C" int dgvit_ring_export(dgvit_ring_view ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest,
+                                 long long a0, long long n, void* stream) {
+  return ring_export(ring, out, out_bytes, cols, nrows, oldest, a0, n, (hipStream_t)stream);
+}
+extern "C" int dgvit_per_set_leaves(float* tree, long long capacity, long long first, long long count, const float* leaves, void* stream) {
+  return per_set_leaves(tree, capacity, first, count, leaves, (hipStream_t)stream);
+}
 // prioritized replay (replay.hip)
 extern "C" long long dgvit_per_tree_floats(long long capacity) { return per_tree_floats(capacity); }
 extern "C" int dgvit_per_init(float* tree, long long capacity, void* stream) { return per_init(tree, capacity, (hipStream_t)stream); }

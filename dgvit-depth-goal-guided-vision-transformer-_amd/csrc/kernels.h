@@ -114,6 +114,10 @@ int ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, c
                              const int* moves, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
                              long long envs, long long pool, hipStream_t stream);
 int ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, hipStream_t stream);
+// the ring as a file: ages [a0, a0 + n) of every field packed into one device buffer (include/dgvit_hip.h: The ring as a file)
+int ring_export(const dgvit_ring_view& ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest, long long a0,
+                long long n, hipStream_t stream);
+int per_set_leaves(float* tree, long long capacity, long long first, long long count, const float* leaves, hipStream_t stream);
 // replay.hip: prioritized replay on a radix-64 sum / min tree in one fp32 buffer (layout and draw: include/dgvit_hip.h)
 long long per_tree_floats(long long capacity);   // -1 outside [1, 2^24]
 int per_init(float* tree, long long capacity, hipStream_t stream);

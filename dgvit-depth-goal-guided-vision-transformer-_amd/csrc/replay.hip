@@ -2,6 +2,7 @@
 // ring's slots in ONE fp32 buffer, so that a wave64 handles one sample and one wave instruction reads the 64 children of a node.
 //   per_init      : sums 0, mins +inf, max leaf 1
 //   per_set_range : leaves [first, first + count) <- the max leaf (a newly stored transition), ancestors rebuilt
+//   per_set_leaves: leaves [first, first + count) <- given values, clamped as a leaf is; ancestors rebuilt as per_set_range's
 //   per_update    : leaf[idx[j]] <- clamp((|prio[j]| + eps)^alpha, 2^-64, 2^64), ancestors rebuilt
 //   per_sample    : u[j] -> (leaf index, importance weight (p_min / leaf)^beta) by a descent from the top block
 //
@@ -82,6 +83,16 @@ __global__ void __launch_bounds__(256) per_set_leaves_kernel(float* __restrict__
   const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
   if (k >= count) return;
   const float v = tree[0];
+  tree[off0 + first + k] = v;
+  tree[off0 + pad0 + first + k] = v;
+}
+
+// leaf first + k <- leaves[k], clamped as per_max_kernel clamps (a NaN becomes the smallest leaf); its min word is its sum
+__global__ void __launch_bounds__(256) per_write_leaves_kernel(float* __restrict__ tree, long long off0, int pad0, long long first, long long count,
+                                                               const float* __restrict__ leaves) {
+  const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= count) return;
+  const float v = fminf(fmaxf(leaves[k], PER_LEAF_MIN), PER_LEAF_MAX);
   tree[off0 + first + k] = v;
   tree[off0 + pad0 + first + k] = v;
 }
@@ -231,6 +242,17 @@ int per_init(float* tree, long long capacity, hipStream_t stream) {
   return DGVIT_OK;
 }
 
+// the ancestors of leaves [first, first + count): a contiguous range of leaves has a contiguous range of ancestors at every level
+static void per_rebuild_range(float* tree, const PerTree& t, long long first, long long count, hipStream_t stream) {
+  long long lo = first, hi = first + count - 1;
+  for (int l = 1; l < t.levels; ++l) {
+    lo >>= 6;
+    hi >>= 6;
+    hipLaunchKernelGGL(per_rebuild_kernel, dim3(blocks(hi - lo + 1, 4)), dim3(256), 0, stream, tree, l, t.off[l - 1], t.pad[l - 1], t.off[l],
+                       t.pad[l], lo, hi - lo + 1, (const long long*)nullptr, 0ll);
+  }
+}
+
 int per_set_range(float* tree, long long capacity, long long first, long long count, hipStream_t stream) {
   PER_CHECK_TREE("per_set_range");
   DGVIT_CHECK_ARG(first >= 0 && count >= 1 && first < capacity && count <= capacity - first,
@@ -238,15 +260,24 @@ int per_set_range(float* tree, long long capacity, long long first, long long co
   {
     ProfileScope ps(PROF_OTHER, 0.0, stream);
     hipLaunchKernelGGL(per_set_leaves_kernel, dim3(blocks(count, 256)), dim3(256), 0, stream, tree, t.off[0], t.pad[0], first, count);
-    long long lo = first, hi = first + count - 1;
-    for (int l = 1; l < t.levels; ++l) {     // a contiguous range of leaves has a contiguous range of ancestors at every level
-      lo >>= 6;
-      hi >>= 6;
-      hipLaunchKernelGGL(per_rebuild_kernel, dim3(blocks(hi - lo + 1, 4)), dim3(256), 0, stream, tree, l, t.off[l - 1], t.pad[l - 1], t.off[l],
-                         t.pad[l], lo, hi - lo + 1, (const long long*)nullptr, 0ll);
-    }
+    per_rebuild_range(tree, t, first, count, stream);
   }
   DGVIT_CHECK_LAUNCH("per_set_range");
+  return DGVIT_OK;
+}
+
+int per_set_leaves(float* tree, long long capacity, long long first, long long count, const float* leaves, hipStream_t stream) {
+  PER_CHECK_TREE("per_set_leaves");
+  DGVIT_CHECK_ARG(leaves, "per_set_leaves: leaves must not be null");
+  DGVIT_CHECK_ARG(first >= 0 && count >= 1 && first < capacity && count <= capacity - first,
+                  "per_set_leaves: first=%lld count=%lld must be a non-empty range inside [0, capacity=%lld)", first, count, capacity);
+  DGVIT_CHECK_ARG((reinterpret_cast<uintptr_t>(leaves) & 3) == 0, "per_set_leaves: leaves must be 4-byte aligned");
+  {
+    ProfileScope ps(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(per_write_leaves_kernel, dim3(blocks(count, 256)), dim3(256), 0, stream, tree, t.off[0], t.pad[0], first, count, leaves);
+    per_rebuild_range(tree, t, first, count, stream);
+  }
+  DGVIT_CHECK_LAUNCH("per_set_leaves");
   return DGVIT_OK;
 }
 

@@ -18,6 +18,8 @@
 //                             the FIFO of the terminal pool, and the store's move list -- one wave, 64 rows a round
 //   ring_store_frames_shared: the obs rows, the moves into the pool and the pending rows of that store in one launch
 //   ring_next_rows          : out[i] = next_row[idx[i]], the index tensor of the next_obs gather over the arena
+//   ring_export             : the store path's mirror: ages [a0, a0 + n) of the ring, every field, the END bits and the
+//                             leaves packed densely, field-major, into one device buffer -- the chunk of a save_transitions file
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
 // the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
@@ -498,6 +500,73 @@ __global__ void __launch_bounds__(256) ring_next_rows_kernel(const int* __restri
   out[i] = r < 0 ? s : r;
 }
 
+// ---- the ring as a file: ages [a0, a0 + n) packed field-major into one device buffer, the chunk that leaves in one
+// device -> host copy.  Block b of the buffer starts at off[b], a multiple of 16 bytes: obs, next_obs, the five small fields, the n END
+// bytes and, with a tree, the n leaves.
+struct export_args {
+  const unsigned char* obs;       // the obs matrix; the arena of a shared ring
+  const unsigned char* next_obs;  // the next_obs matrix; the arena again
+  const int* next_row;            // null: a two-matrix ring
+  const float* small[DGVIT_SMALL_FIELDS];
+  const unsigned char* flags;     // null: episodes were never tracked
+  const float* leaves;            // null: no tree
+  long long off[DGVIT_SMALL_FIELDS + 4];
+  long long ring_bytes;           // bytes between two frame rows of the ring
+  long long dense_bytes;          // bytes of a frame row in the buffer: cols * itemsize
+  long long next_rows;            // rows of next_obs
+  int small_cols[DGVIT_SMALL_FIELDS];
+  int small_ld[DGVIT_SMALL_FIELDS];
+};
+
+// blockIdx.y is the block of the buffer, so everything that depends on it is wave-uniform.  y < 2, thread = one V (16, 4 or 1 bytes) of a
+// dense frame row: ring rows are 16-byte aligned and dense rows a multiple of sizeof(V) behind a 16-byte aligned block, so both sides of
+// the copy are aligned; the bytes are the ring's, no conversion.  next_obs of a shared ring is read at next_row[slot], at the slot's own
+// obs row where the table names no arena row.  y >= 2, thread = one float of a small field, one END byte or one leaf.  Slot of row r is
+// first + r, first < nrows and r < n <= nrows: one subtraction wraps the ring.  Every offset is 64-bit.
+template <typename V>
+__global__ void __launch_bounds__(256) ring_export_kernel(const export_args p, unsigned char* __restrict__ out, long long n, int units,
+                                                          long long nrows, long long first) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int y = (int)blockIdx.y;
+  if (y < 2) {
+    if (i >= n * units) return;
+    const long long r = i / units;
+    const long long c = i - r * units;
+    long long s = first + r;
+    if (s >= nrows) s -= nrows;
+    const unsigned char* __restrict__ src = p.obs + s * p.ring_bytes;
+    if (y == 1) {
+      long long q = s;
+      if (p.next_row) {
+        const long long t = p.next_row[s];
+        if (t >= 0 && t < p.next_rows) q = t;
+      }
+      src = p.next_obs + q * p.ring_bytes;
+    }
+    unsigned char* __restrict__ dst = out + (y == 0 ? p.off[0] : p.off[1]) + r * p.dense_bytes;
+    reinterpret_cast<V*>(dst)[c] = reinterpret_cast<const V*>(src)[c];
+    return;
+  }
+#pragma unroll
+  for (int f = 0; f < DGVIT_SMALL_FIELDS; ++f) {   // unrolled: the by-value struct is never indexed with a register
+    if (y == 2 + f) {
+      const int cols = p.small_cols[f];
+      if (i >= n * cols) return;
+      const long long r = i / cols;
+      const long long c = i - r * cols;
+      long long s = first + r;
+      if (s >= nrows) s -= nrows;
+      reinterpret_cast<float*>(out + p.off[2 + f])[i] = p.small[f][s * p.small_ld[f] + c];
+      return;
+    }
+  }
+  if (i >= n) return;
+  long long s = first + i;
+  if (s >= nrows) s -= nrows;
+  if (y == 2 + DGVIT_SMALL_FIELDS) out[p.off[2 + DGVIT_SMALL_FIELDS] + i] = p.flags ? (unsigned char)(p.flags[s] & RING_END) : (unsigned char)0;
+  else reinterpret_cast<float*>(out + p.off[3 + DGVIT_SMALL_FIELDS])[i] = p.leaves[s];
+}
+
 // both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
 template <typename T>
 int launch_gather_shift(const char* name, const T* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
@@ -789,6 +858,73 @@ int ring_next_rows(const int* next_row, const long long* idx, long long* out, lo
   DGVIT_CHECK_ARG(al4p(next_row) && al8p(idx) && al8p(out), "ring_next_rows: next_row must be 4-byte, idx and out 8-byte aligned");
   hipLaunchKernelGGL(ring_next_rows_kernel, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, stream, next_row, idx, out, nsel, nrows);
   DGVIT_CHECK_LAUNCH("ring_next_rows");
+  return DGVIT_OK;
+}
+
+int ring_export(const dgvit_ring_view& ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest, long long a0,
+                long long n, hipStream_t stream) {
+  DGVIT_CHECK_ARG(ring.obs && ring.next_obs && out, "ring_export: obs, next_obs and out must not be null");
+  DGVIT_CHECK_ARG(ring.frame_u8 == 0 || ring.frame_u8 == 1, "ring_export: frame_u8=%d must be 0 or 1", ring.frame_u8);
+  DGVIT_CHECK_ARG(nrows > 0 && n >= 1 && n <= nrows, "ring_export: n=%lld must be in [1, nrows] and nrows=%lld positive", n, nrows);
+  DGVIT_CHECK_ARG(a0 >= 0 && a0 <= nrows - n, "ring_export: ages a0=%lld .. a0 + n=%lld must lie inside the ring's [0, nrows=%lld]", a0, a0 + n,
+                  nrows);
+  DGVIT_CHECK_ARG(oldest >= 0 && oldest < nrows, "ring_export: oldest=%lld must be in [0, nrows) = [0, %lld)", oldest, nrows);
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_export: cols=%lld must be in [1, 2^25]", cols);
+  DGVIT_CHECK_ARG(ring.frame_ld % (ring.frame_u8 ? 16 : 4) == 0 && ring.frame_ld >= cols && ring.frame_ld <= (1ll << 26),
+                  "ring_export: frame_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring.frame_ld,
+                  ring.frame_u8 ? 16 : 4, cols);
+  if (ring.next_row)
+    DGVIT_CHECK_ARG(ring.next_rows >= nrows && ring.next_rows < (1ll << 31) && al4p(ring.next_row),
+                    "ring_export: next_rows=%lld of a shared ring must be in [nrows, 2^31) and next_row 4-byte aligned", ring.next_rows);
+  else
+    DGVIT_CHECK_ARG(ring.next_rows == nrows, "ring_export: next_rows=%lld must be nrows=%lld without next_row", ring.next_rows, nrows);
+  DGVIT_CHECK_ARG(al16(ring.obs) && al16(ring.next_obs), "ring_export: obs and next_obs must be 16-byte aligned");
+  DGVIT_CHECK_ARG(al16(out), "ring_export: out, the chunk, must be 16-byte aligned");
+  DGVIT_CHECK_ARG(!ring.leaves || al4p(ring.leaves), "ring_export: leaves must be 4-byte aligned");
+  export_args p{};
+  p.obs = static_cast<const unsigned char*>(ring.obs);
+  p.next_obs = static_cast<const unsigned char*>(ring.next_obs);
+  p.next_row = ring.next_row;
+  p.flags = ring.flags;
+  p.leaves = ring.leaves;
+  const long long item = ring.frame_u8 ? 1 : 4;
+  p.ring_bytes = ring.frame_ld * item;
+  p.dense_bytes = cols * item;
+  p.next_rows = ring.next_rows;
+  const auto pad16 = [](long long b) { return (b + 15) & ~15ll; };
+  long long off = 0, most = n;
+  p.off[0] = off, off = pad16(off + n * p.dense_bytes);
+  p.off[1] = off, off = pad16(off + n * p.dense_bytes);
+  for (int f = 0; f < DGVIT_SMALL_FIELDS; ++f) {
+    DGVIT_CHECK_ARG(ring.small[f], "ring_export: small[%d] must not be null", f);
+    DGVIT_CHECK_ARG(ring.small_cols[f] >= 1 && ring.small_ld[f] >= ring.small_cols[f] && ring.small_ld[f] <= (1 << 20),
+                    "ring_export: small_cols[%d]=%d must be at least 1 and small_ld[%d]=%d at least that and at most 2^20", f,
+                    ring.small_cols[f], f, ring.small_ld[f]);
+    DGVIT_CHECK_ARG(al4p(ring.small[f]), "ring_export: small[%d] must be 4-byte aligned", f);
+    p.small[f] = ring.small[f], p.small_cols[f] = ring.small_cols[f], p.small_ld[f] = ring.small_ld[f];
+    p.off[2 + f] = off, off = pad16(off + n * 4ll * ring.small_cols[f]);
+    if (n * ring.small_cols[f] > most) most = n * ring.small_cols[f];
+  }
+  p.off[2 + DGVIT_SMALL_FIELDS] = off, off = pad16(off + n);
+  p.off[3 + DGVIT_SMALL_FIELDS] = off;
+  if (ring.leaves) off = pad16(off + 4 * n);
+  DGVIT_CHECK_ARG(out_bytes >= off, "ring_export: out_bytes=%lld is less than the %lld bytes of n=%lld transitions", out_bytes, off, n);
+  const int vec = p.dense_bytes % 16 == 0 ? 16 : (p.dense_bytes % 4 == 0 ? 4 : 1);
+  const int units = (int)(p.dense_bytes / vec);
+  if (n * units > most) most = n * units;
+  const long long blocks = (most + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_export: n=%lld rows of cols=%lld are more than one launch covers", n, cols);
+  const dim3 grid((unsigned)blocks, ring.leaves ? 4 + DGVIT_SMALL_FIELDS : 3 + DGVIT_SMALL_FIELDS);
+  long long first = oldest + a0;   // oldest < nrows and a0 < nrows
+  if (first >= nrows) first -= nrows;
+  unsigned char* o = static_cast<unsigned char*>(out);
+  {
+    ProfileScope ps(PROF_OTHER, 0.0, stream);
+    if (vec == 16) hipLaunchKernelGGL(ring_export_kernel<uint4>, grid, dim3(256), 0, stream, p, o, n, units, nrows, first);
+    else if (vec == 4) hipLaunchKernelGGL(ring_export_kernel<uint32_t>, grid, dim3(256), 0, stream, p, o, n, units, nrows, first);
+    else hipLaunchKernelGGL(ring_export_kernel<unsigned char>, grid, dim3(256), 0, stream, p, o, n, units, nrows, first);
+  }
+  DGVIT_CHECK_LAUNCH("ring_export");
   return DGVIT_OK;
 }
 

@@ -18,9 +18,13 @@ stores such a step from device tensors without visiting the host.  ``shared_next
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
+import json
+import os
+import shutil
 from typing import Dict, Optional, Tuple
 
 import numpy as np
+from numpy.lib.format import open_memmap
 import torch
 
 from . import _lib
@@ -82,6 +86,49 @@ def _shared_next(shared, terminal_frames, size, num_envs):
 
 SMALL_FIELDS = ("pobs", "act", "rew", "next_pobs", "done")   # what one dgvit_ring_store_small launch stores
 
+# ---- the ring as a file
+FILE_FIELDS = FRAME_FIELDS + SMALL_FIELDS    # the field files of save_transitions and the blocks of a chunk, in this order
+FILE_FORMAT_VERSION = 1
+LOAD_CHUNK = 4096                            # transitions per host -> device copy of load_transitions
+META_KEYS = ("format_version", "stored", "size", "num_envs", "oldest_slot", "next_index", "obs_shape", "pstate_dim", "act_dim", "frame_dtype",
+             "shared_next_obs", "terminal_frames", "lost_terminal_frames", "episodes_tracked", "prioritized", "alpha", "eps", "max_leaf_bits",
+             "update_max_bits")
+
+
+def export_layout(n: int, obs_shape, pstate_dim: int, act_dim: int, frame_dtype, prioritized: bool = False):
+    """({block: (byte offset, bytes)}, bytes of the whole chunk) of n transitions as dgvit_ring_export packs them (include/dgvit_hip.h):
+    field-major, the blocks ``FILE_FIELDS`` in their order -- n dense rows each, a frame row H*W elements of ``frame_dtype``, the small
+    fields fp32 -- then ``end``, n bytes, and ``priority``, n fp32 leaves, when ``prioritized``.  Every block starts at a multiple of 16
+    bytes.  Host-only."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+        raise ValueError(f"n must be an int >= 1, got {n!r}")
+    n, item = int(n), 1 if _frame_dtype(frame_dtype) is torch.uint8 else 4
+    cols = {"obs": int(np.prod(obs_shape)) * item, "next_obs": int(np.prod(obs_shape)) * item, "pobs": 4 * int(pstate_dim),
+            "act": 4 * int(act_dim), "rew": 4, "next_pobs": 4 * int(pstate_dim), "done": 4, "end": 1}
+    if prioritized:
+        cols["priority"] = 4
+    blocks, off = {}, 0
+    for k in (*FILE_FIELDS, "end", "priority")[:len(cols)]:
+        blocks[k] = (off, n * cols[k])
+        off = _al16(off + n * cols[k])
+    return blocks, off
+
+
+def _chunk(chunk):
+    """``chunk`` after its check: host-only, runs before anything touches a device"""
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or int(chunk) < 1:
+        raise ValueError(f"chunk must be an int >= 1 (transitions per device -> host copy), got {chunk!r}")
+    return int(chunk)
+
+
+def _load_options(priorities, restore_rng):
+    """``priorities`` and ``restore_rng`` of load_transitions after their checks: host-only, runs before anything touches a device"""
+    if not isinstance(priorities, str) or priorities not in ("file", "reset"):
+        raise ValueError(f"priorities must be 'file' or 'reset', got {priorities!r}")
+    if restore_rng is not None and not isinstance(restore_rng, (bool, np.bool_)):
+        raise ValueError(f"restore_rng must be None, True or False, got {restore_rng!r}")
+    return priorities, None if restore_rng is None else bool(restore_rng)
+
 
 class DeviceReplayBuffer:
     """The replay ring in HBM.  ``frame_dtype=torch.uint8`` (keyword-only; default ``torch.float32``) stores ``obs`` and ``next_obs`` as
@@ -92,8 +139,8 @@ class DeviceReplayBuffer:
     frames, bit-equal to numpy's and CPU torch's ``codes / 255`` in fp32.  With a uint8 ring ``add`` / ``add_batch`` take each frame
     field, independently, as host floats (they travel in the one staged matrix and are quantised from it), as host uint8 (numpy or CPU
     tensor: the codes themselves, four to a float of the same matrix) or as a device tensor, fp32 or uint8.  A device tensor given to
-    ``add`` / ``add_batch`` never visits the host, whatever the ring's format and whichever field it is.  Buffers have no
-    ``state_dict``.
+    ``add`` / ``add_batch`` never visits the host, whatever the ring's format and whichever field it is.
+    ``save_transitions`` / ``load_transitions`` / ``clear`` keep the ring beyond the process.
 
     Episodes.  ``episode_flags`` is None until ``track_episodes()``, ``on_episode_end()`` or ``sample(n_step=...)`` is first
     used; from then on it is a (size,) uint8 device tensor that the store path keeps current, inside the second launch of an ``add`` or
@@ -321,6 +368,288 @@ class DeviceReplayBuffer:
         self.stored = min(self.stored + n, self.size)
         self._on_store(i, n)
 
+    # ---- the ring as a file
+    def _leaves(self):
+        """the (size,) leaves of the priority tree, a view; None: a ring without one"""
+        return None
+
+    def _layout(self, n, frame_dtype=None, leaves=None):
+        return export_layout(n, self.shapes["obs"], self.fields["pobs"], self.fields["act"], frame_dtype or self.frame_dtype,
+                             self._leaves() is not None if leaves is None else leaves)
+
+    def _export_chunk(self, a0: int, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The one dgvit_ring_export launch of a chunk: ages [a0, a0 + n) of the ring -- age a lies in slot ``(oldest + a) % size``,
+        ``oldest = next_index`` when the ring is full, else 0 -- packed as ``export_layout`` says into ``out``, a uint8 device tensor
+        (allocated when None), which is returned."""
+        if not 0 <= a0 < a0 + n <= self.stored:
+            raise ValueError(f"ages [{a0}, {a0 + n}) must be a non-empty range inside [0, stored={self.stored})")
+        nbytes = self._layout(n)[1]
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        u8, leaves = self.frame_dtype is torch.uint8, self._leaves()
+        view = _lib.dgvit_ring_view()
+        view.obs = self.store["obs"].data_ptr()
+        view.next_obs = (self.arena if self.shared_next_obs else self.store["next_obs"]).data_ptr()
+        view.next_row = self.next_row.data_ptr() if self.shared_next_obs else None
+        for j, k in enumerate(SMALL_FIELDS):
+            view.small[j], view.small_cols[j], view.small_ld[j] = self.store[k].data_ptr(), self.fields[k], self.rows[k]
+        view.flags = None if self.episode_flags is None else self.episode_flags.data_ptr()
+        view.leaves = None if leaves is None else leaves.data_ptr()
+        view.frame_ld = self.row_bytes if u8 else self.rows["obs"]
+        view.next_rows = self.arena_rows if self.shared_next_obs else self.size
+        view.frame_u8 = int(u8)
+        oldest = self.next_index if self.stored == self.size else 0
+        with torch.cuda.device(self.device):
+            rc = _lib.load().dgvit_ring_export(view, _ptr(out), out.numel(), self.fields["obs"], self.size, oldest, a0, n, _stream())
+        _lib.check(rc, "dgvit_ring_export")
+        return out
+
+    def _meta(self) -> dict:
+        """meta.json of save_transitions; the two device reads (the pool's counters, the tree's header) synchronise"""
+        u8, tree = self.frame_dtype is torch.uint8, getattr(self, "tree", None)
+        header = [None, None] if tree is None else tree[:2].view(torch.int32).tolist()
+        return {"format_version": FILE_FORMAT_VERSION, "stored": self.stored, "size": self.size, "num_envs": self.num_envs,
+                "oldest_slot": self.next_index if self.stored == self.size else 0, "next_index": self.next_index,
+                "obs_shape": list(self.shapes["obs"]), "pstate_dim": self.fields["pobs"], "act_dim": self.fields["act"],
+                "frame_dtype": "uint8" if u8 else "float32", "shared_next_obs": self.shared_next_obs, "terminal_frames": self.terminal_frames,
+                "lost_terminal_frames": self.lost_terminal_frames(), "episodes_tracked": self.episode_flags is not None,
+                "prioritized": tree is not None, "alpha": getattr(self, "alpha", None), "eps": getattr(self, "eps", None),
+                "max_leaf_bits": header[0], "update_max_bits": header[1]}
+
+    def save_transitions(self, path, *, chunk: int = 4096, overwrite: bool = False) -> None:
+        """Write the stored transitions to the directory ``path`` (cpprb's name): ``meta.json`` (``META_KEYS``) and one plain
+        ``.npy`` per field of ``FILE_FIELDS``, first axis = age, the oldest stored transition first -- age a lies in slot
+        ``(oldest + a) % size``.  Frames are the ring's own: uint8 codes from a uint8 ring, fp32 from an fp32 ring, dense (H, W) rows
+        without the ring's padding; ``next_obs`` of a shared ring is the frame ``sample`` returns for the slot.  ``end.npy`` is uint8,
+        bit 0 the slot's END flag (HEAD is derived on load; zeros when episodes were never tracked), ``priority.npy`` the fp32 leaves
+        ``(|p| + eps)^alpha`` of a prioritized ring, ``rng.npy`` the bytes of ``self.gen.get_state()``.  Every array file can be read with
+        ``numpy.load(..., mmap_mode="r")``.
+
+        ``chunk`` transitions at a time are packed by one dgvit_ring_export launch into one of two device buffers and leave in ONE copy to
+        one of two pinned buffers on a side stream, so the copy of chunk c overlaps the host's write of chunk c - 1 into the memory-mapped
+        files: host memory stays bounded by two chunks.  The host waits on events, never on the device as a whole.  The directory is
+        written under a temporary name beside ``path`` and renamed at the end.  An existing ``path`` raises FileExistsError unless
+        ``overwrite=True``; an empty ring raises RuntimeError; a call inside a stream capture raises DgvitError."""
+        chunk = _chunk(chunk)
+        if not isinstance(overwrite, (bool, np.bool_)):
+            raise ValueError(f"overwrite must be a bool, got {overwrite!r}")
+        path = os.path.abspath(os.fspath(path))
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DgvitError("save_transitions() copies to the host and waits for it, which a stream capture cannot")
+        if self.stored == 0:
+            raise RuntimeError("save_transitions() on an empty buffer: there is nothing to save")
+        if os.path.lexists(path) and not overwrite:
+            raise FileExistsError(f"{path} exists: pass overwrite=True to replace it")
+        stored, leaves = self.stored, self._leaves() is not None
+        chunk = min(chunk, stored)
+        tmp = f"{path}.tmp-{os.getpid()}"
+        if os.path.lexists(tmp):
+            shutil.rmtree(tmp)
+        os.makedirs(tmp)
+        try:
+            frame = np.uint8 if self.frame_dtype is torch.uint8 else np.float32
+            spec = {k: (frame if k in FRAME_FIELDS else np.float32, self.shapes[k]) for k in FILE_FIELDS}
+            spec["end"] = (np.uint8, ())
+            if leaves:
+                spec["priority"] = (np.float32, ())
+            files = {k: open_memmap(os.path.join(tmp, k + ".npy"), mode="w+", dtype=dt, shape=(stored, *shape)) for k, (dt, shape) in spec.items()}
+            nbytes = self._layout(chunk)[1]
+            dev = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            pin = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            cur, side = torch.cuda.current_stream(self.device), torch.cuda.Stream(self.device)
+            copied = [None, None]
+
+            def write(a0, n, p):
+                """the host's part: chunk [a0, a0 + n) out of pinned buffer p into the files, once its copy has arrived"""
+                copied[p].synchronize()
+                host, blocks = pin[p].numpy(), self._layout(n)[0]
+                for k, (dt, shape) in spec.items():
+                    off, nb = blocks[k]
+                    files[k][a0:a0 + n] = host[off:off + nb].view(dt).reshape(n, *shape)
+
+            waiting = None
+            for c, a0 in enumerate(range(0, stored, chunk)):
+                n, p = min(chunk, stored - a0), c & 1
+                if copied[p] is not None:
+                    cur.wait_event(copied[p])        # device buffer p is free once chunk c - 2 has left it
+                self._export_chunk(a0, n, out=dev[p])
+                exported = torch.cuda.Event()
+                exported.record(cur)
+                side.wait_event(exported)
+                need = self._layout(n)[1]
+                with torch.cuda.stream(side):        # pinned buffer p is free: the host wrote chunk c - 2 in the round before
+                    pin[p][:need].copy_(dev[p][:need], non_blocking=True)
+                copied[p] = torch.cuda.Event()
+                copied[p].record(side)
+                if waiting is not None:
+                    write(*waiting)
+                waiting = (a0, n, p)
+            write(*waiting)
+            for f in files.values():
+                f.flush()
+            del files
+            np.save(os.path.join(tmp, "rng.npy"), self.gen.get_state().numpy())
+            with open(os.path.join(tmp, "meta.json"), "w") as f:
+                json.dump(self._meta(), f, indent=1)
+            if os.path.lexists(path):
+                shutil.rmtree(path) if os.path.isdir(path) and not os.path.islink(path) else os.remove(path)
+            os.rename(tmp, path)
+        except BaseException:
+            shutil.rmtree(tmp, ignore_errors=True)
+            raise
+
+    def _set_leaves(self, start: int, leaves: torch.Tensor) -> None:
+        """hook: ring slots start .. (mod size) have just been loaded with these leaves of a file; a ring without a tree ignores them"""
+
+    def _restore_max_leaf(self, meta: dict) -> None:
+        """hook: the last chunk of a file with priorities is in"""
+
+    def _check_file(self, path, priorities):
+        """meta.json and the memory-mapped arrays of a save_transitions directory, checked against this ring -> (meta, arrays); ``arrays``
+        has ``priority`` only when the file's leaves are to be loaded.  Nothing is stored and no device is touched."""
+        with open(os.path.join(path, "meta.json")) as f:
+            meta = json.load(f)
+        if meta.get("format_version") != FILE_FORMAT_VERSION:
+            raise ValueError(f"{path}: format_version={meta.get('format_version')!r}, this package reads {FILE_FORMAT_VERSION}")
+        for k in META_KEYS:
+            if k not in meta:
+                raise ValueError(f"{path}: meta.json has no {k}")
+        mine = {"num_envs": self.num_envs, "obs_shape": list(self.shapes["obs"]), "pstate_dim": self.fields["pobs"], "act_dim": self.fields["act"]}
+        for k, v in mine.items():
+            if (list(meta[k]) if k == "obs_shape" else meta[k]) != v:
+                raise ValueError(f"{path}: {k}={meta[k]!r} in the file, {v!r} in this ring")
+        stored = meta["stored"]
+        if not isinstance(stored, int) or stored < 1 or stored % self.num_envs:
+            raise ValueError(f"{path}: stored={stored!r} must be a positive multiple of num_envs={self.num_envs}")
+        if meta["frame_dtype"] not in ("float32", "uint8"):
+            raise ValueError(f"{path}: frame_dtype={meta['frame_dtype']!r} must be 'float32' or 'uint8'")
+        with_leaves = (priorities == "file" and self._leaves() is not None and bool(meta["prioritized"])
+                       and os.path.exists(os.path.join(path, "priority.npy")))
+        if with_leaves and (meta["alpha"], meta["eps"]) != (self.alpha, self.eps):
+            raise ValueError(f"{path}: the leaves are (|p| + eps)^alpha with alpha={meta['alpha']!r} eps={meta['eps']!r}, this ring has "
+                             f"alpha={self.alpha!r} eps={self.eps!r}: pass priorities='reset'")
+        frame = np.dtype(meta["frame_dtype"])
+        spec = {k: (frame if k in FRAME_FIELDS else np.dtype(np.float32), self.shapes[k]) for k in FILE_FIELDS}
+        spec["end"] = (np.dtype(np.uint8), ())
+        if with_leaves:
+            spec["priority"] = (np.dtype(np.float32), ())
+        arrays = {}
+        for k, (dt, shape) in spec.items():
+            a = np.load(os.path.join(path, k + ".npy"), mmap_mode="r", allow_pickle=False)
+            if a.dtype != dt or a.shape != (stored, *shape):
+                raise ValueError(f"{path}: {k}.npy is {a.dtype} {a.shape}, expected {dt} {(stored, *shape)}")
+            arrays[k] = a
+        return meta, arrays
+
+    def load_transitions(self, path, *, priorities: str = "file", restore_rng: Optional[bool] = None) -> int:
+        """Store the transitions of a ``save_transitions`` directory, oldest first, through the ring's own store path (``_commit``) -> how
+        many were stored.  What is stored, the flags, a shared ring's bookkeeping and the refusals are therefore ``add_batch``'s and
+        ``add_vec``'s.  ``LOAD_CHUNK`` transitions at a time are packed into a pinned buffer, go to the device in ONE copy, and are handed
+        to ``_commit`` as device views of that chunk.  The episode structure is replayed: a ring with ``num_envs = E > 1`` takes one
+        ``_commit`` per vector step with the step's END bits as its ``episode_end``; a ring with E = 1 one ``_commit`` per run of slots up
+        to and including an END, followed by ``on_episode_end()``; a file without tracked episodes one ``_commit`` per chunk (per step where
+        a ring of several lanes tracks episodes itself, so that its marks are a step's).
+
+        The file's ``num_envs``, ``obs_shape``, ``pstate_dim`` and ``act_dim`` must be the ring's (ValueError naming the key, before
+        anything is stored); ``size``, ``frame_dtype``, ``shared_next_obs`` and ``terminal_frames`` may differ.  A uint8 file into an fp32
+        ring stores the correctly rounded ``codes.float() / 255``, the bits ``sample`` returns from a uint8 ring, formed on the device
+        by a lookup in the table of the 256 quotients; an fp32 file into a uint8 ring is quantised by the store path.  A ring
+        smaller than the file ends with the newest transitions.  When the ring is empty and the file's ``size`` and ``num_envs`` are the
+        ring's -- a *same-geometry* load -- ``next_index`` first moves to the file's ``oldest_slot``, so every transition returns to the
+        slot it had and ``next_index`` and ``stored`` end as they were.  ``restore_rng=None`` restores ``self.gen`` from ``rng.npy``
+        exactly then (True / False force it): the resumed run then draws the indices the saved run would have drawn.
+
+        On a prioritized ring each ``_commit`` leaves the max leaf in its slots; with ``priorities="file"`` the file's leaves are then
+        written over them (dgvit_per_set_leaves) and the max leaf is restored after the last chunk -- ``alpha`` and ``eps`` must equal
+        the file's, else ValueError.  ``priorities="reset"``, or a file without ``priority.npy``, leaves every slot at the max leaf."""
+        priorities, restore_rng = _load_options(priorities, restore_rng)
+        path = os.path.abspath(os.fspath(path))
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DgvitError("load_transitions() reads files and stages them through the host, which a stream capture cannot")
+        meta, arrays = self._check_file(path, priorities)
+        rng = np.load(os.path.join(path, "rng.npy"), allow_pickle=False)
+        stored, E, leaves = meta["stored"], self.num_envs, "priority" in arrays
+        same = self.stored == 0 and meta["size"] == self.size and meta["num_envs"] == E
+        if same:
+            self.next_index = int(meta["oldest_slot"])
+        tracked = bool(meta["episodes_tracked"])
+        if tracked:
+            self.track_episodes()
+        if self.stored and self.episode_flags is not None:      # what is there does not go on into the file: its episodes end here
+            self.on_episode_end(None if E == 1 else torch.ones(E, dtype=torch.bool, device=self.device))
+        by_step = E > 1 and self.episode_flags is not None
+        file_dtype = torch.uint8 if meta["frame_dtype"] == "uint8" else torch.float32
+        chunk = min(max(LOAD_CHUNK // E, 1) * E, self.size, stored)       # a multiple of E (E divides size and stored)
+        nbytes = self._layout(chunk, file_dtype, leaves)[1]
+        pin = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        arrived = [None, None]
+        cur = torch.cuda.current_stream(self.device)
+        if file_dtype is torch.uint8 and self.frame_dtype is torch.float32:
+            # fl(k / 255), the 256 values a uint8 ring's gather returns: looked up on the device, because a device division by a
+            # scalar is a multiplication by fl(1 / 255), which differs from the quotient in 126 of the 256 codes (replay_ring.hip)
+            table = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(self.device)
+        for c, a0 in enumerate(range(0, stored, chunk)):
+            n, p = min(chunk, stored - a0), c & 1
+            blocks, need = self._layout(n, file_dtype, leaves)
+            if arrived[p] is not None:
+                arrived[p].synchronize()             # pinned buffer p has been read: chunk c - 2 is on the device
+            host = pin[p].numpy()
+            for k, (off, nb) in blocks.items():
+                host[off:off + nb].view(arrays[k].dtype).reshape(arrays[k][a0:a0 + n].shape)[...] = arrays[k][a0:a0 + n]
+            dev[:need].copy_(pin[p][:need], non_blocking=True)      # behind the launches that read chunk c - 1 out of `dev`
+            arrived[p] = torch.cuda.Event()
+            arrived[p].record(cur)
+            views = {}
+            for k in FILE_FIELDS:
+                off, nb = blocks[k]
+                v = dev[off:off + nb]
+                if k in FRAME_FIELDS and file_dtype is torch.uint8:
+                    v = v.view(n, -1)
+                    views[k] = v if self.frame_dtype is torch.uint8 else table.index_select(0, v.reshape(-1).int()).view(n, -1)
+                else:
+                    views[k] = v.view(torch.float32).view(n, -1)
+            ends = dev[blocks["end"][0]:blocks["end"][0] + n]
+            prio = dev[blocks["priority"][0]:blocks["priority"][0] + 4 * n].view(torch.float32) if leaves else None
+
+            def commit(lo, hi, end=None):
+                start = self.next_index
+                self._commit({k: v[lo:hi] for k, v in views.items()}, hi - lo, end)
+                if leaves:
+                    self._set_leaves(start, prio[lo:hi])
+
+            if by_step:
+                for lo in range(0, n, E):
+                    commit(lo, lo + E, ends[lo:lo + E])
+            elif tracked and E == 1:
+                lo = 0
+                for e in np.flatnonzero(np.asarray(arrays["end"][a0:a0 + n]) & FLAG_END).tolist():
+                    commit(lo, e + 1)
+                    self.on_episode_end()
+                    lo = e + 1
+                if lo < n:
+                    commit(lo, n)
+            else:
+                commit(0, n)
+        for ev in arrived:
+            if ev is not None:
+                ev.synchronize()                     # the pinned buffers go out of scope
+        if leaves:
+            self._restore_max_leaf(meta)
+        if same if restore_rng is None else restore_rng:
+            self.gen.set_state(torch.from_numpy(rng))
+        return stored
+
+    def clear(self) -> None:
+        """Empty the ring without reallocating (cpprb's name): ``next_index`` and ``stored`` to 0, the episode flags to zeros (they stay
+        allocated), a shared ring's ``next_row`` to -1 and its pool's counters to 0; the frame matrices are not touched."""
+        self.next_index = self.stored = 0
+        if self.episode_flags is not None:
+            self.episode_flags.zero_()
+        if self.shared_next_obs:
+            self.next_row.fill_(-1)
+            self._pool_state.zero_()
+
     def _add(self, kw, n) -> None:
         """add / add_batch: of n > size transitions the last ``size`` are the ones that stay"""
         if self.num_envs > 1:
@@ -532,7 +861,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         buf.update_priorities(batch["indexes"], (q - y).abs().detach())
 
     ``sac_losses.critic_loss(weights=batch["weights"], done=batch["done"], ...)`` is that loss in one launch, and its ``.td`` the write-back.
-    Priorities have no ``state_dict`` and rank-based prioritization is not implemented."""
+    ``save_transitions`` writes the leaves as ``priority.npy`` and ``load_transitions`` puts them back; rank-based
+    prioritization is not implemented."""
 
     def __init__(self, size: int, obs_shape: Tuple[int, int] = (128, 160), pstate_dim: int = 2, act_dim: int = 2, device="cuda",
                  seed: Optional[int] = None, alpha: float = 0.6, eps: float = 1e-4, *, frame_dtype=torch.float32, num_envs=1,
@@ -562,6 +892,36 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             for start, count in ((i, first), (0, n - first)):
                 if count > 0:
                     _lib.check(lib.dgvit_per_set_range(_ptr(self.tree), self.size, start, count, _stream()), "dgvit_per_set_range")
+
+    def _leaves(self):
+        off = self._levels[0][0]
+        return self.tree[off:off + self.size]
+
+    def _set_leaves(self, start: int, leaves: torch.Tensor) -> None:
+        """the file's leaves over the max leaf that ``_on_store`` has just given ring slots start .. start + n - 1 (mod size):
+        dgvit_per_set_leaves, twice when the slots wrap"""
+        n = leaves.numel()
+        first = min(n, self.size - start)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            for slot, lo, count in ((start, 0, first), (0, first, n - first)):
+                if count > 0:
+                    rc = lib.dgvit_per_set_leaves(_ptr(self.tree), self.size, slot, count, leaves[lo:].data_ptr(), _stream())
+                    _lib.check(rc, "dgvit_per_set_leaves")
+
+    def _restore_max_leaf(self, meta: dict) -> None:
+        """The tree's header after a load, two words written on the device: the max leaf (word 0) is the larger of the ring's and the
+        file's -- it never falls -- and word 1, the scratch of the last update, the file's, so that a tree loaded into a fresh ring is
+        the saved one bit for bit."""
+        header = torch.tensor([meta["max_leaf_bits"], meta["update_max_bits"]], dtype=torch.int32).view(torch.float32).to(self.device)
+        self.tree[0:1] = torch.maximum(self.tree[0:1], header[0:1])
+        self.tree[1:2] = header[1:2]
+
+    def clear(self) -> None:
+        """the base's ``clear`` and the tree as a new buffer's: dgvit_per_init"""
+        super().clear()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().dgvit_per_init(_ptr(self.tree), self.size, _stream()), "dgvit_per_init")
 
     def draw(self, batch_size: int, beta: float = 0.4, stratified: bool = False,
              uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:

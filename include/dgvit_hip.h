@@ -580,6 +580,46 @@ int dgvit_per_sample(const float* tree, long long capacity, const float* uniform
                      long long* idx_out, float* weights_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The ring as a file (dgvit_amd.replay: save_transitions, load_transitions).  Transitions are numbered by AGE: age a lies
+ * in slot (oldest + a) % nrows, oldest = the next slot to be written when the ring is full and 0 before.
+ *
+ * dgvit_ring_export: the store path's mirror.  Ages [a0, a0 + n) of every field in ONE launch into ONE device buffer `out`, the chunk
+ *   that then leaves in one device -> host copy.  The buffer is field-major; block b starts at a multiple of 16 bytes:
+ *     obs, next_obs          n dense rows of cols elements in the ring's own format (frame_u8: bytes, else the fp32 bits): the row
+ *                            padding of the ring (frame_ld - cols) is not written, nothing is converted
+ *     small[0 .. 4]          n rows of small_cols[f] floats (pobs, act, rew, next_pobs, done for the package)
+ *     end                    n bytes: flags[slot] & DGVIT_RING_END, zeros when flags is NULL (HEAD is not exported: it is derived)
+ *     leaves                 n floats leaves[slot], only when leaves is not NULL (the tree's level-0 sums, tree + 64)
+ *   off_0 = 0, off_{b+1} = align16(off_b + bytes_b); out_bytes must cover the last block.  next_obs of a two-matrix ring
+ *   (next_row == NULL, next_rows == nrows) is row `slot` of its matrix; of a shared ring (obs = next_obs = the arena, next_rows the
+ *   arena's rows) it is arena row next_row[slot], or the slot's own obs row where the table names no arena row -- what
+ *   dgvit_ring_next_rows resolves.  A dense frame row is copied 16 bytes at a time when cols * itemsize is a multiple of 16, 4 bytes at
+ *   a time when it is a multiple of 4, else by bytes; every offset is 64-bit.  obs, next_obs and out 16-byte aligned, frame_ld a
+ *   multiple of 4 floats / 16 bytes, 1 <= n, 0 <= a0, a0 + n <= nrows, 0 <= oldest < nrows.
+ * dgvit_per_set_leaves: leaves [first, first + count) of the tree (inside the ring: no wrap) take leaves[k], clamped to [2^-64, 2^64]
+ *   as every leaf is (a NaN gives 2^-64), and their ancestors are rebuilt as dgvit_per_set_range rebuilds them: a tree whose stored
+ *   leaves are written back is bit-equal to the tree they were read from.  The max leaf (header word 0) is not an argument: it is one
+ *   word of `tree` that the caller writes on the device when the last range is in.
+ * Neither synchronises; both are capturable.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* obs;                           /* (nrows, frame_ld) ring matrix; the arena of a shared ring */
+  const void* next_obs;                      /* (next_rows, frame_ld); the arena again for a shared ring */
+  const int* next_row;                       /* NULL: a two-matrix ring */
+  const float* small[DGVIT_SMALL_FIELDS];    /* (nrows, small_ld[f]) fp32 */
+  const unsigned char* flags;                /* may be NULL */
+  const float* leaves;                       /* may be NULL */
+  long long frame_ld;                        /* elements between two frame rows */
+  long long next_rows;
+  int small_cols[DGVIT_SMALL_FIELDS];
+  int small_ld[DGVIT_SMALL_FIELDS];
+  int frame_u8;
+} dgvit_ring_view;
+int dgvit_ring_export(dgvit_ring_view ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest, long long a0,
+                      long long n, void* stream);
+int dgvit_per_set_leaves(float* tree, long long capacity, long long first, long long count, const float* leaves, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * the depth-frame preprocessing in front of the path -- what env_lab.py does with OpenCV on the
  * host for every camera message (listener_callback :420-434: cv2.normalize MINMAX -> uint8, add_nose :78-89 (N(0, 50) noise,
  * clip, 5x5 Gaussian blur), blurring :69-76 (11x11 blur of the centre band)) and for every step (:295-299: cv2.resize to
