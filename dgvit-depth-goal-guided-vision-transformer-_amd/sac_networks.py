@@ -3,7 +3,8 @@
 
 Constructor signatures, attribute names (``trans``, ``fc_embed``, ``fc1`` ... used by DRL.py:107-111,145-148 to pick
 optimiser sub-sets) and ``state_dict`` keys match the reference.  The encoder and every Linear run in
-libdgvit_hip.so; sampling (Normal / tanh / clamp on (B, 2) tensors) stays in PyTorch.
+libdgvit_hip.so, and so does ``sample()`` (clamp / exp / tanh / log_prob and their gradients: one launch each way,
+``functional.tanh_gaussian_sample``); only the N(0, 1) draw stays in PyTorch.
 
 ``image_size`` / ``patch_size`` are extra keyword arguments (default = the reference's hard-wired 128x160 @ 16x20).
 """

@@ -240,7 +240,13 @@ int dgvit_linear_backward(const float* dy, const float* x, const float* w, const
  *   y         : (towers, heads3, batch, n3)
  *   dy        : towers * heads3 pointers to (batch, n3) gradients of the single outputs; NULL = that output is unused: it
  *               contributes nothing and its third layer gets no gradient (like an nn.Linear outside the autograd graph)
- *   din[s]    : (batch, kx[s]) dense, NULL to skip;  dparams: like params, NULL entries skipped (written, not accumulated)
+ *   din[s]    : (batch, kx[s]) with dense rows (row stride kx[s]) whatever ldx[s] is, NULL to skip;  dparams: like params, NULL
+ *               entries skipped (written, not accumulated)
+ * Alignment: every pointer is a float pointer (4 bytes).  W2 and every W3 must be 16-byte aligned (DGVIT_ERR_ARG otherwise); the
+ * backward reads h1 and h2 in 16-byte pieces, so they must be 16-byte aligned as well.  W1, the biases, the inputs (base and ldx),
+ * dy, din, dparams and the scratch take any 4-byte alignment: a W1 that is 16-byte aligned in every tower with K0 % 4 == 0 is read
+ * in 16-byte pieces, one that is 8-byte aligned with an even K0 in 8-byte pairs, any other element by element; a dparams entry that
+ * is not 16-byte aligned (or whose size is not a multiple of 4) is summed by the scalar form of the reduction when batch > 32.
  * -------------------------------------------------------------------------------------------- */
 typedef struct dgvit_mlp_desc {
   int batch, nseg, kx[3], ldx[3];
