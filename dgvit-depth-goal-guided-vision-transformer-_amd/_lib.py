@@ -223,6 +223,7 @@ DIAG_SIGNATURES = {
     "dgvit_set_gemm_wgrad_slice_major": (None, [_I]),
     "dgvit_attention_forward_queries": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_queries": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_attention_forward_bf16_queries": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_set_gemm_bf16_mfma16": (None, [_I]),
     "dgvit_set_gemm_bf16_stamps": (None, [_P]),
     # the row kernels with row_step / nullable outputs / the queued reduction (include/dgvit_hip_diag.h)

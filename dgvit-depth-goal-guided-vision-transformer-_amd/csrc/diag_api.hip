@@ -53,6 +53,10 @@ extern "C" int dgvit_attention_backward_queries(const float* qkv, const float* o
                                                 int B, int N, int H, int dh, int nq, void* stream) {
   return attention_bwd(qkv, out, dout, lse, dqkv, B, N, H, dh, nq, (hipStream_t)stream);
 }
+extern "C" int dgvit_attention_forward_bf16_queries(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh,
+                                                    int nq, void* stream) {
+  return attention_fwd_bf16((const bf16_t*)qkv, (bf16_t*)out, lse, B, N, H, dh, nq, (hipStream_t)stream);
+}
 extern "C" void dgvit_set_gemm_bf16_group_m(int rows) { g_gemm_bf16_group_m = rows > 0 ? rows : g_gemm_bf16_group_m_default; }
 extern "C" void dgvit_set_gemm_bf16_stamps(long long* stamps) { g_gemm_bf16_stamps = stamps; }
 extern "C" void dgvit_set_gemm_bf16_l2_budget_kb(int kb) { g_gemm_bf16_l2_budget_kb = kb > 0 ? kb : 0; }

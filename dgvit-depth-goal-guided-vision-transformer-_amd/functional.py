@@ -689,6 +689,29 @@ def op_attention_bf16(qkv, heads, dim_head=64, want_lse=False):
     return (out, lse) if want_lse else out
 
 
+def op_attention_bf16_queries(qkv, heads, nq, dim_head=64, *, out, lse=None):
+    """The fused bf16 attention (N <= 288) for the first nq query tokens, as the bf16 encoder's last block calls it with nq = 1
+    (dgvit_attention_forward_bf16_queries: diagnostic library only, inside ``diagnostic_library()``).  ``out`` (B, N, heads * dim_head)
+    bf16 and ``lse`` (B, heads, N) fp32 or None are the caller's buffers, passed as they are: no copy is made, rows >= nq keep what
+    they held."""
+    lib = _lib.load()
+    if not hasattr(lib, "dgvit_attention_forward_bf16_queries"):
+        raise DgvitError("dgvit_attention_forward_bf16_queries belongs to the diagnostic library: call inside diagnostic_library()")
+    B, N, W = qkv.shape
+    if W != 3 * heads * dim_head:
+        raise DgvitError(f"qkv last dim {W} != 3*{heads}*{dim_head}")
+    for t, name, dt, shape in ((qkv, "qkv", torch.bfloat16, (B, N, W)), (out, "out", torch.bfloat16, (B, N, heads * dim_head)),
+                               (lse, "lse", torch.float32, (B, heads, N))):
+        if t is None and name == "lse":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise DgvitError(f"{name}: expected a contiguous {dt} tensor of shape {shape} on a ROCm device")
+    with torch.cuda.device(qkv.device):
+        rc = lib.dgvit_attention_forward_bf16_queries(_ptr(qkv), _ptr(out), _ptr(lse), B, N, heads, dim_head, int(nq), _stream())
+    _lib.check(rc, "dgvit_attention_forward_bf16_queries")
+    return (out, lse) if lse is not None else out
+
+
 def op_attention_bwd_bf16(qkv, out, dout, lse, heads, dim_head=64):
     lib = _lib.load()
     qkv, out, dout, lse = _dev_bf16(qkv, "qkv"), _dev_bf16(out, "out"), _dev_bf16(dout, "dout"), _dev(lse, "lse")

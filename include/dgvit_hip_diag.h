@@ -108,6 +108,10 @@ void dgvit_set_gemm_wgrad_slice_major(int on);
 int dgvit_attention_forward_queries(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, void* stream);
 int dgvit_attention_backward_queries(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N, int H,
                                      int dh, int nq, void* stream);
+/* dgvit_attention_forward_bf16 (dgvit_hip.h) for the first nq query tokens only, as the bf16 encoder's last block calls it with nq = 1:
+ * rows >= nq of out / lse are not written.  1 <= nq <= N <= 288; lse may be NULL. */
+int dgvit_attention_forward_bf16_queries(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh, int nq,
+                                         void* stream);
 /* A/B knob: which MFMA the ring GEMM issues: 1 (default) v_mfma_f32_16x16x32_bf16, 0 v_mfma_f32_32x32x16_bf16 (same cycles per
  * FLOP; the kernel runs under the chip's power limit and the 16x16 shape measured 2-3 % faster; same results up to summation order) */
 void dgvit_set_gemm_bf16_mfma16(int on);
