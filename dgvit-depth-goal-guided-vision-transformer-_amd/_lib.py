@@ -130,6 +130,11 @@ SIGNATURES = {
     "dgvit_ring_plan_next": (_I, [_P, _P, _P, _P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_ring_store_frames_shared": (_I, [_P, _I, _LL, _P, _I, _LL, _P, _P, _I, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_ring_next_rows": (_I, [_P, _P, _P, _LL, _LL, _P]),
+    # frame stacks at sample time and on the acting side (include/dgvit_hip.h: Frame stacks)
+    "dgvit_ring_stack_rows": (_I, [_P, _P, _P, _P, _LL, _P, _P, _P, _LL, _LL, _LL, _I, _I, _LL, _P]),
+    "dgvit_gather_stack_frames": (_I, [_P, _P, _P, _P, _LL, _LL, _I, _I, _LL, _LL, _LL, _LL, _P]),
+    "dgvit_gather_shift_stack_frames": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _I, _I, _ULL, _P, _P]),
+    "dgvit_frame_stack_push": (_I, [_P, _P, _LL, _P, _I, _LL, _LL, _I, _P]),
     # the ring as a file (include/dgvit_hip.h: The ring as a file)
     "dgvit_ring_export": (_I, [dgvit_ring_view, _P, _LL, _LL, _LL, _LL, _LL, _LL, _P]),
     "dgvit_per_set_leaves": (_I, [_P, _LL, _LL, _LL, _P, _P]),

@@ -340,6 +340,29 @@ extern "C" int dgvit_ring_store_frames_shared(const void* src0, int src0_u8, lon
 extern "C" int dgvit_ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, void* stream) {
   return ring_next_rows(next_row, idx, out, nsel, nrows, (hipStream_t)stream);
 }
+// frame stacks at sample time and on the acting side (replay_ring.hip)
+extern "C" int dgvit_ring_stack_rows(const long long* idx, const long long* tail, const unsigned char* flags, const float* done,
+                                     long long done_ld, const int* next_row, long long* obs_rows, long long* next_rows, long long nsel,
+                                     long long nrows, long long envs, int frames, int full, long long arena_rows, void* stream) {
+  return ring_stack_rows(idx, tail, flags, done, done_ld, next_row, obs_rows, next_rows, nsel, nrows, envs, frames, full, arena_rows,
+                         (hipStream_t)stream);
+}
+extern "C" int dgvit_gather_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, long long nsel, long long cols,
+                                         int frames, int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1,
+                                         void* stream) {
+  return gather_stack_frames(src0, src1, rows, out, nsel, cols, frames, ring_u8, ring_ld, row_floats, nrows0, nrows1, (hipStream_t)stream);
+}
+extern "C" int dgvit_gather_shift_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, int* shifts_out,
+                                               long long nsel, int H, int W, int frames, int ring_u8, long long ring_ld, long long row_floats,
+                                               long long nrows0, long long nrows1, int pad, int stream_id, unsigned long long seed,
+                                               const unsigned long long* seed_dev, void* stream) {
+  return gather_shift_stack_frames(src0, src1, rows, out, shifts_out, nsel, H, W, frames, ring_u8, ring_ld, row_floats, nrows0, nrows1, pad,
+                                   stream_id, seed, seed_dev, (hipStream_t)stream);
+}
+extern "C" int dgvit_frame_stack_push(float* stack, const float* frame, long long frame_ld, const unsigned char* reset, int reset_all,
+                                      long long envs, long long cols, int frames, void* stream) {
+  return frame_stack_push(stack, frame, frame_ld, reset, reset_all, envs, cols, frames, (hipStream_t)stream);
+}
 // the ring as a file (replay_ring.hip, replay.hip)
 extern "C" int dgvit_ring_export(dgvit_ring_view ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest,
                                  long long a0, long long n, void* stream) {

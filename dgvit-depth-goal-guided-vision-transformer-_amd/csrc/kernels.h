@@ -114,6 +114,18 @@ int ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, c
                              const int* moves, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
                              long long envs, long long pool, hipStream_t stream);
 int ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, hipStream_t stream);
+// frame stacks at sample time: the backward walk that names each sample's K frame rows, the two gathers that interleave them channel-last,
+// and the acting side's stack (include/dgvit_hip.h: Frame stacks)
+int ring_stack_rows(const long long* idx, const long long* tail, const unsigned char* flags, const float* done, long long done_ld,
+                    const int* next_row, long long* obs_rows, long long* next_rows, long long nsel, long long nrows, long long envs, int frames,
+                    int full, long long arena_rows, hipStream_t stream);
+int gather_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, long long nsel, long long cols, int frames,
+                        int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1, hipStream_t stream);
+int gather_shift_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, int* shifts_out, long long nsel, int H,
+                              int W, int frames, int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1,
+                              int pad, int stream_id, unsigned long long seed, const unsigned long long* seed_dev, hipStream_t stream);
+int frame_stack_push(float* stack, const float* frame, long long frame_ld, const unsigned char* reset, int reset_all, long long envs,
+                     long long cols, int frames, hipStream_t stream);
 // the ring as a file: ages [a0, a0 + n) of every field packed into one device buffer (include/dgvit_hip.h: The ring as a file)
 int ring_export(const dgvit_ring_view& ring, void* out, long long out_bytes, long long cols, long long nrows, long long oldest, long long a0,
                 long long n, hipStream_t stream);

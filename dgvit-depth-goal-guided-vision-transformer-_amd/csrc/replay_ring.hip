@@ -20,6 +20,12 @@
 //   ring_next_rows          : out[i] = next_row[idx[i]], the index tensor of the next_obs gather over the arena
 //   ring_export             : the store path's mirror: ages [a0, a0 + n) of the ring, every field, the END bits and the
 //                             leaves packed densely, field-major, into one device buffer -- the chunk of a save_transitions file
+//   ring_stack_rows         : frame stacks at sample time: the n-step walk backward -- for each sampled slot the rows of its
+//                             K newest frames inside its episode, one wave per sample, for obs and for next_obs
+//   gather_stack_frames     : out[i][p][c] = frame c of sample i at pixel p, the channel-last (B, H, W, K) stack, from a row table; the last
+//                             channel may come from a second matrix (next_obs); fp32 or byte ring
+//   gather_shift_stack_frames: the same with ONE random shift per sample applied to all K channels, the draw of gather_shift_frames
+//   frame_stack_push        : the acting side's stack (replay.FrameStack): every pixel's K channels move down by one, the new frame on top
 // The dequantisation is the correctly rounded DIVISION: k * (1.0f / 255.0f) alone differs from numpy's and CPU torch's uint8 -> float / 255
 // in 126 of the 256 codes (dequant_u8 below repairs it with one Newton step).  One dword (4 pixels) of a byte ring per thread, one float4 of
 // the fp32 side: 256-B and 1-KiB wave accesses.  Columns at or beyond `cols` of every row written (ring or out) are zeros, whatever the
@@ -111,6 +117,19 @@ struct row4_stride {};
 template <typename T>
 using src_stride = std::conditional_t<std::is_same_v<T, float>, row4_stride, long long>;
 
+// the (dy, dx) of sample r in [-pad, pad]^2: one Philox draw per sample and tag, shared by the single-frame and the stacked shifted gather
+__device__ __forceinline__ void shift_draw(long long r, int pad, uint32_t tag, unsigned long long seed,
+                                           const unsigned long long* __restrict__ seed_dev, int& dy, int& dx) {
+  dy = 0, dx = 0;
+  if (pad > 0) {
+    if (seed_dev) seed = *seed_dev;   // graph-capturable form, as dropout_kernel
+    const uint4 rb = drop_bits(r, seed, tag);
+    const uint32_t span = 2u * (uint32_t)pad + 1u;
+    dy = (int)__umulhi(rb.x, span) - pad;
+    dx = (int)__umulhi(rb.y, span) - pad;
+  }
+}
+
 // out[i][y][x] = fp32(src[idx[i]][clamp(y + dy_i)][clamp(x + dx_i)]): the gather with a per-sample integer shift in [-pad, pad]^2
 // (F.pad(mode="replicate", pad) then a crop at (pad + dy, pad + dx)); columns H*W .. 4 * row4 of out are written as zeros.  T = float or
 // unsigned char is the ring's element; the draw does not depend on it, so one seed gives both rings one shift table.
@@ -126,14 +145,8 @@ __global__ void __launch_bounds__(256) gather_shift_frames_kernel(const T* __res
   if (c >= row4) return;
   const long long r = blockIdx.x;
   const long long s = ring_row(idx ? idx[r] : r, nrows);
-  int dy = 0, dx = 0;
-  if (pad > 0) {
-    if (seed_dev) seed = *seed_dev;   // graph-capturable form, as dropout_kernel
-    const uint4 rb = drop_bits(r, seed, tag);
-    const uint32_t span = 2u * (uint32_t)pad + 1u;
-    dy = (int)__umulhi(rb.x, span) - pad;
-    dx = (int)__umulhi(rb.y, span) - pad;
-  }
+  int dy, dx;
+  shift_draw(r, pad, tag, seed, seed_dev, dy, dx);
   if (shifts_out && c == 0) {
     shifts_out[2 * r] = dy;
     shifts_out[2 * r + 1] = dx;
@@ -567,6 +580,182 @@ __global__ void __launch_bounds__(256) ring_export_kernel(const export_args p, u
   else reinterpret_cast<float*>(out + p.off[3 + DGVIT_SMALL_FIELDS])[i] = p.leaves[s];
 }
 
+// ---- frame stacks at sample time: the K newest frames of a slot's episode, channel-last, built from the single frames the
+// ring holds.  The n-step walk goes forward along an episode; this is the same walk backward.
+constexpr int STACK_MAX = 16;   // one lane per predecessor; a 128 x 160 stack of 16 is 1.3 MB a sample
+
+// Lane k < K of the wave learns p = pred_k = (s - k E) mod nrows, its flags and its done in one round trip; pred_k (k >= 1) is linked iff
+// k E < nrows, it lies at or behind slot 0 only in a full ring, and neither a flag nor done stops a walk behind it.  Returns d, the number
+// of consecutive linked predecessors from k = 1 (wave-uniform, 0 <= d <= K - 1).  Lanes that are not linked keep p = s, which nothing
+// selects: every p is a slot of the ring.
+__device__ __forceinline__ int stack_walk_from(long long s, int lane, int K, long long nrows, long long E, bool full,
+                                               const float* __restrict__ done, long long done_ld, const unsigned char* __restrict__ flags,
+                                               long long& p) {
+  p = s;
+  bool linked = false;
+  if (lane >= 1 && lane < K) {
+    const long long back = lane * E;   // E <= nrows < 2^56 (launcher): no overflow
+    if (back < nrows) {
+      const long long q = s - back;    // > -nrows: one addition wraps the ring
+      if (q >= 0 || full) {
+        p = q < 0 ? q + nrows : q;
+        linked = flags[p] == 0 && done[p * done_ld] == 0.f;
+      }
+    }
+  }
+  const unsigned long long stop = __ballot(lane >= 1 && !linked);   // lanes K .. 63 always stop: never empty, and bit 0 is never set
+  return __ffsll((long long)stop) - 2;
+}
+
+// One wave per sample (4 per workgroup), as nstep_walk_kernel.  obs_rows[b][c] = pred_min(K-1-c, d) of s = clamp(idx[b]); next_rows[b][c]
+// = pred^t_min(K-2-c, d_t) for c < K - 1, rows of the obs matrix, and next_rows[b][K-1] the row of t's next_obs in ITS matrix: t itself,
+// or next_row[t] of a shared ring (t where the table names no arena row, as ring_next_rows_kernel).  t = tail[b] with a second walk, or
+// t = s and d_t = d without `tail`.  No atomics: a function of the ring and idx[b].
+__global__ void __launch_bounds__(256) ring_stack_rows_kernel(const long long* __restrict__ idx, const long long* __restrict__ tail,
+                                                              const unsigned char* __restrict__ flags, const float* __restrict__ done,
+                                                              long long done_ld, const int* __restrict__ next_row,
+                                                              long long* __restrict__ obs_rows, long long* __restrict__ next_rows,
+                                                              long long nsel, long long nrows, long long E, int K, int full,
+                                                              long long arena_rows) {
+  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (w >= nsel) return;       // wave-uniform
+  const long long s = ring_row(idx[w], nrows);
+  long long p;
+  const int d = stack_walk_from(s, lane, K, nrows, E, full != 0, done, done_ld, flags, p);
+  const long long orow = __shfl(p, min(max(K - 1 - lane, 0), d), 64);
+  long long t = s, pt = p;
+  int dt = d;
+  if (tail) {                  // wave-uniform: the n-step sample's next_obs stack ends at the walk's tail
+    t = ring_row(tail[w], nrows);
+    dt = stack_walk_from(t, lane, K, nrows, E, full != 0, done, done_ld, flags, pt);
+  }
+  long long nrow = __shfl(pt, min(max(K - 2 - lane, 0), dt), 64);
+  if (lane == K - 1) {
+    nrow = t;
+    if (next_row) {
+      const long long r = next_row[t];
+      if (r >= 0 && r < arena_rows) nrow = r;
+    }
+  }
+  if (lane < K) {
+    obs_rows[w * K + lane] = orow;
+    next_rows[w * K + lane] = nrow;
+  }
+}
+
+// out[r][p][c] = fp32(src_c[rows[r][c]][p]), src_c = src1 for c == K - 1 and src0 before: the (H W, K) channel-last stack of sample r.
+// blockIdx.x is the sample, so its K rows are wave-uniform (scalar loads); thread = one group of 4 pixels: ONE float4 (fp32 ring) or ONE
+// dword (byte ring) of each of the K source frames, then the group's 4 K contiguous output floats as K float4s -- K is a template
+// argument so that the transposition is register renaming.  The 256 groups of a workgroup are 1024 K contiguous output floats, so the
+// float4s go through LDS (4 K KiB) and leave in output order: store j of the workgroup is 256 consecutive float4s, 4 KiB, where a
+// thread storing its own K float4s would stride 16 K bytes (both forms were measured: DESIGN 3.43).  Pixels at or beyond
+// `cols` are zeros, whatever the ring holds there, and so is every float4 of a group at or beyond `groups` (a row_floats longer than
+// al4(cols K): that LDS was never written and is not read); float4s at or beyond out4 = row_floats / 4 belong to the next sample and
+// are not written.  The grid covers out4, not groups: a group whose float4s all lie beyond out4 has nothing to store.  Every row is
+// clamped to its matrix.
+template <typename T, int K>
+__global__ void __launch_bounds__(256) gather_stack_frames_kernel(const T* __restrict__ src0, const T* __restrict__ src1,
+                                                                  const long long* __restrict__ rows, float* __restrict__ out, int groups,
+                                                                  int cols, long long ld, int out4, long long nrows0, long long nrows1) {
+  __shared__ float4 stage[256 * K];
+  const int g = (int)blockIdx.y * 256 + (int)threadIdx.x;
+  const long long r = blockIdx.x;
+  if (g < groups) {
+    const int p0 = 4 * g;
+    float v[K][4];
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      const long long s = ring_row(rows[r * K + c], c == K - 1 ? nrows1 : nrows0);
+      const T* __restrict__ frame = (c == K - 1 ? src1 : src0) + s * ld + p0;
+      if constexpr (std::is_same_v<T, float>) {
+        const float4 t = *reinterpret_cast<const float4*>(frame);
+        v[c][0] = t.x, v[c][1] = t.y, v[c][2] = t.z, v[c][3] = t.w;
+      } else {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(frame);
+        v[c][0] = dequant_u8(w & 255u), v[c][1] = dequant_u8((w >> 8) & 255u), v[c][2] = dequant_u8((w >> 16) & 255u),
+        v[c][3] = dequant_u8(w >> 24);
+      }
+#pragma unroll
+      for (int e = 1; e < 4; ++e)   // p0 < cols: element 0 is always a pixel
+        if (p0 + e >= cols) v[c][e] = 0.f;
+    }
+    float4* __restrict__ mine = stage + (int)threadIdx.x * K;
+#pragma unroll
+    for (int j = 0; j < K; ++j)     // element q = 4 j + t of the group is pixel q / K, channel q % K
+      mine[j] = make_float4(v[(4 * j) % K][(4 * j) / K], v[(4 * j + 1) % K][(4 * j + 1) / K], v[(4 * j + 2) % K][(4 * j + 2) / K],
+                            v[(4 * j + 3) % K][(4 * j + 3) / K]);
+  }
+  __syncthreads();                  // every thread of the workgroup arrives: nobody has returned
+  const int base = (int)blockIdx.y * 256 * K;   // < out4 + 4096 <= 2^25 + 2^12
+  float4* __restrict__ o = reinterpret_cast<float4*>(out) + r * out4 + base;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int i = j * 256 + (int)threadIdx.x;   // float4 i of the workgroup was formed by its thread i / K
+    if (base + i < out4) o[i] = (int)blockIdx.y * 256 + i / K < groups ? stage[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// The stacked gather with the random shift: gather_shift_frames_kernel's launch shape, draw (shift_draw: the same r, tag and seed, so the
+// shift table is the unstacked call's) and clamps, ONE (dy, dx) per sample for all K channels.  Thread = one float4 of the output row;
+// its 4 elements advance channel first, then x, then y, and each reads its own frame's row from the table (K <= 16 rows, cached).
+template <typename T>
+__global__ void __launch_bounds__(256) gather_shift_stack_kernel(const T* __restrict__ src0, const T* __restrict__ src1,
+                                                                 const long long* __restrict__ rows, float* __restrict__ out,
+                                                                 int* __restrict__ shifts_out, int out4, long long ld, long long nrows0,
+                                                                 long long nrows1, int H, int W, int K, int pad, uint32_t tag,
+                                                                 unsigned long long seed, const unsigned long long* __restrict__ seed_dev) {
+  const int c4 = (int)blockIdx.y * 256 + (int)threadIdx.x;
+  if (c4 >= out4) return;
+  const long long r = blockIdx.x;
+  int dy, dx;
+  shift_draw(r, pad, tag, seed, seed_dev, dy, dx);
+  if (shifts_out && c4 == 0) {
+    shifts_out[2 * r] = dy;
+    shifts_out[2 * r + 1] = dx;
+  }
+  const unsigned q0 = 4u * (unsigned)c4, px = q0 / (unsigned)K;   // H * W * K <= 2^27 (launcher)
+  int ch = (int)(q0 - px * (unsigned)K), y = (int)(px / (unsigned)W), x = (int)(px - (unsigned)y * (unsigned)W);
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int sy = min(max(y + dy, 0), H - 1), sx = min(max(x + dx, 0), W - 1);
+    const bool last = ch == K - 1;
+    const long long s = ring_row(rows[r * K + ch], last ? nrows1 : nrows0);
+    const T* __restrict__ frame = (last ? src1 : src0) + s * ld;
+    // the source pixel is always inside its frame (clamped), so it is loaded unconditionally; y >= H are the padding columns
+    if constexpr (std::is_same_v<T, float>) {
+      const float t = frame[(long long)sy * W + sx];
+      v[e] = y < H ? t : 0.f;
+    } else {
+      const uint32_t t = frame[sy * W + sx];
+      v[e] = y < H ? dequant_u8(t) : 0.f;
+    }
+    if (++ch == K) {
+      ch = 0;
+      if (++x == W) { x = 0; ++y; }
+    }
+  }
+  reinterpret_cast<float4*>(out)[r * out4 + c4] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// The acting side (replay.FrameStack): stack is (E, cols, K) fp32, channel K - 1 the newest.  Thread = one pixel of one environment: it
+// alone reads and writes that pixel's K channels, in ascending order, so the update in place is safe.  An environment with reset[e] != 0
+// (or every one, reset_all) has all K channels filled with the new frame, Gym's FrameStack at reset.
+__global__ void __launch_bounds__(256) frame_stack_push_kernel(float* __restrict__ stack, const float* __restrict__ frame, long long frame_ld,
+                                                               const unsigned char* __restrict__ reset, int reset_all, long long total,
+                                                               int cols, int K) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long long e = i / cols;
+  const int p = (int)(i - e * cols);
+  const float v = frame[e * frame_ld + p];
+  const bool fill = reset_all || (reset && reset[e] != 0);
+  float* px = stack + i * K;      // not __restrict__-qualified reads: channel c + 1 is read before channel c is written
+  for (int c = 0; c + 1 < K; ++c) px[c] = fill ? v : px[c + 1];
+  px[K - 1] = v;
+}
+
 // both shifted gathers: `name` is the entry point's, `ld` the source's row stride in elements (an fp32 ring's is row_floats)
 template <typename T>
 int launch_gather_shift(const char* name, const T* src, const long long* idx, float* out, int* shifts_out, long long nsel, int H, int W,
@@ -934,4 +1123,123 @@ int nstep_walk_strided(const float* rew, long long rew_ld, const float* done, lo
                        long long* tail_out, hipStream_t stream) {
   return launch_nstep_walk("nstep_walk_strided", rew, rew_ld, done, done_ld, flags, next_small, small_ld, idx, nsel, nrows, &stride, n, gamma,
                            ret_out, done_out, discount_out, next_small_out, steps_out, tail_out, stream);
+}
+
+namespace {
+
+// the row table, the two sources and the output of both stacked gathers: what they ask alike -> cols * frames in *out_cols
+int check_stack(const char* name, const void* src0, const void* src1, const long long* rows, const float* out, long long nsel, long long cols,
+                int frames, int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1) {
+  DGVIT_CHECK_ARG(src0 && src1 && rows && out, "%s: src0, src1, rows and out must not be null", name);
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 24), "%s: nsel=%lld must be in [1, 2^24)", name, nsel);   // one workgroup column per sample
+  DGVIT_CHECK_ARG(nrows0 > 0 && nrows1 > 0, "%s: nrows0=%lld and nrows1=%lld must be positive", name, nrows0, nrows1);
+  DGVIT_CHECK_ARG(frames >= 1 && frames <= STACK_MAX, "%s: frames=%d must be in [1, %d]", name, frames, STACK_MAX);
+  DGVIT_CHECK_ARG(ring_u8 == 0 || ring_u8 == 1, "%s: ring_u8=%d must be 0 or 1", name, ring_u8);
+  DGVIT_CHECK_ARG(cols > 0 && cols * frames <= (1ll << 27), "%s: cols=%lld must be positive and cols * frames=%lld at most 2^27", name, cols,
+                  cols * frames);   // 32-bit element indices inside a row
+  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
+                  "%s: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", name, ring_ld, ring_u8 ? 16 : 4, cols);
+  DGVIT_CHECK_ARG(row_floats % 4 == 0 && row_floats >= cols * frames && row_floats <= (1ll << 27) + 4,
+                  "%s: row_floats=%lld must be a multiple of 4 and at least cols * frames=%lld", name, row_floats, cols * frames);
+  DGVIT_CHECK_ARG(al16(src0) && al16(src1) && al16(out) && al8p(rows), "%s: src0, src1 and out must be 16-byte aligned, rows 8-byte aligned",
+                  name);
+  return DGVIT_OK;
+}
+
+template <typename T, int K>
+void launch_gather_stack_k(const void* src0, const void* src1, const long long* rows, float* out, long long nsel, int groups, int cols,
+                           long long ld, int out4, long long nrows0, long long nrows1, hipStream_t stream) {
+  hipLaunchKernelGGL((gather_stack_frames_kernel<T, K>), dim3((unsigned)nsel, (unsigned)((out4 + 256 * K - 1) / (256 * K))), dim3(256), 0,
+                     stream, static_cast<const T*>(src0), static_cast<const T*>(src1), rows, out, groups, cols, ld, out4, nrows0, nrows1);
+}
+
+template <typename T>
+void launch_gather_stack(int frames, const void* src0, const void* src1, const long long* rows, float* out, long long nsel, int groups,
+                         int cols, long long ld, int out4, long long nrows0, long long nrows1, hipStream_t stream) {
+#define DGVIT_STACK_CASE(K) \
+  case K: return launch_gather_stack_k<T, K>(src0, src1, rows, out, nsel, groups, cols, ld, out4, nrows0, nrows1, stream)
+  switch (frames) {
+    DGVIT_STACK_CASE(1); DGVIT_STACK_CASE(2); DGVIT_STACK_CASE(3); DGVIT_STACK_CASE(4); DGVIT_STACK_CASE(5); DGVIT_STACK_CASE(6);
+    DGVIT_STACK_CASE(7); DGVIT_STACK_CASE(8); DGVIT_STACK_CASE(9); DGVIT_STACK_CASE(10); DGVIT_STACK_CASE(11); DGVIT_STACK_CASE(12);
+    DGVIT_STACK_CASE(13); DGVIT_STACK_CASE(14); DGVIT_STACK_CASE(15); DGVIT_STACK_CASE(16);
+  }
+#undef DGVIT_STACK_CASE
+}
+
+}  // namespace
+
+int ring_stack_rows(const long long* idx, const long long* tail, const unsigned char* flags, const float* done, long long done_ld,
+                    const int* next_row, long long* obs_rows, long long* next_rows, long long nsel, long long nrows, long long envs, int frames,
+                    int full, long long arena_rows, hipStream_t stream) {
+  DGVIT_CHECK_ARG(idx && flags && done && obs_rows && next_rows, "ring_stack_rows: idx, flags, done, obs_rows and next_rows must not be null");
+  DGVIT_CHECK_ARG(nsel > 0 && nsel < (1ll << 31), "ring_stack_rows: nsel=%lld must be in [1, 2^31)", nsel);
+  DGVIT_CHECK_ARG(nrows > 0 && nrows < (1ll << 56), "ring_stack_rows: nrows=%lld must be in [1, 2^56)", nrows);   // lane * envs cannot overflow
+  DGVIT_CHECK_ARG(envs >= 1 && envs <= nrows && nrows % envs == 0, "ring_stack_rows: envs=%lld must be in [1, nrows] and divide nrows=%lld", envs,
+                  nrows);
+  DGVIT_CHECK_ARG(frames >= 1 && frames <= STACK_MAX, "ring_stack_rows: frames=%d must be in [1, %d]", frames, STACK_MAX);
+  DGVIT_CHECK_ARG(full == 0 || full == 1, "ring_stack_rows: full=%d must be 0 or 1", full);
+  DGVIT_CHECK_ARG(done_ld > 0, "ring_stack_rows: done_ld=%lld must be positive", done_ld);
+  DGVIT_CHECK_ARG(next_row ? arena_rows >= nrows && arena_rows < (1ll << 31) : arena_rows == nrows,
+                  "ring_stack_rows: arena_rows=%lld must be in [nrows, 2^31) with next_row and nrows=%lld without", arena_rows, nrows);
+  DGVIT_CHECK_ARG(al8p(idx) && al8p(tail) && al8p(obs_rows) && al8p(next_rows) && al4p(done) && al4p(next_row),
+                  "ring_stack_rows: idx, tail, obs_rows and next_rows must be 8-byte aligned, done and next_row 4-byte aligned");
+  hipLaunchKernelGGL(ring_stack_rows_kernel, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, idx, tail, flags, done, done_ld, next_row,
+                     obs_rows, next_rows, nsel, nrows, envs, frames, full, arena_rows);
+  DGVIT_CHECK_LAUNCH("ring_stack_rows");
+  return DGVIT_OK;
+}
+
+int gather_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, long long nsel, long long cols, int frames,
+                        int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1, hipStream_t stream) {
+  if (const int rc = check_stack("gather_stack_frames", src0, src1, rows, out, nsel, cols, frames, ring_u8, ring_ld, row_floats, nrows0, nrows1))
+    return rc;
+  const int groups = (int)((cols + 3) / 4), out4 = (int)(row_floats / 4);
+  if (ring_u8)
+    launch_gather_stack<unsigned char>(frames, src0, src1, rows, out, nsel, groups, (int)cols, ring_ld, out4, nrows0, nrows1, stream);
+  else
+    launch_gather_stack<float>(frames, src0, src1, rows, out, nsel, groups, (int)cols, ring_ld, out4, nrows0, nrows1, stream);
+  DGVIT_CHECK_LAUNCH("gather_stack_frames");
+  return DGVIT_OK;
+}
+
+int gather_shift_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, int* shifts_out, long long nsel, int H,
+                              int W, int frames, int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1,
+                              int pad, int stream_id, unsigned long long seed, const unsigned long long* seed_dev, hipStream_t stream) {
+  const char* name = "gather_shift_stack_frames";
+  DGVIT_CHECK_ARG(H > 0 && W > 0, "%s: frame H=%d W=%d must be positive", name, H, W);
+  const long long cols = (long long)H * W;
+  if (const int rc = check_stack(name, src0, src1, rows, out, nsel, cols, frames, ring_u8, ring_ld, row_floats, nrows0, nrows1)) return rc;
+  DGVIT_CHECK_ARG(pad >= 0 && pad < H && pad < W, "%s: pad=%d must be in [0, min(H, W)) = [0, %d)", name, pad, H < W ? H : W);
+  DGVIT_CHECK_ARG(stream_id >= 0 && stream_id < DGVIT_SHIFT_STREAMS, "%s: stream_id=%d must be in [0, %d)", name, stream_id, DGVIT_SHIFT_STREAMS);
+  DGVIT_CHECK_ARG(al4p(shifts_out) && al8p(seed_dev), "%s: shifts_out must be 4-byte and seed_dev 8-byte aligned", name);
+  const int out4 = (int)(row_floats / 4);
+  const dim3 grid((unsigned)nsel, (unsigned)((out4 + 255) / 256));
+  if (ring_u8)
+    hipLaunchKernelGGL(gather_shift_stack_kernel<unsigned char>, grid, dim3(256), 0, stream, static_cast<const unsigned char*>(src0),
+                       static_cast<const unsigned char*>(src1), rows, out, shifts_out, out4, ring_ld, nrows0, nrows1, H, W, frames, pad,
+                       shift_tag(stream_id), seed, seed_dev);
+  else
+    hipLaunchKernelGGL(gather_shift_stack_kernel<float>, grid, dim3(256), 0, stream, static_cast<const float*>(src0),
+                       static_cast<const float*>(src1), rows, out, shifts_out, out4, ring_ld, nrows0, nrows1, H, W, frames, pad,
+                       shift_tag(stream_id), seed, seed_dev);
+  DGVIT_CHECK_LAUNCH(name);
+  return DGVIT_OK;
+}
+
+int frame_stack_push(float* stack, const float* frame, long long frame_ld, const unsigned char* reset, int reset_all, long long envs,
+                     long long cols, int frames, hipStream_t stream) {
+  DGVIT_CHECK_ARG(stack && frame, "frame_stack_push: stack and frame must not be null");
+  DGVIT_CHECK_ARG(envs >= 1 && envs < (1ll << 24), "frame_stack_push: envs=%lld must be in [1, 2^24)", envs);
+  DGVIT_CHECK_ARG(frames >= 1 && frames <= STACK_MAX, "frame_stack_push: frames=%d must be in [1, %d]", frames, STACK_MAX);
+  DGVIT_CHECK_ARG(cols > 0 && cols * frames <= (1ll << 27), "frame_stack_push: cols=%lld must be positive and cols * frames=%lld at most 2^27",
+                  cols, cols * frames);
+  DGVIT_CHECK_ARG(frame_ld >= cols, "frame_stack_push: frame_ld=%lld must be at least cols=%lld", frame_ld, cols);
+  DGVIT_CHECK_ARG(reset_all == 0 || reset_all == 1, "frame_stack_push: reset_all=%d must be 0 or 1", reset_all);
+  DGVIT_CHECK_ARG(al4p(stack) && al4p(frame), "frame_stack_push: stack and frame must be 4-byte aligned");
+  const long long total = envs * cols, blocks = (total + 255) / 256;
+  DGVIT_CHECK_ARG(blocks < (1ll << 31), "frame_stack_push: envs=%lld frames of cols=%lld are more than one launch covers", envs, cols);
+  hipLaunchKernelGGL(frame_stack_push_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, stack, frame, frame_ld, reset, reset_all, total,
+                     (int)cols, frames);
+  DGVIT_CHECK_LAUNCH("frame_stack_push");
+  return DGVIT_OK;
 }

@@ -13,10 +13,13 @@ Differences from the reference, on purpose:
     configuration refuses p > 0); the masks come from the forward's one Philox seed and are regenerated in the backward (nothing
     is stored; include/dgvit_hip.h: dgvit_got_forward_v2).  ``pool`` 'cls' and 'mean' both work;
   * ``heads == 1 and dim_head == dim`` gives the reference's projection-less attention (``to_out = nn.Identity()``) on the fp32 path;
-  * ``RMSNorm`` also works stand-alone (``unit_offset`` included).
+  * ``RMSNorm`` also works stand-alone (``unit_offset`` included);
+  * ``frame_channels=K`` (keyword-only, default 1) takes channel-last frame stacks ``(B, H, W, K)`` -- what
+    ``replay.sample(frame_stack=K)`` and ``replay.FrameStack`` return.  ``channels`` stays accepted and ignored.
 """
 import math
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -94,6 +97,13 @@ class Transformer(_Holder):
             for _ in range(depth)])
 
 
+def _frame_channels(k):
+    """``frame_channels`` after its check: host-only, runs before anything touches a device"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 16:
+        raise ValueError(f"frame_channels must be an int in [1, 16] (the frames of a channel-last (B, H, W, K) stack), got {k!r}")
+    return int(k)
+
+
 def _weights_loaded(module, incompatible_keys):
     """load_state_dict post-hook (a module-level function: the module must stay picklable, attention_imitating.py:199)."""
     module._bf16_weights.invalidate()
@@ -103,8 +113,9 @@ class GoT(nn.Module):
     """Goal-guided ViT encoder: (B, H, W) depth frames + (B, dim) goal embedding -> (B, dim) features."""
 
     def __init__(self, *, image_size, patch_size, num_classes, dim, depth, heads, mlp_dim, pool='cls', channels=3,
-                 dim_head=64, dropout=0., emb_dropout=0.1):
+                 dim_head=64, dropout=0., emb_dropout=0.1, frame_channels=1):
         super().__init__()
+        self.frame_channels = K = _frame_channels(frame_channels)
         image_height, image_width = pair(image_size)
         patch_height, patch_width = pair(patch_size)
         self.layer_norm = RMSNorm(dim)
@@ -115,9 +126,12 @@ class GoT(nn.Module):
             raise ValueError(f"transformer dropout={dropout} must be in [0, 1): p = 1 drops every branch output and attention "
                              "probability (keep = 0 has no 1/keep scale)")
         num_patches = (image_height // patch_height) * (image_width // patch_width)
-        # `channels` is accepted and ignored exactly like the reference (frames are single-channel, 3-D input)
+        # `channels` is accepted and ignored exactly like the reference (frames are single-channel, 3-D input).  frame_channels = K > 1:
+        # a contiguous (B, H, W, K) stack viewed as (B, H, W K) with patches of (ph, pw K) has exactly the rows of einops'
+        # 'b (h p1) (w p2) c -> b (h w) (p1 p2 c)' -- element px K + c of a window row is pixel (py, px, c) -- so the encoder below is
+        # the single-channel one of that wider image, kernel for kernel; the Linear's columns are ordered (p1, p2, c)
         self.to_patch_embedding = nn.Sequential(Patchify(patch_height, patch_width),
-                                                nn.Linear(patch_height * patch_width, dim))
+                                                nn.Linear(patch_height * patch_width * K, dim))
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches + 1, dim))
         self.cls_token = nn.Parameter(torch.randn(1, 1, dim))   # unused, kept for checkpoint compatibility
         self.dropout = nn.Dropout(emb_dropout)
@@ -125,7 +139,8 @@ class GoT(nn.Module):
         self.pool = pool
         self.to_latent = nn.Identity()
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, num_classes))  # unused, kept for checkpoints
-        self._cfg = (image_height, image_width, patch_height, patch_width, dim, depth, heads, dim_head, mlp_dim,
+        self._frame_shape = (image_height, image_width)
+        self._cfg = (image_height, image_width * K, patch_height, patch_width * K, dim, depth, heads, dim_head, mlp_dim,
                      1 if pool == 'mean' else 0, 0)       # last entry: schedule flags (set_schedule)
         self.compute_dtype = torch.float32
         self._long_sequence_bf16 = False   # set_schedule(long_sequence_bf16=True): the long-sequence request covers bf16 too
@@ -248,7 +263,21 @@ class GoT(nn.Module):
                 seed = self.draw_dropout_seed()
         return keep, seed, lkeep
 
+    def _frames(self, img):
+        """``img`` as the fused encoder takes it: unchanged for single frames; a contiguous channel-last (B, H, W, K) stack as its
+        (B, H, W K) view, through which autograd returns the frame gradient in the stack's own shape"""
+        K = getattr(self, "frame_channels", 1)
+        if K == 1:
+            return img
+        H, W = self._frame_shape
+        if not torch.is_tensor(img) or img.dim() != 4 or tuple(img.shape[1:]) != (H, W, K) or not img.is_contiguous():
+            got = f"{tuple(img.shape)}{'' if img.is_contiguous() else ', not contiguous'}" if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f"img must be a contiguous channel-last (B, H, W, K) = (B, {H}, {W}, {K}) stack of frame_channels={K} frames, "
+                             f"channel K - 1 the newest (a channel-first batch takes permute(0, 2, 3, 1).contiguous() first), got {got}")
+        return img.view(img.shape[0], H, W * K)
+
     def forward(self, img, goal):
+        img = self._frames(img)
         keep, seed, lkeep = self._dropout_args(img)
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:
@@ -264,6 +293,7 @@ class GoT(nn.Module):
         as ``forward`` draws it).  The call always runs the GEMM schedule (never the small-batch block path) and, for rows='all', the
         dense last block.  In the bf16 configuration the probabilities come from the bf16 q / k the attention reads (fp32 softmax)."""
         r = F_.maps_rows(rows)     # (ValueError before anything is drawn)
+        img = self._frames(img)
         keep, seed, lkeep = self._dropout_args(img)
         params = self.param_table()
         if self.compute_dtype == torch.bfloat16:

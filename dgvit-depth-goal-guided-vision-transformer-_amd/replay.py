@@ -15,6 +15,8 @@ to call.  What a walk may not cross is kept in ``episode_flags``, one byte per s
 parallel environments, a vector step in E consecutive slots, and an environment's steps lie E slots apart: ``add_vec``
 stores such a step from device tensors without visiting the host.  ``shared_next_obs=True`` stores each frame once: a transition's
 ``next_obs`` is its successor's ``obs`` row, and only the frames without a successor slot are kept apart.
+``sample(..., frame_stack=K)`` returns channel-last stacks of the last K frames of each slot's episode, built at sample time by the same
+walk run backward, and ``FrameStack`` keeps that stack on the acting side: the ring never stores a frame twice.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -60,6 +62,18 @@ def _n_step(n):
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= NSTEP_MAX:
         raise ValueError(f"n_step must be None or an int in [1, {NSTEP_MAX}], got {n!r}")
     return int(n)
+
+
+STACK_MAX = 16              # one lane of a wave per predecessor (csrc/replay_ring.hip: STACK_MAX)
+
+
+def _frame_stack(k, what="frame_stack"):
+    """``frame_stack`` (None: single frames) or ``frames`` after its check: host-only, runs before anything touches a device"""
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= STACK_MAX:
+        raise ValueError(f"{what} must be {'None or ' if what == 'frame_stack' else ''}an int in [1, {STACK_MAX}], got {k!r}")
+    return int(k)
 
 
 def _num_envs(num_envs, size):
@@ -734,7 +748,8 @@ class DeviceReplayBuffer:
         return torch.randint(0, self.stored, (batch_size,), device=self.device, dtype=torch.int64, generator=self.gen)
 
     def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None, random_shift: int = 0,
-               return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99) -> Dict[str, torch.Tensor]:
+               return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
+               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Uniform sample with replacement -> dict of DEVICE tensors shaped like the reference's batch
         (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip.
 
@@ -759,10 +774,28 @@ class DeviceReplayBuffer:
 
         On a ``shared_next_obs=True`` ring ``next_obs`` comes out of the arena with the same gather, at the rows ``next_row`` names for
         the sampled slots (the walk's last ones for ``n_step``): one small launch more, dgvit_ring_next_rows, and nothing else changes --
-        a replayed graph follows later ``add()``s because the table lives on the device."""
-        n_step, gamma = _n_step(n_step), _unit("gamma", gamma)
+        a replayed graph follows later ``add()``s because the table lives on the device.
+
+        ``frame_stack=K`` (an int in [1, 16]) returns ``obs`` and ``next_obs`` as ``(B, H, W, K)`` fp32, contiguous and
+        channel-last, channel K - 1 the newest frame: the sampled slot's frame and the K - 1 frames before it in ITS episode and lane,
+        found by the n-step walk run backward -- predecessor ``(s - k E) % size`` counts while its flags and ``done`` are zero and, in a
+        ring that is not full yet, while it does not lie before slot 0.  Frames from before the episode's first stored slot repeat that
+        first frame, as Gym's ``FrameStack`` does at reset.  The ``next_obs`` stack is the ``obs`` stack moved on by one: channel K - 1
+        is the transition's ``next_obs`` (the n-step tail's with ``n_step``, from whose slot the walk back then starts), the channels
+        below are ``obs`` frames.  ``K = 1`` equals the plain sample's ``unsqueeze(-1)``; every other key is unchanged.  ``random_shift``
+        draws ONE (dy, dx) per sample and field for all K channels, the very draw of the unstacked call: equal seeds give equal
+        ``obs_shift`` / ``next_obs_shift``.  Three launches in the place of the two frame gathers: dgvit_ring_stack_rows, which names
+        every sample's 2 K rows, and one dgvit_gather_stack_frames (``_shift_`` with ``random_shift``) per field; the uint8 ring,
+        ``num_envs``, ``shared_next_obs``, prioritization, ``n_step`` and capture compose.  Like ``n_step`` the eager call starts
+        ``track_episodes()``, and inside a capture the flags must exist.  A replayed graph follows later ``add()``s through the flags
+        and ``next_row``, but "the ring is full" is passed by value and frozen: a graph captured before the ring first fills keeps
+        treating the seam between slot ``size - 1`` and slot 0 as an episode start (conservative: it never reads an unwritten slot) --
+        re-capture once the ring has filled, and re-capture a full ring's graph after ``clear()``.  Known limit: the oldest slot of a
+        full ring has the HEAD slot before it, so its stack repeats its own frame although its episode may be older; those frames are
+        gone.  ``frame_stack=None`` is the path above, launch for launch."""
+        n_step, gamma, K = _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
-        if n_step is not None:
+        if n_step is not None or K is not None:
             self.track_episodes()
         lib = _lib.load()
         u8 = self.frame_dtype is torch.uint8
@@ -774,13 +807,25 @@ class DeviceReplayBuffer:
             self.shift_seed = _shift_seed(self.device)
         with torch.cuda.device(self.device):
             at = idx                             # the slots a field is gathered at: the walk's last ones for next_obs of an n-step call
+            walk = tables = None
+            if K is not None:                    # the stacks' row tables need the n-step tails: the walk goes first
+                if n_step is not None:
+                    walk = self._walk(idx, n_step, gamma)
+                tables = self._stack_rows(idx, None if walk is None else walk["tail"], K)
             for k, n in self.fields.items():
                 r = self.rows[k]
                 if n_step is not None and k in ("rew", "next_pobs", "done"):
                     if k == "rew":               # (fields are in the reference's order: obs, pobs and act are out, next_obs is to come)
-                        walk = self._walk(idx, n_step, gamma)
+                        if walk is None:
+                            walk = self._walk(idx, n_step, gamma)
                         at = walk.pop("tail")
                     out[k] = walk.pop(k)
+                    continue
+                if K is not None and k in FRAME_FIELDS:
+                    shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if pad and return_shifts else None
+                    out[k] = self._gather_stack(k, tables[k], K, pad, shifts)
+                    if shifts is not None:
+                        out[k + "_shift"] = shifts
                     continue
                 buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
                 src, nrows, rows_at = self.store.get(k), self.size, at
@@ -805,6 +850,43 @@ class DeviceReplayBuffer:
             out.update(walk)                     # discount, steps
         out["indexes"] = idx
         return out
+
+    def _stack_rows(self, idx, tail, K):
+        """the one dgvit_ring_stack_rows launch of a stacked sample: {field: (B, K) int64 rows of its K frames}; ``tail`` the n-step
+        walk's last slots or None"""
+        B = idx.numel()
+        rows = {k: torch.empty(B, K, dtype=torch.int64, device=self.device) for k in FRAME_FIELDS}
+        shared = self.shared_next_obs
+        rc = _lib.load().dgvit_ring_stack_rows(_ptr(idx), _ptr(tail), _ptr(self.episode_flags), _ptr(self.store["done"]), self.rows["done"],
+                                               _ptr(self.next_row if shared else None), _ptr(rows["obs"]), _ptr(rows["next_obs"]), B, self.size,
+                                               self.num_envs, K, int(self.stored == self.size), self.arena_rows if shared else self.size,
+                                               _stream())
+        _lib.check(rc, "dgvit_ring_stack_rows")
+        return rows
+
+    def _gather_stack(self, k, rows, K, pad, shifts):
+        """frame field k of a stacked sample, (B, H, W, K): dgvit_gather_stack_frames, or its shifted form, over the obs matrix and --
+        for the newest channel of next_obs -- the next_obs matrix or the arena"""
+        B, cols, (H, W) = rows.shape[0], self.fields[k], self.shapes[k]
+        u8 = self.frame_dtype is torch.uint8
+        src0 = src1 = self.store["obs"]
+        nrows1 = self.size
+        if k == "next_obs":
+            src1, nrows1 = (self.arena, self.arena_rows) if self.shared_next_obs else (self.store["next_obs"], self.size)
+        row, ld = _al4(cols * K), self.row_bytes if u8 else self.rows["obs"]
+        buf = torch.empty(B, row, dtype=torch.float32, device=self.device)
+        lib = _lib.load()
+        if pad:
+            seed_dev = self.shift_seed if isinstance(self.shift_seed, torch.Tensor) else None
+            rc = lib.dgvit_gather_shift_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), _ptr(shifts), B, H, W, K, int(u8), ld, row,
+                                                     self.size, nrows1, pad, int(k == "next_obs"),
+                                                     0 if seed_dev is not None else int(self.shift_seed), _ptr(seed_dev), _stream())
+            _lib.check(rc, "dgvit_gather_shift_stack_frames")
+        else:
+            rc = lib.dgvit_gather_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), B, cols, K, int(u8), ld, row, self.size, nrows1,
+                                               _stream())
+            _lib.check(rc, "dgvit_gather_stack_frames")
+        return buf[:, :cols * K].reshape(B, H, W, K).contiguous()   # a copy only where H W K is no multiple of 4: the row padding goes
 
     def _walk(self, idx, n_step, gamma):
         """the one dgvit_nstep_walk launch of an n-step sample (dgvit_nstep_walk_strided on a ring of several environments): rew, done,
@@ -949,13 +1031,15 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         return idx, weights
 
     def sample(self, batch_size: int, beta: float = 0.4, stratified: bool = False, uniforms: Optional[torch.Tensor] = None,
-               random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99) -> Dict[str, torch.Tensor]:
+               random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
+               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift``,
-        ``return_shifts``, ``n_step`` and ``gamma`` as there; the draw and the weights do not depend on them).  The base's dict plus
+        ``return_shifts``, ``n_step``, ``gamma`` and ``frame_stack`` as there; the draw and the weights do not depend on them).  The base's dict plus
         ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor, the start slots of an n-step sample."""
-        _n_step(n_step), _unit("gamma", gamma)
+        _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
         idx, weights = self.draw(batch_size, beta, stratified, uniforms)
-        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma)
+        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma,
+                             frame_stack=frame_stack)
         out["weights"] = weights
         return out
 
@@ -997,3 +1081,82 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     def max_priority(self) -> torch.Tensor:
         """the largest leaf ever written (0-d device tensor; 1 at first, never falls): what a newly stored transition gets"""
         return self.tree[0].clone()
+
+
+def _stack_args(num_envs, obs_shape, frames):
+    """``FrameStack``'s arguments after their checks -> (E, (H, W), K): host-only, runs before anything touches a device"""
+    if isinstance(num_envs, bool) or not isinstance(num_envs, (int, np.integer)) or int(num_envs) < 1:
+        raise ValueError(f"num_envs must be an int >= 1, got {num_envs!r}")
+    shape = tuple(obs_shape) if isinstance(obs_shape, (tuple, list)) else ()
+    if len(shape) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in shape):
+        raise ValueError(f"obs_shape must be (H, W), two ints >= 1, got {obs_shape!r}")
+    return int(num_envs), (int(shape[0]), int(shape[1])), _frame_stack(frames, "frames")
+
+
+class FrameStack:
+    """The acting side of ``sample(frame_stack=K)``: the last K frames of each of E environments as one live
+    ``(E, H, W, K)`` fp32 device tensor, channel-last with channel K - 1 the newest -- what ``choose_action`` of a
+    ``frame_channels=K`` network takes.
+
+        fs = FrameStack(num_envs=E, obs_shape=(H, W), frames=K, device="cuda")
+        stack = fs.push(frame, reset=None)
+
+    ``push`` moves every environment's channels down by one and puts the new frame -- ``(E, H, W)``, or ``(H, W)`` when E == 1; an fp32
+    tensor on the stack's device, or any host array or CPU tensor, which is copied over -- into channel K - 1.  Environments with ``reset``
+    set have all K channels filled with the frame, as Gym's ``FrameStack`` does at reset: ``reset`` is None, ``True`` (everyone) or a bool
+    mask ``(E,)`` on the host or the device; the first ``push`` (and the first after ``reset()``) resets everyone.  One launch,
+    dgvit_frame_stack_push, thread = pixel; with device inputs (a device mask is read as the bytes it is) nothing synchronises, nothing
+    else is launched and the call is capturable.  "Reset everyone" -- ``reset=True``, or the first push after construction or
+    ``reset()`` -- is a host value passed to the kernel by value, so a capture freezes it: capture after a first eager ``push`` and
+    pass resets as a device mask, which every replay reads anew; a push captured directly after ``reset()`` would refill every channel
+    on every replay.  The returned tensor is the live buffer: valid until the next ``push``, clone it to keep it.
+
+    Contract with the ring: in the usual loop -- ``push`` the new observation, store the transition with ``add`` / ``add_vec``, mark
+    ``on_episode_end`` and pass ``reset`` for the environments that then start over -- the stack pushed at a step is bit-equal to
+    ``sample(indices=[slot], frame_stack=K)["obs"]`` of the slot that step was stored in, as long as the K - 1 slots before it are still
+    in the ring and, on a uint8 ring, as long as the frames are k / 255 values."""
+
+    def __init__(self, num_envs: int = 1, obs_shape: Tuple[int, int] = (128, 160), frames: int = 4, device="cuda"):
+        self.num_envs, self.obs_shape, self.frames = _stack_args(num_envs, obs_shape, frames)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DgvitError("FrameStack lives in HBM; pass a ROCm device")
+        self.stack = torch.zeros(self.num_envs, *self.obs_shape, self.frames, dtype=torch.float32, device=self.device)
+        self._fresh = True
+
+    def reset(self) -> None:
+        """Empty the stack: zeros, and the next ``push`` fills every environment's K channels with its frame"""
+        self.stack.zero_()
+        self._fresh = True
+
+    def push(self, frame, reset=None) -> torch.Tensor:
+        E, (H, W), K = self.num_envs, self.obs_shape, self.frames
+        if torch.is_tensor(frame) and frame.device.type != "cpu":
+            if frame.device != self.stack.device or frame.dtype != torch.float32:
+                raise ValueError(f"frame: a device tensor must be float32 on {self.stack.device}, got {frame.dtype} on {frame.device}")
+            frame = frame.detach()
+        else:
+            frame = torch.from_numpy(np.ascontiguousarray(np.asarray(frame.detach().numpy() if torch.is_tensor(frame) else frame),
+                                                          dtype=np.float32)).to(self.device, non_blocking=True)
+        if tuple(frame.shape) not in ((E, H, W),) + (((H, W),) if E == 1 else ()):
+            raise ValueError(f"frame: expected ({E}, {H}, {W}){f' or ({H}, {W})' if E == 1 else ''}, got {tuple(frame.shape)}")
+        frame = frame.reshape(E, H * W).contiguous()
+        everyone, mask = self._fresh, None
+        if isinstance(reset, (bool, np.bool_)):
+            everyone, reset = everyone or bool(reset), None
+        if reset is not None:                    # checked even where the first push resets everyone anyway
+            if torch.is_tensor(reset) and reset.device.type != "cpu":
+                if reset.device != self.stack.device or reset.dtype != torch.bool or tuple(reset.shape) != (E,):
+                    raise ValueError(f"reset: a device mask must be ({E},) bool on {self.stack.device}, got {tuple(reset.shape)} {reset.dtype} "
+                                     f"on {reset.device}")
+                mask = reset.detach().contiguous().view(torch.uint8)   # the bool's own bytes: no cast launch, no allocation
+            else:
+                host = np.asarray(reset.numpy() if torch.is_tensor(reset) else reset)
+                if host.dtype != np.bool_ or host.shape != (E,):
+                    raise ValueError(f"reset must be None, True or a bool mask ({E},), got {reset!r}")
+                mask = torch.from_numpy(host.astype(np.uint8)).to(self.device, non_blocking=True)
+        with torch.cuda.device(self.device):
+            rc = _lib.load().dgvit_frame_stack_push(_ptr(self.stack), _ptr(frame), H * W, _ptr(mask), int(everyone), E, H * W, K, _stream())
+        _lib.check(rc, "dgvit_frame_stack_push")
+        self._fresh = False
+        return self.stack

@@ -86,17 +86,17 @@ def _encoder_maps(module, inp, rows):
     return module.trans.attention_maps(istate, goal, rows)
 
 
-def _encoder(dim, depth, heads, image_size, patch_size):
+def _encoder(dim, depth, heads, image_size, patch_size, frame_channels=1):
     return GoT(image_size=image_size, patch_size=patch_size, num_classes=2, dim=dim, depth=depth, heads=heads, mlp_dim=2048,
-               channels=1)
+               channels=1, frame_channels=frame_channels)
 
 
 class GoTQNetwork(nn.Module):
     """Twin-Q critic on GoT features: forward([istate, pstate, a]) -> (q1, q2), each (B, nb_actions)."""
 
-    def __init__(self, nb_actions, nb_pstate, block, head, l_f_size, image_size=(128, 160), patch_size=(16, 20)):
+    def __init__(self, nb_actions, nb_pstate, block, head, l_f_size, image_size=(128, 160), patch_size=(16, 20), *, frame_channels=1):
         super().__init__()
-        self.trans = _encoder(l_f_size, block, head, image_size, patch_size)
+        self.trans = _encoder(l_f_size, block, head, image_size, patch_size, frame_channels)
         # dead parameters of the reference (got_sac_network.py:90-92): kept so checkpoints load strictly
         self.conv1 = nn.Conv2d(4, 16, 5, stride=2)
         self.conv2 = nn.Conv2d(16, 64, 5, stride=2)
@@ -131,9 +131,9 @@ class GoTPolicy(nn.Module):
     """Tanh-Gaussian actor on GoT features."""
 
     def __init__(self, nb_actions, nb_pstate, block, head, l_f_size, action_space=None, image_size=(128, 160),
-                 patch_size=(16, 20)):
+                 patch_size=(16, 20), *, frame_channels=1):
         super().__init__()
-        self.trans = _encoder(l_f_size, block, head, image_size, patch_size)
+        self.trans = _encoder(l_f_size, block, head, image_size, patch_size, frame_channels)
         self.fc_embed = nn.Linear(nb_pstate, l_f_size)
         self.fc1 = nn.Linear(l_f_size, 128)
         self.fc2 = nn.Linear(128, 128)
@@ -145,13 +145,22 @@ class GoTPolicy(nn.Module):
 
     def choose_action(self, istate, pstate, evaluate=False):
         dev = self.fc1.weight.device
-        if istate.ndim < 4:
+        K = getattr(self.trans, "frame_channels", 1)
+        if K > 1:                               # a channel-last stack, (H, W, K) or (E, H, W, K), as replay.FrameStack returns it
+            single = istate.ndim < 4
+            istate = torch.as_tensor(istate).float().to(dev)
+            pstate = torch.as_tensor(pstate).float().to(dev)
+            if single:
+                istate, pstate = istate.unsqueeze(0), pstate.unsqueeze(0)
+            istate = istate.contiguous()
+        elif istate.ndim < 4:
             istate = torch.FloatTensor(istate).float().permute(2, 0, 1)      # (H, W, 1) -> (1, H, W)
             pstate = torch.FloatTensor(pstate).float().unsqueeze(0)
         else:
             istate = torch.FloatTensor(istate).float().permute(0, 3, 1, 2)
             pstate = torch.FloatTensor(pstate).float()
-        istate, pstate = istate.to(dev), pstate.to(dev)
+        if K == 1:
+            istate, pstate = istate.to(dev), pstate.to(dev)
         if evaluate is False:
             action, _, _ = self.sample([istate, pstate])
         else:
@@ -187,9 +196,9 @@ class GoTPolicy(nn.Module):
 
 class DeterministicGoTPolicy(nn.Module):
     def __init__(self, nb_actions, nb_pstate, block, head, l_f_size, action_space=None, image_size=(128, 160),
-                 patch_size=(16, 20)):
+                 patch_size=(16, 20), *, frame_channels=1):
         super().__init__()
-        self.trans = _encoder(l_f_size, block, head, image_size, patch_size)
+        self.trans = _encoder(l_f_size, block, head, image_size, patch_size, frame_channels)
         self.fc_embed = nn.Linear(nb_pstate, l_f_size)
         self.fc1 = nn.Linear(l_f_size, 128)
         self.fc2 = nn.Linear(128, 32)

@@ -540,6 +540,52 @@ int dgvit_ring_store_frames_shared(const void* src0, int src0_u8, long long src0
 int dgvit_ring_next_rows(const int* next_row, const long long* idx, long long* out, long long nsel, long long nrows, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Frame stacks (dgvit_amd.replay: sample(..., frame_stack=K), FrameStack).  The ring keeps single frames; the stack of the
+ * K newest frames of a slot's episode, channel-last (H, W, K) with channel K - 1 the newest, exists only at sample time.  The n-step
+ * walk goes forward along an episode; this is the same walk backward.  1 <= frames = K <= 16.
+ *
+ * dgvit_ring_stack_rows: for each b < nsel, one wave.  s = clamp(idx[b], 0, nrows-1), E = envs, pred_0 = s, pred_k = (s - k E) mod nrows.
+ *   Predecessor k >= 1 is LINKED iff k E < nrows, and s - k E >= 0 or full != 0 (the caller's "every slot is written", by value), and
+ *   flags[pred_k] == 0 and done[pred_k * done_ld] == 0 -- where the n-step walk stops, seen from the slot behind.  d = the number of
+ *   consecutive linked predecessors from k = 1.  Then (int64, K per sample)
+ *     obs_rows[b][c]  = pred_min(K-1-c, d)                             c < K: frames from before the episode's first slot repeat it
+ *     next_rows[b][c] = pred^t_min(K-2-c, d_t)                         c < K - 1, rows of the OBS matrix
+ *     next_rows[b][K-1] = next_row ? next_row[t] (t where that is no arena row) : t      a row of the NEXT_OBS matrix / the arena
+ *   with t = clamp(tail[b]) and d_t walked back from t when tail is not NULL (an n-step sample: dgvit_nstep_walk's tail_out), else
+ *   t = s and d_t = d.  envs divides nrows; arena_rows is the arena's row count with next_row and nrows without.  Every row is a slot
+ *   of the ring or a row of the arena; no atomics.
+ * dgvit_gather_stack_frames: out[b][p * K + c] = fp32(src_c[clamp(rows[b][c])][p]) for p < cols, c < K, zeros up to row_floats, a
+ *   multiple of 4 and at least cols * K: the (B, H, W, K) batch.  src_c = src1 for c == K - 1 and src0 before (rows clamped to nrows1 and
+ *   nrows0): obs passes its matrix twice, next_obs the obs matrix and its own -- or the arena twice.  ring_u8: 0 fp32 rows of ring_ld
+ *   floats (a multiple of 4), 1 byte rows of ring_ld bytes (a multiple of 16), returned as code / 255 like dgvit_gather_rows_u8.  One
+ *   launch: a thread reads one float4 / one dword (4 pixels) of each of the K frames and forms the 4 K contiguous floats as K float4s,
+ *   which a workgroup stores in output order, 4 KiB per store, through 4 K KiB of LDS.  row_floats may exceed al4(cols * K): every
+ *   float up to row_floats is written, zeros behind the stack.
+ *   cols * K <= 2^27, 1 <= nsel < 2^24; src0, src1, out 16-byte aligned.
+ * dgvit_gather_shift_stack_frames: the same with the random shift of dgvit_gather_shift_frames, ONE (dy, dx) per sample for all K channels:
+ *     out[b][(y W + x) K + c] = fp32(src_c[rows[b][c]][clamp(y + dy_b, 0, H-1) * W + clamp(x + dx_b, 0, W-1)])
+ *   The draw is that call's -- sample index b, stream_id, seed / seed_dev -- so equal seeds give the shift table of the unstacked call;
+ *   shifts_out may be NULL.  0 <= pad < min(H, W).
+ * dgvit_frame_stack_push: the acting side.  stack is (envs, cols, K) fp32 in place; per environment e and pixel p
+ *     stack[e][p][c] = stack[e][p][c + 1] for c < K - 1,  stack[e][p][K - 1] = frame[e * frame_ld + p]
+ *   or, where reset_all != 0 or reset[e] != 0 (reset: envs bytes, may be NULL), all K channels = the new frame.  One launch, thread =
+ *   pixel.
+ * None of the four synchronises; all are capturable.
+ * -------------------------------------------------------------------------------------------- */
+int dgvit_ring_stack_rows(const long long* idx, const long long* tail /* may be NULL */, const unsigned char* flags, const float* done,
+                          long long done_ld, const int* next_row /* may be NULL */, long long* obs_rows, long long* next_rows,
+                          long long nsel, long long nrows, long long envs, int frames, int full, long long arena_rows, void* stream);
+int dgvit_gather_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, long long nsel, long long cols,
+                              int frames, int ring_u8, long long ring_ld, long long row_floats, long long nrows0, long long nrows1,
+                              void* stream);
+int dgvit_gather_shift_stack_frames(const void* src0, const void* src1, const long long* rows, float* out, int* shifts_out /* may be NULL */,
+                                    long long nsel, int H, int W, int frames, int ring_u8, long long ring_ld, long long row_floats,
+                                    long long nrows0, long long nrows1, int pad, int stream_id, unsigned long long seed,
+                                    const unsigned long long* seed_dev, void* stream);
+int dgvit_frame_stack_push(float* stack, const float* frame, long long frame_ld, const unsigned char* reset /* may be NULL */, int reset_all,
+                           long long envs, long long cols, int frames, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Prioritized replay (proportional PER, Schaul et al. 2016) on the device: the index draw in front of the gathers, the importance
  * weights and the priority write-back, none of which touches the host (dgvit_amd.replay.PrioritizedDeviceReplayBuffer).
  *
