@@ -229,6 +229,10 @@ DIAG_SIGNATURES = {
     "dgvit_attention_forward_queries": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_backward_queries": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dgvit_attention_forward_bf16_queries": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dgvit_attention_forward_drop": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
+    "dgvit_attention_backward_drop": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
+    "dgvit_attention_forward_tiled_drop": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
+    "dgvit_attention_backward_tiled_drop": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _F, _ULL, _P, _I, _P]),
     "dgvit_set_gemm_bf16_mfma16": (None, [_I]),
     "dgvit_set_gemm_bf16_stamps": (None, [_P]),
     # the row kernels with row_step / nullable outputs / the queued reduction (include/dgvit_hip_diag.h)

@@ -57,6 +57,45 @@ extern "C" int dgvit_attention_forward_bf16_queries(const unsigned short* qkv, u
                                                     int nq, void* stream) {
   return attention_fwd_bf16((const bf16_t*)qkv, (bf16_t*)out, lse, B, N, H, dh, nq, (hipStream_t)stream);
 }
+// ---- the fp32 attention kernels with the site-0 mask of one layer (tests/test_gpu_attention_fp32_matrix.py): in the product only the
+// encoder reaches the DROP instantiations
+namespace {
+int check_attn_layer(const char* what, int layer) {   // check_layer_site of encoder_bf16.hip, for the one site these entries have
+  DGVIT_CHECK_ARG(layer >= 0 && layer < (1 << 22), "%s: layer=%d outside [0, 2^22)", what, layer);
+  return DGVIT_OK;
+}
+}  // namespace
+extern "C" int dgvit_attention_forward_drop(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, float keep,
+                                            unsigned long long seed, const unsigned long long* seed_dev, int layer, void* stream) {
+  TRY(check_attn_layer("dgvit_attention_forward_drop", layer));
+  DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dgvit_attention_forward_drop: keep=%g outside (0, 1]", (double)keep);
+  const LayerDrop drop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev};
+  return attention_fwd(qkv, out, lse, B, N, H, dh, nq, (hipStream_t)stream, &drop);
+}
+extern "C" int dgvit_attention_backward_drop(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B,
+                                             int N, int H, int dh, int nq, float keep, unsigned long long seed,
+                                             const unsigned long long* seed_dev, int layer, void* stream) {
+  TRY(check_attn_layer("dgvit_attention_backward_drop", layer));
+  DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dgvit_attention_backward_drop: keep=%g outside (0, 1]", (double)keep);
+  const LayerDrop drop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev};
+  return attention_bwd(qkv, out, dout, lse, dqkv, B, N, H, dh, nq, (hipStream_t)stream, &drop);
+}
+extern "C" int dgvit_attention_forward_tiled_drop(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, float keep,
+                                                  unsigned long long seed, const unsigned long long* seed_dev, int layer, void* stream) {
+  TRY(check_attn_layer("dgvit_attention_forward_tiled_drop", layer));
+  DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dgvit_attention_forward_tiled_drop: keep=%g outside (0, 1]", (double)keep);
+  const LayerDrop drop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev};
+  return attention_fwd_tiled(qkv, out, lse, B, N, H, dh, nq, (hipStream_t)stream, &drop);
+}
+extern "C" int dgvit_attention_backward_tiled_drop(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                                   float* scratch, long long scratch_floats, int B, int N, int H, int dh, int nq,
+                                                   float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer,
+                                                   void* stream) {
+  TRY(check_attn_layer("dgvit_attention_backward_tiled_drop", layer));
+  DGVIT_CHECK_ARG(keep > 0.f && keep <= 1.f, "dgvit_attention_backward_tiled_drop: keep=%g outside (0, 1]", (double)keep);
+  const LayerDrop drop{keep, drop_tag(layer, DROP_ATTN), seed, seed_dev};
+  return attention_bwd_tiled(qkv, out, dout, lse, dqkv, scratch, scratch_floats, B, N, H, dh, nq, (hipStream_t)stream, &drop);
+}
 extern "C" void dgvit_set_gemm_bf16_group_m(int rows) { g_gemm_bf16_group_m = rows > 0 ? rows : g_gemm_bf16_group_m_default; }
 extern "C" void dgvit_set_gemm_bf16_stamps(long long* stamps) { g_gemm_bf16_stamps = stamps; }
 extern "C" void dgvit_set_gemm_bf16_l2_budget_kb(int kb) { g_gemm_bf16_l2_budget_kb = kb > 0 ? kb : 0; }

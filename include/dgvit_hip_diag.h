@@ -108,6 +108,21 @@ void dgvit_set_gemm_wgrad_slice_major(int on);
 int dgvit_attention_forward_queries(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, void* stream);
 int dgvit_attention_backward_queries(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N, int H,
                                      int dh, int nq, void* stream);
+/* The fp32 attention kernels with the site-0 (attention-probability) mask of `layer`, which in the product only the encoder reaches:
+ * dgvit_attention_forward_queries / _backward_queries and dgvit_attention_forward_tiled / _backward_tiled with
+ * LayerDrop{keep, tag(layer, site 0), seed, seed_dev}.  keep in (0, 1]; 1 = the calls without _drop, bit for bit; seed_dev, if not NULL,
+ * overrides seed at run time; 0 <= layer < 2^22.  P V and dV take m o P / keep, lse is the undropped softmax's; the backward
+ * regenerates the mask of the same keep, seed and layer. */
+int dgvit_attention_forward_drop(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, float keep,
+                                 unsigned long long seed, const unsigned long long* seed_dev, int layer, void* stream);
+int dgvit_attention_backward_drop(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int N, int H,
+                                  int dh, int nq, float keep, unsigned long long seed, const unsigned long long* seed_dev, int layer,
+                                  void* stream);
+int dgvit_attention_forward_tiled_drop(const float* qkv, float* out, float* lse, int B, int N, int H, int dh, int nq, float keep,
+                                       unsigned long long seed, const unsigned long long* seed_dev, int layer, void* stream);
+int dgvit_attention_backward_tiled_drop(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* scratch,
+                                        long long scratch_floats, int B, int N, int H, int dh, int nq, float keep, unsigned long long seed,
+                                        const unsigned long long* seed_dev, int layer, void* stream);
 /* dgvit_attention_forward_bf16 (dgvit_hip.h) for the first nq query tokens only, as the bf16 encoder's last block calls it with nq = 1:
  * rows >= nq of out / lse are not written.  1 <= nq <= N <= 288; lse may be NULL. */
 int dgvit_attention_forward_bf16_queries(const unsigned short* qkv, unsigned short* out, float* lse, int B, int N, int H, int dh, int nq,
