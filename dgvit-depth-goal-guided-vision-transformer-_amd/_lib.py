@@ -115,6 +115,11 @@ SIGNATURES = {
     "dgvit_cnn_forward": (_I, [_P, _TABLE, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_cnn_backward": (_I, [_P, _TABLE, _TABLE, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
     "dgvit_cnn_backward_v2": (_I, [_P, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _P]),
+    "dgvit_cnn_workspace_floats_v2": (_LL, [_I, _I, _I, _I]),
+    "dgvit_cnn_forward_scratch_floats_v2": (_LL, [_I, _I, _I, _I]),
+    "dgvit_cnn_backward_scratch_floats_v2": (_LL, [_I, _I, _I, _I]),
+    "dgvit_cnn_forward_v2": (_I, [_P, _TABLE, _P, _P, _LL, _P, _LL, _I, _I, _I, _I, _P]),
+    "dgvit_cnn_backward_v3": (_I, [_P, _TABLE, _TABLE, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _I, _P]),
     "dgvit_gather_rows": (_I, [_P, _P, _P, _LL, _LL, _LL, _P]),
     "dgvit_gather_shift_frames": (_I, [_P, _P, _P, _P, _LL, _I, _I, _LL, _LL, _I, _I, _ULL, _P, _P]),
     "dgvit_quantize_rows_u8": (_I, [_P, _LL, _P, _LL, _LL, _LL, _LL, _LL, _P]),

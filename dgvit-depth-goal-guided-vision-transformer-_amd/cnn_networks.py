@@ -3,6 +3,10 @@ shipped configuration trains with (``critic_type: "CNN"``, config.yaml:61; got_s
 CNN actor ``GaussianPolicy`` (:258-327).  Same constructor signatures, attribute names and ``state_dict`` keys
 (``conv1..3`` keep the reference's (cout, cin, 5, 5) weight layout); the conv stack is one fused HIP node
 (functional.cnn_features), every Linear runs on the MFMA GEMM.
+
+``frame_channels=K`` (keyword-only, 1 <= K <= 16) makes ``conv1`` an ``nn.Conv2d(K, 16, 5, stride=2)`` that reads the contiguous
+channel-last (B, H, W, K) stacks of ``sample(frame_stack=K)`` / ``replay.FrameStack.push``: the network equals the reference module with
+that conv1 applied to ``stack.permute(0, 3, 1, 2)``.  The stack is conv1's NHWC input as it stands -- no permute is made anywhere.
 """
 import torch
 from torch import nn
@@ -10,27 +14,43 @@ from torch.distributions import Normal
 
 from . import functional as F_
 from . import sac_networks as _S
+from .goalformer import _frame_channels
 from .sac_networks import LOG_SIG_MAX, LOG_SIG_MIN, epsilon, weights_init_, _lin, _head, _action_affine
 
 
 class _ConvStack(nn.Module):
-    def _make_convs(self):
-        self.conv1 = nn.Conv2d(1, 16, 5, stride=2)
+    def _make_convs(self, frame_channels=1):
+        self.frame_channels = _frame_channels(frame_channels)
+        self.conv1 = nn.Conv2d(self.frame_channels, 16, 5, stride=2)
         self.conv2 = nn.Conv2d(16, 64, 5, stride=2)
         self.conv3 = nn.Conv2d(64, 256, 5, stride=2)
         self.avg = nn.AdaptiveAvgPool2d(output_size=(1, 1))
 
+    def _frames(self, istate):
+        """``istate`` as the fused stack takes it: unchanged for single frames; with frame_channels = K > 1 a contiguous channel-last
+        (B, H, W, K) stack, checked on the host before anything touches a device"""
+        K = getattr(self, "frame_channels", 1)
+        if K == 1:
+            return istate
+        if not torch.is_tensor(istate) or istate.dim() != 4 or istate.shape[3] != K or not istate.is_contiguous():
+            got = (f"{tuple(istate.shape)}{'' if istate.is_contiguous() else ', not contiguous'}" if torch.is_tensor(istate)
+                   else type(istate).__name__)
+            raise ValueError(f"istate must be a contiguous channel-last (B, H, W, K) = (B, H, W, {K}) stack of frame_channels={K} frames, "
+                             f"channel K - 1 the newest (a channel-first batch takes permute(0, 2, 3, 1).contiguous() first), got {got}")
+        return istate
+
     def _features(self, istate):
+        istate = self._frames(istate)
         return F_.cnn_features(istate, [self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
                                         self.conv3.weight, self.conv3.bias])
 
 
 class QNetwork(_ConvStack):
-    """Twin-Q CNN critic: forward([istate (B,H,W), pstate (B,2), a (B,2)]) -> (q1, q2)."""
+    """Twin-Q CNN critic: forward([istate (B,H,W), pstate (B,2), a (B,2)]) -> (q1, q2); istate (B,H,W,K) with frame_channels=K."""
 
-    def __init__(self, nb_actions, nb_pstate):
+    def __init__(self, nb_actions, nb_pstate, *, frame_channels=1):
         super().__init__()
-        self._make_convs()
+        self._make_convs(frame_channels)
         self.fc1 = nn.Linear(256 + 32 + nb_actions, 128)
         self.fc2 = nn.Linear(128, 32)
         self.fc3 = nn.Linear(32, nb_actions)
@@ -49,11 +69,11 @@ class QNetwork(_ConvStack):
 
 
 class GaussianPolicy(_ConvStack):
-    """Tanh-Gaussian CNN actor (got_sac_network.py:258-327)."""
+    """Tanh-Gaussian CNN actor (got_sac_network.py:258-327); istate (B,H,W,K) with frame_channels=K."""
 
-    def __init__(self, nb_actions, nb_pstate, action_space=None):
+    def __init__(self, nb_actions, nb_pstate, action_space=None, *, frame_channels=1):
         super().__init__()
-        self._make_convs()
+        self._make_convs(frame_channels)
         self.fc_embed = nn.Linear(nb_pstate, 32)
         self.fc1 = nn.Linear(256 + 32, 128)
         self.fc2 = nn.Linear(128, 32)

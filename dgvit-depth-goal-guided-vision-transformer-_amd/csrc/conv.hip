@@ -7,8 +7,9 @@
 // weight permuted to [cout][(kh,kw,cin)], bias + ReLU fused in its epilogue; the output rows ARE the next layer's
 // NHWC input.  Backward: dW = dY^T cols (split-K GEMM, bias gradient fused), dcols = dY W (GEMM), and a gather-style
 // col2im (each input pixel sums the <= 9 windows that cover it: deterministic, no atomics) with the previous
-// layer's ReLU mask fused; its unmasked single-channel form turns conv1's column gradient into the frame gradient.
-// The single-channel first layer pads K = 25 to 28 so that it takes the float4 path.
+// layer's ReLU mask fused; its unmasked form turns conv1's column gradient into the frame gradient.
+// The single-channel first layer pads K = 25 to 28 so that it takes the float4 path; on a channel-last stack of C frames (the NHWC
+// input of a Conv2d(C,16,5,s2)) conv1's rows are al4(25 C) floats.
 #include "common.h"
 #include "kernels.h"
 
@@ -50,9 +51,38 @@ __global__ void __launch_bounds__(256) im2col_c1_kernel(const float* __restrict_
   cols[idx] = v;
 }
 
+// any channel count (conv1 on a channel-last frame stack with C = 2, 3, 5, ...): row of KP = al4(25 C) floats, tail zero.  For one kh
+// the KS * C floats of a window are contiguous in the NHWC input, so a row is five contiguous runs: one thread writes one float4 of a
+// row (rows are 16-byte aligned) from four consecutive floats of a run (a run may end inside the four; C is odd in general, so the reads
+// are dwords -- consecutive lanes read consecutive addresses).  The row is decoded once per thread, the run with one small division.
+__global__ void __launch_bounds__(256) im2col_cn_kernel(const float* __restrict__ x, float* __restrict__ cols, int B, int H, int W, int C,
+                                                        int OH, int OW, int KP) {
+  const int kp4 = KP / 4;
+  const long long total = (long long)B * OH * OW * kp4;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int k0 = (int)(idx % kp4) * 4;
+  long long r = idx / kp4;
+  const int ow = (int)(r % OW); r /= OW;
+  const int oh = (int)(r % OH);
+  const long long b = r / OH;
+  const int run = KS * C, K = KS * run;
+  const long long pitch = (long long)W * C;
+  const float* win = x + ((b * H + oh * STRIDE) * W + ow * STRIDE) * C;   // window origin; its row kh starts at win + kh * pitch
+  int kh = k0 / run, j = k0 - kh * run;
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = k0 + e < K ? win[kh * pitch + j] : 0.f;
+    if (++j == run) { j = 0; ++kh; }
+  }
+  reinterpret_cast<float4*>(cols)[idx] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
 // dx[b][y][x][c] = relu'(xin) * sum over windows (oh,ow,kh,kw) with oh*2+kh == y, ow*2+kw == x of dcols[...]
 // RELU == false: no mask (the image gradient of conv1: the frame is not the output of a ReLU); xin is not read.  V: channels per thread,
-// 4 (C % 4 == 0, float4) or 1 (the single-channel frame).  dcols rows are KP floats (conv1: the 25 real taps of 28; the padding is never read).
+// 4 (C % 4 == 0, float4) or 1 (any C: the single-channel frame, a frame stack of 2, 3, 5, ... channels).  dcols rows are KP floats
+// (conv1: the 25 C real taps of KP; the padding is never read).
 template <int V, bool RELU>
 __global__ void __launch_bounds__(256) col2im_relu_kernel(const float* __restrict__ dcols, const float* __restrict__ xin,
                                                           float* __restrict__ dx, int B, int H, int W, int C, int OH, int OW, int KP) {
@@ -159,10 +189,13 @@ inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 int im2col(const float* x, float* cols, int B, int H, int W, int C, int OH, int OW, int KP, hipStream_t st) {
   if (C == 1) {
     hipLaunchKernelGGL(im2col_c1_kernel, dim3(nblk((long long)B * OH * OW * KP)), dim3(256), 0, st, x, cols, B, H, W, OH, OW, KP);
-  } else {
-    DGVIT_CHECK_ARG(C % 4 == 0 && KP == KS * KS * C, "im2col: channels must be 1 or a multiple of 4");
+  } else if (C % 4 == 0) {
+    DGVIT_CHECK_ARG(KP == KS * KS * C, "im2col: rows of %d floats for %d channels", KP, C);
     hipLaunchKernelGGL(im2col_c4_kernel, dim3(nblk((long long)B * OH * OW * KS * KS * (C / 4))), dim3(256), 0, st, x, cols, B, H, W,
                        C, OH, OW);
+  } else {
+    DGVIT_CHECK_ARG(C > 1 && KP % 4 == 0 && KP >= KS * KS * C && al16(cols), "im2col: rows of %d floats for %d channels, or unaligned rows", KP, C);
+    hipLaunchKernelGGL(im2col_cn_kernel, dim3(nblk((long long)B * OH * OW * (KP / 4))), dim3(256), 0, st, x, cols, B, H, W, C, OH, OW, KP);
   }
   DGVIT_CHECK_LAUNCH("im2col");
   return DGVIT_OK;
@@ -176,10 +209,14 @@ int col2im_relu(const float* dcols, const float* xin, float* dx, int B, int H, i
   return DGVIT_OK;
 }
 
-int col2im_frame(const float* dcols, float* dx, int B, int H, int W, int OH, int OW, int KP, hipStream_t st) {
-  DGVIT_CHECK_ARG(KP >= KS * KS, "col2im: column rows of %d floats hold fewer than the %d taps", KP, KS * KS);
-  hipLaunchKernelGGL((col2im_relu_kernel<1, false>), dim3(nblk((long long)B * H * W)), dim3(256), 0, st, dcols, nullptr, dx, B, H, W, 1, OH,
-                     OW, KP);
+int col2im_frame(const float* dcols, float* dx, int B, int H, int W, int C, int OH, int OW, int KP, hipStream_t st) {
+  DGVIT_CHECK_ARG(C >= 1 && KP >= KS * KS * C, "col2im: column rows of %d floats hold fewer than the %d taps", KP, KS * KS * C);
+  if (C % 4 == 0 && KP % 4 == 0 && al16(dcols) && al16(dx))
+    hipLaunchKernelGGL((col2im_relu_kernel<4, false>), dim3(nblk((long long)B * H * W * (C / 4))), dim3(256), 0, st, dcols, nullptr, dx, B, H,
+                       W, C, OH, OW, KP);
+  else
+    hipLaunchKernelGGL((col2im_relu_kernel<1, false>), dim3(nblk((long long)B * H * W * C)), dim3(256), 0, st, dcols, nullptr, dx, B, H, W, C,
+                       OH, OW, KP);
   DGVIT_CHECK_LAUNCH("col2im");
   return DGVIT_OK;
 }

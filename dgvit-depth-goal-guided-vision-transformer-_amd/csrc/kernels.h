@@ -72,8 +72,8 @@ int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, 
 int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
-// the single-channel frame gradient from conv1's column gradient (rows of KP floats, 25 real taps): no ReLU mask
-int col2im_frame(const float*, float*, int, int, int, int, int, int, hipStream_t);
+// the (B, H, W, C) frame gradient from conv1's column gradient (rows of KP floats, 25 C real taps): no ReLU mask
+int col2im_frame(const float* dcols, float* dx, int B, int H, int W, int C, int OH, int OW, int KP, hipStream_t);
 int weight_pack(const float*, float*, int, int, int, int, hipStream_t);
 int avgpool(const float*, float*, int, int, int, hipStream_t);
 int avgpool_bwd_relu(const float*, const float*, float*, int, int, int, hipStream_t);

@@ -240,6 +240,18 @@ def got_encoder(img, goal, cfg_tuple, params, dropout_keep=1.0, dropout_seed=0, 
 
 
 # ------------------------------------------------------------------------------------------------ CNN feature stack
+def _cnn_frame_dims(img, params):
+    """(B, H, W, C) of the frames conv1 reads: (B, H, W) single frames, or a channel-last (B, H, W, K) stack for a conv1.weight of
+    (16, K, 5, 5) -- conv1's NHWC input as it stands"""
+    K = int(params[0].shape[1]) if params[0].dim() == 4 else -1
+    if img.dim() == 3 and K == 1:
+        return (*img.shape, 1)
+    if img.dim() == 4 and img.shape[3] == K:
+        return tuple(img.shape)
+    raise DgvitError(f"img must be (B, H, W) for a conv1.weight of (16, 1, 5, 5), or a channel-last (B, H, W, K) stack for (16, K, 5, 5); "
+                     f"got img {tuple(img.shape)} and conv1.weight {tuple(params[0].shape)}")
+
+
 class _CnnStack(torch.autograd.Function):
     """conv1-relu-conv2-relu-conv3-relu-avgpool of QNetwork / GaussianPolicy (got_sac_network.py:151-155) as one node."""
 
@@ -248,18 +260,16 @@ class _CnnStack(torch.autograd.Function):
         lib = _lib.load()
         img = _dev(img, "img")
         params = [_dev(p, f"conv param[{i}]") for i, p in enumerate(params)]
-        if img.dim() != 3:
-            raise DgvitError(f"img must be (B, H, W), got {tuple(img.shape)}")
-        B, H, W = img.shape
-        nws = lib.dgvit_cnn_workspace_floats(B, H, W)
-        nsc = lib.dgvit_cnn_forward_scratch_floats(B, H, W)
+        B, H, W, C = _cnn_frame_dims(img, params)
+        nws = lib.dgvit_cnn_workspace_floats_v2(B, H, W, C)
+        nsc = lib.dgvit_cnn_forward_scratch_floats_v2(B, H, W, C)
         if nws < 0 or nsc < 0:
             _lib.check(-1, "dgvit_cnn_workspace_floats")
         ws = torch.empty(nws, dtype=torch.float32, device=img.device)
         scratch = torch.empty(nsc, dtype=torch.float32, device=img.device)
         feat = torch.empty(B, 256, dtype=torch.float32, device=img.device)
         with torch.cuda.device(img.device):
-            rc = lib.dgvit_cnn_forward(_ptr(img), _table(params), _ptr(feat), _ptr(ws), nws, _ptr(scratch), nsc, B, H, W, _stream())
+            rc = lib.dgvit_cnn_forward_v2(_ptr(img), _table(params), _ptr(feat), _ptr(ws), nws, _ptr(scratch), nsc, B, H, W, C, _stream())
         _lib.check(rc, "dgvit_cnn_forward")
         if need_grad:
             ctx.ws = ws
@@ -272,21 +282,23 @@ class _CnnStack(torch.autograd.Function):
         ws = _take_workspace(ctx, "dgvit_cnn_backward")
         img, *params = ctx.saved_tensors
         dfeat = _dev(dfeat, "dfeat")
-        B, H, W = img.shape
+        B, H, W, C = _cnn_frame_dims(img, params)
         grads = [torch.empty_like(p) if need else None for p, need in zip(params, ctx.needs_input_grad[2:])]   # None: frozen, skipped
-        dimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
-        nsc = lib.dgvit_cnn_backward_scratch_floats(B, H, W)
+        dimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None      # the stack's own shape
+        nsc = lib.dgvit_cnn_backward_scratch_floats_v2(B, H, W, C)
         scratch = torch.empty(nsc, dtype=torch.float32, device=img.device)
         with torch.cuda.device(img.device):
-            rc = lib.dgvit_cnn_backward_v2(_ptr(img), _table(params), _table(grads), _ptr(dfeat), _ptr(dimg), _ptr(ws), ws.numel(),
-                                           _ptr(scratch), nsc, B, H, W, _stream())
+            rc = lib.dgvit_cnn_backward_v3(_ptr(img), _table(params), _table(grads), _ptr(dfeat), _ptr(dimg), _ptr(ws), ws.numel(),
+                                           _ptr(scratch), nsc, B, H, W, C, _stream())
         _lib.check(rc, "dgvit_cnn_backward")
         ctx.ws = None
         return (dimg, None, *grads)
 
 
 def cnn_features(img, conv_params):
-    """(B, H, W) frames -> (B, 256) pooled features; conv_params = [w1, b1, w2, b2, w3, b3] (reference layouts)."""
+    """(B, H, W) frames, or a contiguous channel-last (B, H, W, K) stack of them when conv1.weight is (16, K, 5, 5) (1 <= K <= 16: what
+    ``sample(frame_stack=K)`` returns; equals the reference stack on ``img.permute(0, 3, 1, 2)``) -> (B, 256) pooled features;
+    conv_params = [w1, b1, w2, b2, w3, b3] (reference layouts).  The frame gradient comes back in the shape of ``img``."""
     if img.shape[0] == 0:
         return _empty_batch((0, 256), [img, *conv_params])
     need_grad = torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in conv_params))

@@ -364,6 +364,20 @@ int dgvit_cnn_backward(const float* img, const float* const* params, float* cons
 int dgvit_cnn_backward_v2(const float* img, const float* const* params, float* const* grads, const float* dfeat, float* dimg,
                           const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H, int W,
                           void* stream);
+/* The same stack on frame stacks: conv1 is Conv2d(C,16,5,s2), 1 <= C <= 16 (anything else: DGVIT_ERR_ARG; the sizing functions
+ * return -1).  The stack is CHANNEL-LAST: img and dimg are (B, H, W, C) floats, contiguous, channel C - 1 the newest frame -- what
+ * sample(frame_stack=C) returns, and conv1's NHWC input as it stands: the result equals nn.Conv2d(C, 16, 5, stride=2) applied to
+ * img.permute(0, 3, 1, 2).  params[0] / grads[0] are (16, C, 5, 5), the reference layout of that Conv2d; the other five slots are
+ * unchanged.  The entry points above are these with C = 1 (the same launches, bit for bit).  conv1's column matrix of the backward is
+ * M1 x al4(25 C) floats (M1 = B * OH1 * OW1; 28 per row for C = 1) and is not chunked: size the scratch with the _v2 functions. */
+long long dgvit_cnn_workspace_floats_v2(int B, int H, int W, int C);
+long long dgvit_cnn_forward_scratch_floats_v2(int B, int H, int W, int C);
+long long dgvit_cnn_backward_scratch_floats_v2(int B, int H, int W, int C);
+int dgvit_cnn_forward_v2(const float* img, const float* const* params, float* feat, float* ws, long long ws_floats,
+                         float* scratch, long long scratch_floats, int B, int H, int W, int C, void* stream);
+int dgvit_cnn_backward_v3(const float* img, const float* const* params, float* const* grads, const float* dfeat, float* dimg,
+                          const float* ws, long long ws_floats, float* scratch, long long scratch_floats, int B, int H, int W, int C,
+                          void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * the step BEFORE the path.  The reference samples numpy batches from cpprb and copies
