@@ -12,7 +12,8 @@ from .cnn_networks import QNetwork, GaussianPolicy  # noqa: F401
 from . import functional  # noqa: F401
 from . import preprocess  # noqa: F401
 from . import sac_losses  # noqa: F401
+from . import replay  # noqa: F401
 from .runtime import GraphedStep  # noqa: F401
 
-__all__ = ["GoT", "GoTPolicy", "GoTQNetwork", "DeterministicGoTPolicy", "QNetwork", "GaussianPolicy", "weights_init_", "functional", "sac_losses", "GraphedStep", "DgvitError",
+__all__ = ["GoT", "GoTPolicy", "GoTQNetwork", "DeterministicGoTPolicy", "QNetwork", "GaussianPolicy", "weights_init_", "functional", "sac_losses", "replay", "GraphedStep", "DgvitError",
            "load_library", "diagnostic_library", "LIB_PATH", "DIAG_LIB_PATH"]

@@ -96,6 +96,11 @@ class GaussianPolicy(_ConvStack):
         mean, log_std_raw = self._head_outputs(inp)
         return _S._tanh_gaussian(self, mean, log_std_raw)
 
+    def log_prob(self, inp, action):
+        """``log pi(action | inp)``, (B, 1), at a given ``action`` (B, nb_actions): ``GoTPolicy.log_prob`` behind the CNN head"""
+        mean, log_std_raw = self._head_outputs(inp)
+        return _S._log_prob(self, mean, log_std_raw, action)
+
     def to(self, device):
         self.action_scale = self.action_scale.to(device)
         self.action_bias = self.action_bias.to(device)

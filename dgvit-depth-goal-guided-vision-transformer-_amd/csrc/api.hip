@@ -106,6 +106,17 @@ extern "C" int dgvit_tanh_gaussian_backward(const float* mean, const float* log_
   return tanh_gaussian_backward(mean, log_std_raw, eps, scale, scale_n, ls_min, ls_max, d_action, d_log_prob, d_tanh_mean, dmean, dlog_std_raw, B, A,
                                 (hipStream_t)stream);
 }
+extern "C" int dgvit_tanh_gaussian_log_prob(const float* mean, const float* log_std_raw, const float* action, const float* scale,
+                                            const float* bias, int scale_n, float ls_min, float ls_max, float* log_prob, int B, int A,
+                                            void* stream) {
+  return tanh_gaussian_log_prob(mean, log_std_raw, action, scale, bias, scale_n, ls_min, ls_max, log_prob, B, A, (hipStream_t)stream);
+}
+extern "C" int dgvit_tanh_gaussian_log_prob_backward(const float* mean, const float* log_std_raw, const float* action, const float* scale,
+                                                     const float* bias, int scale_n, float ls_min, float ls_max, const float* d_log_prob,
+                                                     float* dmean, float* dlog_std_raw, int B, int A, void* stream) {
+  return tanh_gaussian_log_prob_backward(mean, log_std_raw, action, scale, bias, scale_n, ls_min, ls_max, d_log_prob, dmean, dlog_std_raw, B, A,
+                                         (hipStream_t)stream);
+}
 
 // ---------------------------------------------------------------------------------------------- operator exports
 extern "C" long long dgvit_gemm_scratch_floats(int layout, int M, int N, int K) {
@@ -269,6 +280,11 @@ extern "C" int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, con
 }
 extern "C" int dgvit_sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, void* stream) {
   return sac_scale_grads(src, dst, n, scale_dev, (hipStream_t)stream);
+}
+extern "C" int dgvit_sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo,
+                                 const float* q2_demo, const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A,
+                                 void* stream) {
+  return sac_bc_loss(pred, action, mask, mask_u8, q1_demo, q2_demo, q1_pi, q2_pi, nll, out, grads, B, A, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- replay staging

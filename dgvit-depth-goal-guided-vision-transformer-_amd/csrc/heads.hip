@@ -471,7 +471,8 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
 //   log_prob = sum_a [ -eps^2 / 2 - ls - log(sqrt(2 pi)) - log(scale * (1 - y^2) + 1e-6) ]
 // (Normal(mean, std).log_prob(x) evaluated at x = mean + std * eps is -eps^2/2 - ls - log sqrt(2 pi) exactly.)
 namespace {
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;
+constexpr double kHalfLog2PiD = 0.91893853320467274178;      // log(sqrt(2 pi)); the log-density kernels below sum in double
+constexpr float kHalfLog2Pi = (float)kHalfLog2PiD;
 constexpr float kEpsilon = 1e-6f;
 
 __global__ void __launch_bounds__(256) tanh_gaussian_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ lsr,
@@ -537,5 +538,105 @@ int tanh_gaussian_backward(const float* mean, const float* lsr, const float* eps
   hipLaunchKernelGGL(tanh_gaussian_bwd_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, mean, lsr, eps, scale, sn, lo, hi, dact, dlp,
                      dtm, dmean, dls, B, A);
   DGVIT_CHECK_LAUNCH("tanh_gaussian_backward");
+  return DGVIT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tanh-Gaussian log-density of a given action
+// log pi(a | s) for a STORED action: the density sample() reports, at y = (a - bias) / scale instead of tanh(mean + std eps):
+//   y  = clamp((a - bias) / scale, -(1 - 1e-6), 1 - 1e-6);   x = atanh(y) = 0.5 log((1 + y) / (1 - y))
+//   ls = clamp(log_std_raw, ls_min, ls_max);   e = (x - mean) exp(-ls)
+//   log_prob = sum_a [ -e^2 / 2 - ls - log(sqrt(2 pi)) - log(scale * (1 - y^2) + 1e-6) ]
+// A demonstration at or beyond the action bound stays finite through the clip.  In double from the fp32 inputs, rounded once where a
+// value is stored (the convention of sac_loss.hip): near the clip atanh amplifies every fp32 rounding of 1 - y by up to 10^6, and the
+// whole kernel is B * A elements.  thread = one batch row, as the sampling kernels.
+namespace {
+constexpr double kLogProbClip = 1.0 - 1e-6;
+
+__device__ __forceinline__ double log_prob_y(float a, float sc, float bi) {
+  return fmin(fmax(((double)a - (double)bi) / (double)sc, -kLogProbClip), kLogProbClip);
+}
+
+__global__ void __launch_bounds__(256) tanh_gaussian_log_prob_kernel(const float* __restrict__ mean, const float* __restrict__ lsr,
+                                                                     const float* __restrict__ action, const float* __restrict__ scale,
+                                                                     const float* __restrict__ bias, int sn, float lo, float hi,
+                                                                     float* __restrict__ logp, int B, int A) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  double lp = 0.0;
+  for (int a = 0; a < A; ++a) {
+    const int i = b * A + a;
+    const float sc = scale[sn == 1 ? 0 : a], bi = bias[sn == 1 ? 0 : a];
+    const double y = log_prob_y(action[i], sc, bi);
+    const double x = 0.5 * log((1.0 + y) / (1.0 - y));
+    const double ls = (double)fminf(fmaxf(lsr[i], lo), hi);
+    const double e = (x - (double)mean[i]) * exp(-ls);
+    lp += -0.5 * e * e - ls - kHalfLog2PiD - log((double)sc * (1.0 - y * y) + 1e-6);
+  }
+  logp[b] = (float)lp;
+}
+
+// dmean = g e exp(-ls);  dlog_std_raw = g (e^2 - 1) inside [ls_min, ls_max] (bounds included), 0 outside;  g = dlp[b]
+__global__ void __launch_bounds__(256) tanh_gaussian_log_prob_bwd_kernel(const float* __restrict__ mean, const float* __restrict__ lsr,
+                                                                         const float* __restrict__ action, const float* __restrict__ scale,
+                                                                         const float* __restrict__ bias, int sn, float lo, float hi,
+                                                                         const float* __restrict__ dlp, float* __restrict__ dmean,
+                                                                         float* __restrict__ dls, int B, int A) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const double g = (double)dlp[b];
+  for (int a = 0; a < A; ++a) {
+    const int i = b * A + a;
+    const float sc = scale[sn == 1 ? 0 : a], bi = bias[sn == 1 ? 0 : a];
+    const double y = log_prob_y(action[i], sc, bi);
+    const double x = 0.5 * log((1.0 + y) / (1.0 - y));
+    const float raw = lsr[i];
+    const double inv_sd = exp(-(double)fminf(fmaxf(raw, lo), hi));
+    const double e = (x - (double)mean[i]) * inv_sd;
+    dmean[i] = (float)(g * e * inv_sd);
+    dls[i] = (raw >= lo && raw <= hi) ? (float)(g * (e * e - 1.0)) : 0.f;
+  }
+}
+
+inline bool al4h(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+
+int log_prob_sizes(const char* name, int sn, float lo, float hi, int B, int A) {
+  DGVIT_CHECK_ARG(B >= 1, "%s: B=%d must be at least 1", name, B);
+  DGVIT_CHECK_ARG(A >= 1 && A <= 16, "%s: A=%d must be in [1, 16]", name, A);
+  DGVIT_CHECK_ARG((long long)B * A < (1ll << 31), "%s: B*A=%lld must be below 2^31", name, (long long)B * A);
+  DGVIT_CHECK_ARG(sn == 1 || sn == A, "%s: scale_n=%d must be 1 or A=%d", name, sn, A);
+  DGVIT_CHECK_ARG(lo <= hi, "%s: ls_min=%g must not exceed ls_max=%g", name, (double)lo, (double)hi);
+  return DGVIT_OK;
+}
+}  // namespace
+
+int tanh_gaussian_log_prob(const float* mean, const float* lsr, const float* action, const float* scale, const float* bias, int sn, float lo,
+                           float hi, float* logp, int B, int A, hipStream_t stream) {
+  DGVIT_CHECK_ARG(mean && lsr && action && scale && bias && logp,
+                  "tanh_gaussian_log_prob: mean, log_std_raw, action, scale, bias and log_prob must not be null");
+  if (int rc = log_prob_sizes("tanh_gaussian_log_prob", sn, lo, hi, B, A)) return rc;
+  DGVIT_CHECK_ARG(al4h(mean) && al4h(lsr) && al4h(action) && al4h(scale) && al4h(bias) && al4h(logp),
+                  "tanh_gaussian_log_prob: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(tanh_gaussian_log_prob_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, mean, lsr, action, scale, bias, sn, lo, hi,
+                       logp, B, A);
+  }
+  DGVIT_CHECK_LAUNCH("tanh_gaussian_log_prob");
+  return DGVIT_OK;
+}
+
+int tanh_gaussian_log_prob_backward(const float* mean, const float* lsr, const float* action, const float* scale, const float* bias, int sn,
+                                    float lo, float hi, const float* dlp, float* dmean, float* dls, int B, int A, hipStream_t stream) {
+  DGVIT_CHECK_ARG(mean && lsr && action && scale && bias && dlp && dmean && dls,
+                  "tanh_gaussian_log_prob_backward: mean, log_std_raw, action, scale, bias, d_log_prob, dmean and dlog_std_raw must not be null");
+  if (int rc = log_prob_sizes("tanh_gaussian_log_prob_backward", sn, lo, hi, B, A)) return rc;
+  DGVIT_CHECK_ARG(al4h(mean) && al4h(lsr) && al4h(action) && al4h(scale) && al4h(bias) && al4h(dlp) && al4h(dmean) && al4h(dls),
+                  "tanh_gaussian_log_prob_backward: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(tanh_gaussian_log_prob_bwd_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, mean, lsr, action, scale, bias, sn, lo,
+                       hi, dlp, dmean, dls, B, A);
+  }
+  DGVIT_CHECK_LAUNCH("tanh_gaussian_log_prob_backward");
   return DGVIT_OK;
 }

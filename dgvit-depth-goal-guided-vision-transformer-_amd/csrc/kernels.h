@@ -70,6 +70,8 @@ int sac_critic_loss(const float* q1, const float* q2, const float* reward, const
 int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, const float* log_alpha, float alpha, int with_temperature,
                    float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A, hipStream_t);
 int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t);
+int sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo, const float* q2_demo,
+                const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
 // the (B, H, W, C) frame gradient from conv1's column gradient (rows of KP floats, 25 C real taps): no ReLU mask
@@ -152,6 +154,12 @@ int tanh_gaussian_forward(const float*, const float*, const float*, const float*
                           int, int, hipStream_t);
 int tanh_gaussian_backward(const float*, const float*, const float*, const float*, int, float, float, const float*, const float*,
                            const float*, float*, float*, int, int, hipStream_t);
+// log pi(a | s) of a given action under the same policy and its gradient for mean and log_std_raw
+int tanh_gaussian_log_prob(const float* mean, const float* log_std_raw, const float* action, const float* scale, const float* bias, int scale_n,
+                           float ls_min, float ls_max, float* log_prob, int B, int A, hipStream_t);
+int tanh_gaussian_log_prob_backward(const float* mean, const float* log_std_raw, const float* action, const float* scale, const float* bias,
+                                    int scale_n, float ls_min, float ls_max, const float* d_log_prob, float* dmean, float* dlog_std_raw, int B,
+                                    int A, hipStream_t);
 // block.hip: two launches per transformer block for small batches (no-grad forward), cross-workgroup sums inside the launches
 bool block_path_supports(int B, int N, int D, int H, int dh, int M);
 long long block_path_slab_floats(int B, int N, int D, int H, int M);

@@ -5,6 +5,8 @@
 //                     does: the gamma^m of an n-step batch
 //   sac_actor_loss  : policy_loss = mean(alpha logp - min(q1pi, q2pi)), alpha_loss = -log_alpha mean(logp + target_entropy), and
 //                     d logp | dq1pi | dq2pi and d log_alpha for unit upstream gradients
+//   sac_bc_loss     : the demonstration term of the actor loss: a masked, optionally Q-filtered mean of (pred - action)^2 or
+//                     of -log_prob over the `used` rows it applies to, `used` counted on the device; d pred for a unit upstream gradient
 //   sac_scale_grads : dst = *scale_dev * src, the backward of either loss for the 0-d upstream gradient autograd hands over
 // The two loss kernels are ONE workgroup of 256 threads: B * A is at most 2^20 elements of a few flops each, and one workgroup needs no
 // second launch, no atomics and no counters for its sums.  Every thread walks the elements i = tid, tid + 256, ... (row b = i / A), sums
@@ -121,6 +123,75 @@ __global__ void __launch_bounds__(256) sac_actor_loss_kernel(const float* __rest
   }
 }
 
+// the weight m_b f_b of row b in the demonstration loss: the mask (fp32 weights, or the bytes of a bool tensor) times the Q-filter's
+// decision, mean_a min(q1_demo, q2_demo) > mean_a min(q1_pi, q2_pi), strict; both means summed in double over a = 0 .. A - 1
+__device__ __forceinline__ double bc_row_weight(const void* __restrict__ mask, int mask_u8, const float* __restrict__ q1d,
+                                                const float* __restrict__ q2d, const float* __restrict__ q1p, const float* __restrict__ q2p,
+                                                int b, int A) {
+  double w = 1.0;
+  if (mask) w = mask_u8 ? (double)(static_cast<const unsigned char*>(mask)[b] != 0) : (double)static_cast<const float*>(mask)[b];
+  if (q1d) {
+    double sd = 0.0, sp = 0.0;
+    for (int a = 0; a < A; ++a) {
+      const int i = b * A + a;
+      sd += (double)fminf(q1d[i], q2d[i]);
+      sp += (double)fminf(q1p[i], q2p[i]);
+    }
+    if (!(sd / (double)A > sp / (double)A)) w = 0.0;
+  }
+  return w;
+}
+
+// The demonstration term: loss = sum_b w_b l_b / used, used = sum_b w_b, w_b = bc_row_weight; l_b = mean_a (pred - action)^2,
+// or -pred_b with nll (pred is then the log-density, B values).  thread = rows b = tid, tid + 256, ...; the two sums meet as block_sum
+// does, every thread reads them back, and the second walk writes the gradients for a unit upstream gradient, which need 1 / used.
+// used == 0 gives loss 0 and zero gradients; a row of weight 0 adds nothing, whatever its l_b.
+__global__ void __launch_bounds__(256) sac_bc_loss_kernel(const float* __restrict__ pred, const float* __restrict__ action,
+                                                          const void* __restrict__ mask, int mask_u8, const float* __restrict__ q1d,
+                                                          const float* __restrict__ q2d, const float* __restrict__ q1p,
+                                                          const float* __restrict__ q2p, int nll, float* __restrict__ out,
+                                                          float* __restrict__ grads, int B, int A) {
+  __shared__ double wave_sum[2][4];
+  const double inv_a = 1.0 / (double)A;
+  double acc = 0.0, cnt = 0.0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const double w = bc_row_weight(mask, mask_u8, q1d, q2d, q1p, q2p, b, A);
+    if (w == 0.0) continue;
+    double l;
+    if (nll) {
+      l = -(double)pred[b];
+    } else {
+      double s = 0.0;
+      for (int a = 0; a < A; ++a) {
+        const double d = (double)pred[b * A + a] - (double)action[b * A + a];
+        s += d * d;
+      }
+      l = s * inv_a;
+    }
+    acc += w * l;
+    cnt += w;
+  }
+  const double tot = block_sum(acc, wave_sum[0]);
+  const double used = block_sum(cnt, wave_sum[1]);
+  const double inv_used = used > 0.0 ? 1.0 / used : 0.0;
+  if (threadIdx.x == 0) {
+    out[0] = (float)(tot * inv_used);
+    out[1] = (float)used;
+  }
+  if (!grads) return;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const double w = bc_row_weight(mask, mask_u8, q1d, q2d, q1p, q2p, b, A) * inv_used;
+    if (nll) {
+      grads[b] = w == 0.0 ? 0.f : (float)(-w);
+    } else {
+      for (int a = 0; a < A; ++a) {
+        const int i = b * A + a;
+        grads[i] = w == 0.0 ? 0.f : (float)(2.0 * w * inv_a * ((double)pred[i] - (double)action[i]));
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(256) sac_scale_grads_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n,
                                                               const float* __restrict__ scale_dev) {
   const float s = *scale_dev;
@@ -172,6 +243,31 @@ int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, 
                        losses, grads, dlog_alpha, B, A);
   }
   DGVIT_CHECK_LAUNCH("sac_actor_loss");
+  return DGVIT_OK;
+}
+
+int sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo, const float* q2_demo,
+                const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A, hipStream_t stream) {
+  DGVIT_CHECK_ARG(pred && out, "sac_bc_loss: pred and out must not be null");
+  DGVIT_CHECK_ARG(nll == 0 || nll == 1, "sac_bc_loss: nll=%d must be 0 or 1", nll);
+  DGVIT_CHECK_ARG(mask_u8 == 0 || mask_u8 == 1, "sac_bc_loss: mask_u8=%d must be 0 or 1", mask_u8);
+  DGVIT_CHECK_ARG(nll || action, "sac_bc_loss: action must not be null (it is only unused with nll=1)");
+  DGVIT_CHECK_ARG(B >= 1, "sac_bc_loss: B=%d must be at least 1", B);
+  DGVIT_CHECK_ARG(A >= 1 && A <= SAC_MAX_ACTIONS, "sac_bc_loss: A=%d must be in [1, %d]", A, SAC_MAX_ACTIONS);
+  DGVIT_CHECK_ARG((long long)B * A <= SAC_MAX_ELEMS, "sac_bc_loss: B*A=%lld must be at most %lld", (long long)B * A, SAC_MAX_ELEMS);
+  DGVIT_CHECK_ARG(!nll || A == 1, "sac_bc_loss: nll=1 takes one log-density per row, A=%d must be 1", A);
+  const int nq = (q1_demo != nullptr) + (q2_demo != nullptr) + (q1_pi != nullptr) + (q2_pi != nullptr);
+  DGVIT_CHECK_ARG(nq == 0 || nq == 4, "sac_bc_loss: the filter needs q1_demo, q2_demo, q1_pi and q2_pi together (%d of 4 given)", nq);
+  DGVIT_CHECK_ARG(!nll || nq == 0, "sac_bc_loss: the Q-filter belongs to the squared-error loss, not to nll=1");
+  DGVIT_CHECK_ARG(al4p(pred) && al4p(action) && (mask_u8 || al4p(mask)) && al4p(q1_demo) && al4p(q2_demo) && al4p(q1_pi) && al4p(q2_pi) &&
+                      al4p(out) && al4p(grads),
+                  "sac_bc_loss: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(sac_bc_loss_kernel, dim3(1), dim3(256), 0, stream, pred, action, mask, mask_u8, q1_demo, q2_demo, q1_pi, q2_pi, nll, out,
+                       grads, B, A);
+  }
+  DGVIT_CHECK_LAUNCH("sac_bc_loss");
   return DGVIT_OK;
 }
 

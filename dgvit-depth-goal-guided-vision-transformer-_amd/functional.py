@@ -510,6 +510,72 @@ def tanh_gaussian_sample(mean, log_std_raw, eps, scale, bias, ls_min, ls_max):
     return _TanhGaussian.apply(mean, log_std_raw, eps, scale, bias, ls_min, ls_max)
 
 
+class _TanhGaussianLogProb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, log_std_raw, action, scale, bias, lo, hi):
+        lib = _lib.load()
+        mean, lsr, action = _dev(mean, "mean"), _dev(log_std_raw, "log_std"), _dev(action.detach(), "action")
+        scale, bias = _dev(scale.reshape(-1), "action_scale"), _dev(bias.reshape(-1), "action_bias")
+        B, A = mean.shape
+        logp = torch.empty(B, 1, dtype=torch.float32, device=mean.device)
+        with torch.cuda.device(mean.device):
+            rc = lib.dgvit_tanh_gaussian_log_prob(_ptr(mean), _ptr(lsr), _ptr(action), _ptr(scale), _ptr(bias), scale.numel(), float(lo),
+                                                  float(hi), _ptr(logp), B, A, _stream())
+        _lib.check(rc, "dgvit_tanh_gaussian_log_prob")
+        ctx.lohi = (float(lo), float(hi))
+        ctx.save_for_backward(mean, lsr, action, scale, bias)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlp):
+        lib = _lib.load()
+        mean, lsr, action, scale, bias = ctx.saved_tensors
+        B, A = mean.shape
+        dlp = _dev(dlp, "d_log_prob")
+        dmean, dls = torch.empty_like(mean), torch.empty_like(mean)
+        with torch.cuda.device(mean.device):
+            rc = lib.dgvit_tanh_gaussian_log_prob_backward(_ptr(mean), _ptr(lsr), _ptr(action), _ptr(scale), _ptr(bias), scale.numel(),
+                                                           ctx.lohi[0], ctx.lohi[1], _ptr(dlp), _ptr(dmean), _ptr(dls), B, A, _stream())
+        _lib.check(rc, "dgvit_tanh_gaussian_log_prob_backward")
+        return dmean, dls, None, None, None, None, None
+
+
+LOG_PROB_CLIP = 1.0 - 1e-6       # heads.hip: kLogProbClip
+
+
+def tanh_gaussian_log_prob(mean, log_std_raw, action, scale, bias, ls_min, ls_max):
+    """``log pi(action | s)``, (B, 1), of the tanh-Gaussian policy whose head outputs are ``mean`` and the un-clamped ``log_std_raw`` (both
+    (B, A)), for a GIVEN ``action`` (B, A) -- a stored demonstration, not the policy's own draw:
+
+        y  = clamp((action - bias) / scale, -(1 - 1e-6), 1 - 1e-6);   x = atanh(y)
+        ls = clamp(log_std_raw, ls_min, ls_max);   e = (x - mean) exp(-ls)
+        log_prob = sum_a [ -e^2 / 2 - ls - log(sqrt(2 pi)) - log(scale (1 - y^2) + 1e-6) ]
+
+    the density ``tanh_gaussian_sample`` reports, at ``y``: an action at or beyond the bound gives the finite value at the clip.  One HIP
+    launch forward and one backward, in double from the fp32 inputs.  Differentiable in ``mean`` and ``log_std_raw`` (zero where the raw
+    value lies outside [ls_min, ls_max]); nothing flows to ``action``, ``scale`` or ``bias``.  An empty batch takes torch ops."""
+    if not all(isinstance(t, torch.Tensor) for t in (mean, log_std_raw, action, scale, bias)):
+        raise TypeError("tanh_gaussian_log_prob: mean, log_std_raw, action, scale and bias must be tensors")
+    if mean.dim() != 2 or log_std_raw.shape != mean.shape or action.shape != mean.shape:
+        raise ValueError(f"tanh_gaussian_log_prob: mean, log_std_raw and action must be (B, A) alike, got {tuple(mean.shape)}, "
+                         f"{tuple(log_std_raw.shape)} and {tuple(action.shape)}")
+    A = mean.shape[1]
+    if not 1 <= A <= 16:
+        raise ValueError(f"tanh_gaussian_log_prob: A={A} must be in [1, 16]")
+    if scale.numel() not in (1, A) or bias.numel() != scale.numel():
+        raise ValueError(f"tanh_gaussian_log_prob: scale and bias must hold 1 or A={A} values alike, got {scale.numel()} and {bias.numel()}")
+    if not float(ls_min) <= float(ls_max):
+        raise ValueError(f"tanh_gaussian_log_prob: ls_min={ls_min!r} must not exceed ls_max={ls_max!r}")
+    if mean.shape[0] == 0:
+        for t, name in ((mean, "mean"), (log_std_raw, "log_std"), (action, "action")):
+            _dev(t, name)
+        y = ((action.detach() - bias.to(mean.device)) / scale.to(mean.device)).clamp(-LOG_PROB_CLIP, LOG_PROB_CLIP)
+        ls = torch.clamp(log_std_raw, min=ls_min, max=ls_max)
+        e = (torch.atanh(y) - mean) * torch.exp(-ls)
+        return (-0.5 * e * e - ls - 0.9189385332046727 - torch.log(scale.to(mean.device) * (1 - y * y) + 1e-6)).sum(1, keepdim=True)
+    return _TanhGaussianLogProb.apply(mean, log_std_raw, action, scale, bias, ls_min, ls_max)
+
+
 # ------------------------------------------------------------------------------------------------ operator-level helpers
 def op_gemm(layout, epilogue, A, B, M, N, K, bias=None, res=None, aux=None, want_c2=False):
     lib = _lib.load()

@@ -17,6 +17,8 @@ stores such a step from device tensors without visiting the host.  ``shared_next
 ``next_obs`` is its successor's ``obs`` row, and only the frames without a successor slot are kept apart.
 ``sample(..., frame_stack=K)`` returns channel-last stacks of the last K frames of each slot's episode, built at sample time by the same
 walk run backward, and ``FrameStack`` keeps that stack on the acting side: the ring never stores a frame twice.
+``sample_mixed`` draws one batch from several rings -- the agent's and a demonstration ring -- each ring's launches writing straight into
+its row range of the shared tensors, and ``update_priorities_mixed`` routes the TD errors back.
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -142,6 +144,25 @@ def _load_options(priorities, restore_rng):
     if restore_rng is not None and not isinstance(restore_rng, (bool, np.bool_)):
         raise ValueError(f"restore_rng must be None, True or False, got {restore_rng!r}")
     return priorities, None if restore_rng is None else bool(restore_rng)
+
+
+class _Rows:
+    """Where one ring's launches of a ``sample_mixed`` call write: rows [r0, r0 + n) of tensors of ``total`` rows that all rings of the
+    call share, one per output name, allocated when the first ring asks for it."""
+
+    def __init__(self, total, device):
+        self.total, self.device, self.r0, self.bufs = total, device, 0, {}
+
+    def empty(self, name, n, tail, dtype):
+        buf = self.bufs.get(name)
+        if buf is None:
+            buf = self.bufs[name] = torch.empty(self.total, *tail, dtype=dtype, device=self.device)
+        return buf[self.r0:self.r0 + n]
+
+
+def _empty(into, name, n, tail, dtype, device):
+    """the (n, *tail) tensor an output's launch writes: a fresh one, or this ring's rows of the shared one (``_Rows``)"""
+    return torch.empty(n, *tail, dtype=dtype, device=device) if into is None else into.empty(name, n, tail, dtype)
 
 
 class DeviceReplayBuffer:
@@ -749,7 +770,7 @@ class DeviceReplayBuffer:
 
     def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None, random_shift: int = 0,
                return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
-               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               frame_stack: Optional[int] = None, *, _into: Optional[_Rows] = None) -> Dict[str, torch.Tensor]:
         """Uniform sample with replacement -> dict of DEVICE tensors shaped like the reference's batch
         (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip.
 
@@ -799,7 +820,11 @@ class DeviceReplayBuffer:
             self.track_episodes()
         lib = _lib.load()
         u8 = self.frame_dtype is torch.uint8
-        idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
+        into = _into                             # sample_mixed's hook: every output goes to this ring's rows of the shared tensors
+        if into is None:
+            idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
+        else:
+            idx = self._indices_into(into, batch_size, indices)
         B = idx.numel()
         st = _stream()
         out = {}
@@ -810,30 +835,30 @@ class DeviceReplayBuffer:
             walk = tables = None
             if K is not None:                    # the stacks' row tables need the n-step tails: the walk goes first
                 if n_step is not None:
-                    walk = self._walk(idx, n_step, gamma)
+                    walk = self._walk(idx, n_step, gamma, into)
                 tables = self._stack_rows(idx, None if walk is None else walk["tail"], K)
             for k, n in self.fields.items():
                 r = self.rows[k]
                 if n_step is not None and k in ("rew", "next_pobs", "done"):
                     if k == "rew":               # (fields are in the reference's order: obs, pobs and act are out, next_obs is to come)
                         if walk is None:
-                            walk = self._walk(idx, n_step, gamma)
+                            walk = self._walk(idx, n_step, gamma, into)
                         at = walk.pop("tail")
                     out[k] = walk.pop(k)
                     continue
                 if K is not None and k in FRAME_FIELDS:
-                    shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if pad and return_shifts else None
-                    out[k] = self._gather_stack(k, tables[k], K, pad, shifts)
+                    shifts = _empty(into, k + "_shift", B, (2,), torch.int32, self.device) if pad and return_shifts else None
+                    out[k] = self._gather_stack(k, tables[k], K, pad, shifts, into)
                     if shifts is not None:
                         out[k + "_shift"] = shifts
                     continue
-                buf = torch.empty(B, r, dtype=torch.float32, device=self.device)
+                buf = _empty(into, k, B, (r,), torch.float32, self.device)
                 src, nrows, rows_at = self.store.get(k), self.size, at
                 if k == "next_obs" and self.shared_next_obs:   # the same gathers over the arena, at the rows next_row names
                     src, nrows, rows_at = self.arena, self.arena_rows, torch.empty(B, dtype=torch.int64, device=self.device)
                     _lib.check(lib.dgvit_ring_next_rows(_ptr(self.next_row), _ptr(at), _ptr(rows_at), B, self.size, st), "dgvit_ring_next_rows")
                 if pad and k in FRAME_FIELDS:
-                    shifts = torch.empty(B, 2, dtype=torch.int32, device=self.device) if return_shifts else None
+                    shifts = _empty(into, k + "_shift", B, (2,), torch.int32, self.device) if return_shifts else None
                     _gather_shift(src, rows_at, buf, shifts, self.shapes[k], nrows, pad, int(k == "next_obs"), self.shift_seed)
                     if return_shifts:
                         out[k + "_shift"] = shifts
@@ -844,12 +869,26 @@ class DeviceReplayBuffer:
                     rc = lib.dgvit_gather_rows(_ptr(src), _ptr(rows_at), _ptr(buf), B, r, nrows, st)
                     _lib.check(rc, "dgvit_gather_rows")
                 out[k] = buf[:, :n].reshape(B, *self.shapes[k])
-        if return_shifts and not pad:
+        if return_shifts and not pad and into is None:
             out["obs_shift"], out["next_obs_shift"] = (torch.zeros(B, 2, dtype=torch.int32, device=self.device) for _ in range(2))
         if n_step is not None:
             out.update(walk)                     # discount, steps
         out["indexes"] = idx
         return out
+
+    def _indices_into(self, into, batch_size, indices):
+        """the slots of this ring's rows of a ``sample_mixed`` batch, in the shared ``indexes``: the draw ``sample_indices`` makes, written
+        there by the draw itself, or the given ``indices`` copied there (the prioritized draw has written them already)"""
+        if indices is None:
+            if self.stored == 0:
+                raise RuntimeError("cannot sample from an empty buffer")
+            idx = into.empty("indexes", int(batch_size), (), torch.int64)
+            return torch.randint(0, self.stored, (int(batch_size),), generator=self.gen, out=idx)
+        given = indices.to(self.device, torch.int64).contiguous()
+        idx = into.empty("indexes", given.numel(), (), torch.int64)
+        if idx.data_ptr() != given.data_ptr():
+            idx.copy_(given.reshape(-1))
+        return idx
 
     def _stack_rows(self, idx, tail, K):
         """the one dgvit_ring_stack_rows launch of a stacked sample: {field: (B, K) int64 rows of its K frames}; ``tail`` the n-step
@@ -864,7 +903,7 @@ class DeviceReplayBuffer:
         _lib.check(rc, "dgvit_ring_stack_rows")
         return rows
 
-    def _gather_stack(self, k, rows, K, pad, shifts):
+    def _gather_stack(self, k, rows, K, pad, shifts, into=None):
         """frame field k of a stacked sample, (B, H, W, K): dgvit_gather_stack_frames, or its shifted form, over the obs matrix and --
         for the newest channel of next_obs -- the next_obs matrix or the arena"""
         B, cols, (H, W) = rows.shape[0], self.fields[k], self.shapes[k]
@@ -874,7 +913,7 @@ class DeviceReplayBuffer:
         if k == "next_obs":
             src1, nrows1 = (self.arena, self.arena_rows) if self.shared_next_obs else (self.store["next_obs"], self.size)
         row, ld = _al4(cols * K), self.row_bytes if u8 else self.rows["obs"]
-        buf = torch.empty(B, row, dtype=torch.float32, device=self.device)
+        buf = _empty(into, k, B, (row,), torch.float32, self.device)
         lib = _lib.load()
         if pad:
             seed_dev = self.shift_seed if isinstance(self.shift_seed, torch.Tensor) else None
@@ -886,15 +925,17 @@ class DeviceReplayBuffer:
             rc = lib.dgvit_gather_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), B, cols, K, int(u8), ld, row, self.size, nrows1,
                                                _stream())
             _lib.check(rc, "dgvit_gather_stack_frames")
+        if into is not None:                     # sample_mixed shapes the shared tensor, once for all rings
+            return buf
         return buf[:, :cols * K].reshape(B, H, W, K).contiguous()   # a copy only where H W K is no multiple of 4: the row padding goes
 
-    def _walk(self, idx, n_step, gamma):
+    def _walk(self, idx, n_step, gamma, into=None):
         """the one dgvit_nstep_walk launch of an n-step sample (dgvit_nstep_walk_strided on a ring of several environments): rew, done,
         next_pobs, discount, steps and the tail slots"""
         B, dev = idx.numel(), self.device
-        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
-        ret, done, disc, small = f32(B), f32(B), f32(B), f32(B, self.rows["next_pobs"])
-        steps, tail = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+        f32 = lambda name, *tail: _empty(into, name, B, tail, torch.float32, dev)   # noqa: E731
+        ret, done, disc, small = f32("rew"), f32("done"), f32("discount"), f32("next_pobs", self.rows["next_pobs"])
+        steps, tail = _empty(into, "steps", B, (), torch.int32, dev), torch.empty(B, dtype=torch.int64, device=dev)
         ring = (_ptr(self.store["rew"]), self.rows["rew"], _ptr(self.store["done"]), self.rows["done"], _ptr(self.episode_flags),
                 _ptr(self.store["next_pobs"]), self.rows["next_pobs"], _ptr(idx), B, self.size)
         outs = (n_step, gamma, _ptr(ret), _ptr(done), _ptr(disc), _ptr(small), _ptr(steps), _ptr(tail), _stream())
@@ -1006,7 +1047,7 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             _lib.check(_lib.load().dgvit_per_init(_ptr(self.tree), self.size, _stream()), "dgvit_per_init")
 
     def draw(self, batch_size: int, beta: float = 0.4, stratified: bool = False,
-             uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             uniforms: Optional[torch.Tensor] = None, *, _into: Optional[_Rows] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The index draw alone: ((B,) int64 indices, (B, 1) fp32 importance weights).  ``uniforms`` ((B,) fp32 on the device, values in
         [0, 1]) makes the draw reproducible; absent, it comes from ``self.gen``.  ``stratified`` draws sample j from the j-th of B equal
         slices of the total priority."""
@@ -1022,8 +1063,8 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or uniforms.device != self.store["obs"].device
               or uniforms.numel() != B or not uniforms.is_contiguous()):
             raise ValueError(f"uniforms must be a contiguous fp32 tensor of {B} values on {self.store['obs'].device}")
-        idx = torch.empty(B, dtype=torch.int64, device=self.device)
-        weights = torch.empty(B, 1, dtype=torch.float32, device=self.device)
+        idx = _empty(_into, "indexes", B, (), torch.int64, self.device)
+        weights = _empty(_into, "weights", B, (1,), torch.float32, self.device)
         with torch.cuda.device(self.device):
             rc = _lib.load().dgvit_per_sample(_ptr(self.tree), self.size, _ptr(uniforms), B, int(bool(stratified)), beta, _ptr(idx),
                                               _ptr(weights), _stream())
@@ -1032,14 +1073,14 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
 
     def sample(self, batch_size: int, beta: float = 0.4, stratified: bool = False, uniforms: Optional[torch.Tensor] = None,
                random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
-               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               frame_stack: Optional[int] = None, *, _into: Optional[_Rows] = None) -> Dict[str, torch.Tensor]:
         """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift``,
         ``return_shifts``, ``n_step``, ``gamma`` and ``frame_stack`` as there; the draw and the weights do not depend on them).  The base's dict plus
         ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor, the start slots of an n-step sample."""
         _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
-        idx, weights = self.draw(batch_size, beta, stratified, uniforms)
+        idx, weights = self.draw(batch_size, beta, stratified, uniforms, _into=_into)
         out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma,
-                             frame_stack=frame_stack)
+                             frame_stack=frame_stack, _into=_into)
         out["weights"] = weights
         return out
 
@@ -1081,6 +1122,165 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
     def max_priority(self) -> torch.Tensor:
         """the largest leaf ever written (0-d device tensor; 1 at first, never falls): what a newly stored transition gets"""
         return self.tree[0].clone()
+
+
+# ---- one batch from several rings (DESIGN 3.46)
+MIXED_MAX_RINGS = 4
+
+
+class MixedBatch(dict):
+    """``sample_mixed``'s result: ``sample()``'s dict with ``source`` and ``counts``; ``rings`` are the rings of the call, in list order,
+    which is how ``update_priorities_mixed`` finds them"""
+    rings = ()
+
+
+def _mixed_pairs(pairs):
+    """``pairs`` of sample_mixed after its checks -> [(ring, n)]: host-only, runs before anything is launched"""
+    if not isinstance(pairs, (list, tuple)) or not 1 <= len(pairs) <= MIXED_MAX_RINGS:
+        raise ValueError(f"sample_mixed: pairs must be a list of 1 to {MIXED_MAX_RINGS} (ring, n) pairs, got {pairs!r}")
+    out = []
+    for i, p in enumerate(pairs):
+        if not isinstance(p, (list, tuple)) or len(p) != 2:
+            raise ValueError(f"sample_mixed: pairs[{i}] must be (ring, n), got {p!r}")
+        ring, n = p
+        if not isinstance(ring, DeviceReplayBuffer):
+            raise ValueError(f"sample_mixed: pairs[{i}][0] must be a DeviceReplayBuffer, got {type(ring).__name__}")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0:
+            raise ValueError(f"sample_mixed: pairs[{i}][1], the ring's share of the batch, must be an int >= 0, got {n!r}")
+        if any(ring is r for r, _ in out):
+            raise ValueError(f"sample_mixed: pairs[{i}] names a ring that the list holds already; give a ring once, with its whole share")
+        out.append((ring, int(n)))
+    if sum(n for _, n in out) < 1:
+        raise ValueError("sample_mixed: the shares add up to 0 rows; at least one row must be drawn")
+    first = out[0][0]
+    for i, (ring, _) in enumerate(out[1:], 1):
+        for what, a, b in (("obs_shape", first.shapes["obs"], ring.shapes["obs"]), ("pstate_dim", first.fields["pobs"], ring.fields["pobs"]),
+                           ("act_dim", first.fields["act"], ring.fields["act"]), ("device", first.store["obs"].device, ring.store["obs"].device)):
+            if a != b:
+                raise ValueError(f"sample_mixed: the rings must agree in {what}: {a!r} in pairs[0], {b!r} in pairs[{i}]")
+    return out
+
+
+def _per_ring(name, value, pairs, wanted):
+    """a keyword of sample_mixed with one entry per pair (``uniforms``, ``indices``) after its checks -> list; ``wanted(ring)`` says which
+    rings may have an entry"""
+    if value is None:
+        return [None] * len(pairs)
+    if not isinstance(value, (list, tuple)) or len(value) != len(pairs):
+        raise ValueError(f"sample_mixed: {name} must be None or a list with one entry per pair ({len(pairs)}), got {type(value).__name__}"
+                         + (f" of {len(value)}" if isinstance(value, (list, tuple)) else ""))
+    for i, ((ring, _), v) in enumerate(zip(pairs, value)):
+        if v is not None and not wanted(ring):
+            kind = "prioritized" if isinstance(ring, PrioritizedDeviceReplayBuffer) else "uniform"
+            raise ValueError(f"sample_mixed: {name}[{i}] must be None: pairs[{i}] is a {kind} ring, which takes no {name}")
+        if v is not None and not torch.is_tensor(v):
+            raise ValueError(f"sample_mixed: {name}[{i}] must be None or a tensor, got {type(v).__name__}")
+    out = []
+    for i, ((_, n), v) in enumerate(zip(pairs, value)):
+        if n == 0:                               # a skipped ring reads nothing, its entry included
+            v = None
+        elif v is not None and v.numel() != n:   # the row range is fixed by the share: sample() would take its B from the entry
+            raise ValueError(f"sample_mixed: {name}[{i}] must hold {n} values, one per row of pairs[{i}]'s share, got {v.numel()}")
+        elif v is not None and name == "indices" and (v.dtype.is_floating_point or v.dtype.is_complex or v.dtype == torch.bool):
+            raise ValueError(f"sample_mixed: indices[{i}] must be an integer tensor, got {v.dtype}")
+        out.append(v)
+    return out
+
+
+def sample_mixed(pairs, *, indices=None, random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None,
+                 gamma: float = 0.99, frame_stack: Optional[int] = None, beta: float = 0.4, stratified: bool = False,
+                 uniforms=None) -> MixedBatch:
+    """ONE batch drawn from several rings -- the agent's and a demonstration ring, say (DESIGN 3.46)::
+
+        batch = sample_mixed([(agent_ring, 24), (demo_ring, 8)], random_shift=4, n_step=3, gamma=0.99, frame_stack=4, beta=0.4)
+        update_priorities_mixed(batch, td)
+
+    ``pairs`` is a list of 1 to 4 ``(ring, n_i)``, n_i >= 0 rows from that ring, at least one row in all.  A ring with n_i == 0 is skipped:
+    it draws nothing, launches nothing and its generator does not move (a demonstration share that a schedule has taken to zero).  The
+    rings must agree in ``obs_shape``, ``pstate_dim``, ``act_dim`` and device, and may differ in ``size``, ``frame_dtype``,
+    ``shared_next_obs``, ``num_envs`` and in being uniform or prioritized; a mismatch, something that is no ring, a negative or non-integer
+    n_i or the same ring twice raises ValueError before anything is launched, and an empty ring with n_i > 0 raises what ``sample`` raises.
+
+    The keywords are ``sample()``'s and go to every ring's call; ``beta``, ``stratified`` and ``uniforms`` go to the prioritized rings
+    only.  ``uniforms`` is then a list with one entry per pair, None where the ring is not prioritized (or where its draw is to come from
+    its generator); ``indices`` is likewise a list with one entry per pair or None, an entry None where the ring draws for itself --
+    a prioritized ring always does, so its entry must be None.  An entry holds exactly n_i values (integers for ``indices``), else
+    ValueError before anything is launched: the row ranges are fixed by the shares.  The entry of a ring with n_i == 0 is not read.
+
+    The result is ``sample()``'s dict, every key ONE ``(B, ...)`` tensor, B = sum n_i, ring 0's rows first, then ring 1's, and so on, plus
+    ``source``, (B,) int32, the row's position in ``pairs``, and ``counts``, the tuple of n_i (a host value).  ``indexes`` are slots of
+    the row's own ring.  ``weights`` is there when any ring of the list is prioritized: each prioritized ring's own importance weights,
+    normalised within that ring as its ``sample`` does (by that ring's smallest leaf, not across rings), and 1 for the rows of uniform
+    rings.  ``obs_shift`` / ``next_obs_shift``, ``discount`` and ``steps`` are there for all rows or for none, as the keywords say.
+
+    The contract: ring i's rows of every key equal, bit for bit, what ``ring_i.sample(n_i, ...)`` returns from the same generator state,
+    shift seed and keywords; the seeds of ``random_shift`` are drawn in list order.  Each ring issues the launches of its own ``sample``
+    and no other, and they write straight into the ring's row range of the shared tensors: a frame is written once, there is no
+    ``torch.cat`` and no staging copy.  What is added is one small fill per ring for ``source``, one for ``weights`` when uniform and
+    prioritized rings mix, a copy of a given ``indices`` entry into ``indexes``, and the one trailing ``.contiguous()`` of a stack
+    whose H W K is no multiple of 4, on the whole tensor.  The row ranges are host constants and nothing synchronises, so the call
+    works inside ``GraphedStep`` under ``sample()``'s own conditions (``uniforms`` for prioritized rings, tracked episodes)."""
+    pairs = _mixed_pairs(pairs)
+    first = pairs[0][0]
+    n_step, gamma, K = _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
+    pad, beta = _shift_pad(random_shift, first.shapes["obs"], "random_shift"), _unit("beta", beta)
+    per = [isinstance(ring, PrioritizedDeviceReplayBuffer) for ring, _ in pairs]
+    uniforms = _per_ring("uniforms", uniforms, pairs, lambda ring: isinstance(ring, PrioritizedDeviceReplayBuffer))
+    indices = _per_ring("indices", indices, pairs, lambda ring: not isinstance(ring, PrioritizedDeviceReplayBuffer))
+    for ring, n in pairs:
+        if n and ring.stored == 0:
+            raise RuntimeError("cannot sample from an empty buffer")
+    total, dev = sum(n for _, n in pairs), first.device
+    into = _Rows(total, dev)
+    source = torch.empty(total, dtype=torch.int32, device=dev)
+    if any(per) and any(n and not p for (_, n), p in zip(pairs, per)):        # rows of uniform rings: 1, the rest is overwritten
+        into.bufs["weights"] = torch.ones(total, 1, dtype=torch.float32, device=dev)
+    common = dict(random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma, frame_stack=K)
+    for i, (ring, n) in enumerate(pairs):
+        if n == 0:
+            continue
+        source[into.r0:into.r0 + n].fill_(i)
+        if per[i]:
+            ring.sample(n, beta=beta, stratified=stratified, uniforms=uniforms[i], _into=into, **common)
+        else:
+            ring.sample(n, indices=indices[i], _into=into, **common)
+        into.r0 += n
+    out, bufs = MixedBatch(), into.bufs
+    for k, cols in first.fields.items():
+        buf = bufs[k]
+        if K is not None and k in FRAME_FIELDS:
+            out[k] = buf[:, :cols * K].reshape(total, *first.shapes[k], K).contiguous()     # a copy only where H W K is no multiple of 4
+        elif n_step is not None and k in ("rew", "done"):
+            out[k] = buf.view(total, 1)
+        else:
+            out[k] = buf[:, :cols].reshape(total, *first.shapes[k])
+        if k in FRAME_FIELDS and return_shifts:
+            out[k + "_shift"] = bufs[k + "_shift"] if pad else torch.zeros(total, 2, dtype=torch.int32, device=dev)
+    if n_step is not None:
+        out["discount"], out["steps"] = bufs["discount"].view(total, 1), bufs["steps"]
+    out["indexes"] = bufs["indexes"]
+    if "weights" in bufs:
+        out["weights"] = bufs["weights"]
+    out["source"], out["counts"] = source, tuple(n for _, n in pairs)
+    out.rings = tuple(ring for ring, _ in pairs)
+    return out
+
+
+def update_priorities_mixed(batch: MixedBatch, priorities: torch.Tensor) -> None:
+    """``update_priorities`` for a ``sample_mixed`` batch: ``priorities`` ((B,) or (B, 1) fp32 on the device, typically
+    ``critic_loss(...).td``) is cut into the rings' row ranges, and each prioritized ring with rows in the batch takes its range with its
+    own ``indexes``; uniform rings and rings with a share of 0 are skipped.  The ranges are host constants: nothing synchronises."""
+    if not isinstance(batch, MixedBatch) or len(batch.rings) != len(batch.get("counts", ())):
+        raise ValueError("update_priorities_mixed: batch must be what sample_mixed returned")
+    total = sum(batch["counts"])
+    if not torch.is_tensor(priorities) or tuple(priorities.shape) not in ((total,), (total, 1)):
+        got = tuple(priorities.shape) if torch.is_tensor(priorities) else type(priorities).__name__
+        raise ValueError(f"update_priorities_mixed: priorities must be ({total},) or ({total}, 1), one per row of the batch, got {got}")
+    flat, r0 = priorities.reshape(-1), 0
+    for ring, n in zip(batch.rings, batch["counts"]):
+        if n and isinstance(ring, PrioritizedDeviceReplayBuffer):
+            ring.update_priorities(batch["indexes"][r0:r0 + n], flat[r0:r0 + n])
+        r0 += n
 
 
 def _stack_args(num_envs, obs_shape, frames):

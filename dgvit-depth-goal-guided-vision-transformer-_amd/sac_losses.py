@@ -8,6 +8,12 @@ prioritized replay takes back, the actor loss and the temperature loss -- as one
     policy_loss.backward(); actor_opt.step()
     alpha_loss.backward(); alpha_opt.step()          # FlatAdam([log_alpha]); log_alpha.grad is a (1,) fp32 tensor
 
+Learning from demonstrations: ``bc_loss`` and ``nll_loss`` are the demonstration term of the actor loss over the rows of a
+``replay.sample_mixed`` batch that came from the demonstration ring, normalised on the device by how many rows that is:
+
+    bc = bc_loss(pi, batch["act"], mask=batch["source"] == 1)            # BCLoss(loss, used)
+    (policy_loss + lam * bc.loss).backward()
+
 The temperature is either the float ``alpha=`` or ``exp(log_alpha[0])`` read from device memory when the kernel runs (``log_alpha=``, a
 one-element fp32 device tensor): nothing here synchronises with the host, and a step captured by ``GraphedStep`` follows a ``log_alpha``
 that an optimiser changes between replays.  fp32 tensors on a ROCm device only; there is no CPU path.
@@ -22,6 +28,7 @@ from .functional import _dev, _ptr, _stream
 
 CriticLoss = namedtuple("CriticLoss", ["loss", "td", "target"])
 ActorLoss = namedtuple("ActorLoss", ["policy_loss", "alpha_loss"])
+BCLoss = namedtuple("BCLoss", ["loss", "used"])
 
 MAX_ACTIONS, MAX_ELEMS = 16, 1 << 20      # sac_loss.hip
 
@@ -176,3 +183,88 @@ def actor_loss(log_pi, q1_pi, q2_pi, *, alpha=None, log_alpha=None, target_entro
         if need_al:
             temp = _Precomputed.apply(temp, dla, log_alpha)
     return ActorLoss(policy, temp)
+
+
+def _same_device(what, named):
+    """the tensors of one launch lie on one device (the first one's): the kernel runs there and reads every pointer there"""
+    first = next(((n, t) for n, t in named if t is not None), None)
+    for n, t in named:
+        if t is not None and t.device != first[1].device:
+            raise ValueError(f"{what}: {n} is on {t.device}, {first[0]} on {first[1].device}; all tensors of a call lie on one device")
+
+
+def _mask(mask, what, B):
+    """``mask`` after its shape check -> (tensor or None, 1 when its bytes are a bool tensor's): (B,) or (B, 1), bool or fp32"""
+    if mask is None:
+        return None, 0
+    _column(mask, "mask", what, B)
+    if mask.dtype not in (torch.bool, torch.float32):
+        raise ValueError(f"{what}: mask must be bool or float32, got {mask.dtype}")
+    if not mask.is_cuda:
+        raise _lib.DgvitError(f"{what}: mask is on {mask.device}; the DGViT HIP path needs a ROCm device (no CPU fallback)")
+    mask = mask.detach().contiguous()
+    return (mask.view(torch.uint8), 1) if mask.dtype == torch.bool else (mask, 0)      # the bool's own bytes: no cast launch
+
+
+def _bc(what, pred, action, mask, q, nll, B, A):
+    """the one dgvit_sac_bc_loss launch of bc_loss and nll_loss, whose shape checks have run"""
+    mk, u8 = _mask(mask, what, B)
+    named = [("log_prob" if nll else "pred", pred), ("action", None if nll else action.detach())] + [(n, None if t is None else t.detach()) for n, t in q]
+    _same_device(what, named + [("mask", mk)])
+    p, a, q1d, q2d, q1p, q2p = _on_device(named)
+    need = torch.is_grad_enabled() and pred.requires_grad
+    dev = p.device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    grads = torch.empty(B * A, dtype=torch.float32, device=dev) if need else None
+    with torch.cuda.device(dev):
+        rc = _lib.load().dgvit_sac_bc_loss(_ptr(p), _ptr(a), _ptr(mk), u8, _ptr(q1d), _ptr(q2d), _ptr(q1p), _ptr(q2p), int(nll), _ptr(out),
+                                           _ptr(grads), B, A, _stream())
+    _lib.check(rc, "dgvit_sac_bc_loss")
+    loss = out[0]
+    if need:
+        loss = _Precomputed.apply(loss, grads, pred)
+    return BCLoss(loss, out[1])
+
+
+def bc_loss(pred, action, *, mask=None, q_demo=None, q_pi=None):
+    """``BCLoss(loss, used)``: the behaviour-cloning term of an actor loss over the demonstration rows of a batch, one launch:
+
+        l_b  = mean_a (pred_ba - action_ba)^2
+        m_b  = mask_b: None = 1, a bool tensor, or fp32 weights >= 0 (0/1 or fractional); (B,) or (B, 1) on the device
+        f_b  = 1, or with the Q-filter [ mean_a min(q1_demo, q2_demo)_b > mean_a min(q1_pi, q2_pi)_b ]      (strict: a tie does not apply)
+        used = sum_b m_b f_b            loss = sum_b m_b f_b l_b / used, or 0 when used == 0
+
+    ``pred`` is the policy's action for the batch's states (``sample()``'s action or its tanh(mean)), ``action`` the stored one, both
+    (B, A).  ``q_demo=(q1, q2)`` are the critic's values of the stored actions and ``q_pi=(q1, q2)`` those of ``pred``, each (B, A), given
+    together or not at all: the demonstration then counts only where the critic rates it above the policy's own action.  ``loss`` is 0-d
+    and differentiable in ``pred`` only (the backward is one launch, as ``actor_loss``'s); ``used`` is a 0-d detached device tensor for
+    logging.  Nothing reads a count back: when no row applies the loss and its gradients are exact zeros, never NaN, and a step
+    captured by ``GraphedStep`` follows a mask refilled between replays."""
+    what = "bc_loss"
+    if (q_demo is None) != (q_pi is None):
+        raise ValueError(f"{what}: q_demo= and q_pi= are given together or not at all")
+    q = []
+    B, A = _matrix(pred, "pred", what)
+    _matrix(action, "action", what, (B, A))
+    if q_demo is not None:
+        for name, pair in (("q_demo", q_demo), ("q_pi", q_pi)):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"{what}: {name} must be the pair (q1, q2) of (B, A) tensors")
+            for j, t in enumerate(pair):
+                _matrix(t, f"{name}[{j}]", what, (B, A))
+                q.append((f"{name}[{j}]", t))
+    else:
+        q = [("q", None)] * 4
+    return _bc(what, pred, action, mask, q, False, B, A)
+
+
+def nll_loss(log_prob, *, mask=None):
+    """``BCLoss(loss, used)``: maximum-likelihood behaviour cloning, ``bc_loss`` with ``l_b = -log_prob_b`` for ``log_prob`` = ``policy.log_prob(
+    inp, batch["act"])``, (B,) or (B, 1); same ``mask``, same normalisation by ``used`` on the device, differentiable in ``log_prob`` only.
+    There is no Q-filter here: its two sides are critic values of two ACTIONS, and this loss never forms the policy's action."""
+    what = "nll_loss"
+    if not isinstance(log_prob, torch.Tensor) or log_prob.dim() not in (1, 2) or (log_prob.dim() == 2 and log_prob.shape[1] != 1) \
+            or not 1 <= log_prob.shape[0] <= MAX_ELEMS:
+        got = tuple(log_prob.shape) if isinstance(log_prob, torch.Tensor) else type(log_prob).__name__
+        raise ValueError(f"{what}: log_prob must be (B, 1) or (B,) with 1 <= B <= {MAX_ELEMS}, got {got}")
+    return _bc(what, log_prob, None, mask, [("q", None)] * 4, True, log_prob.shape[0], 1)

@@ -72,6 +72,17 @@ def _tanh_gaussian(module, mean, log_std_raw):
     return F_.tanh_gaussian_sample(mean, log_std_raw, _standard_normal(mean), scale, bias, LOG_SIG_MIN, LOG_SIG_MAX)
 
 
+def _log_prob(module, mean, log_std_raw, action):
+    """log_prob() of the tanh-Gaussian policies from the head outputs: the density sample() reports, at a given action"""
+    if not isinstance(action, torch.Tensor) or action.shape != mean.shape:
+        got = tuple(action.shape) if isinstance(action, torch.Tensor) else type(action).__name__
+        raise ValueError(f"log_prob: action must be a {tuple(mean.shape)} tensor, one row per state, got {got}")
+    scale, bias = module.action_scale, module.action_bias
+    if scale.device != mean.device:
+        module.action_scale, module.action_bias = scale, bias = scale.to(mean.device), bias.to(mean.device)
+    return F_.tanh_gaussian_log_prob(mean, log_std_raw, action, scale, bias, LOG_SIG_MIN, LOG_SIG_MAX)
+
+
 def _action_affine(action_space):
     if action_space is None:
         return torch.tensor(1.), torch.tensor(0.)
@@ -187,6 +198,13 @@ class GoTPolicy(nn.Module):
         log-density as ONE HIP launch behind the head (no Normal object: its argument check alone is a host sync per call)."""
         mean, log_std_raw = self._head_outputs(inp)
         return _tanh_gaussian(self, mean, log_std_raw)
+
+    def log_prob(self, inp, action):
+        """``log pi(action | inp)``, (B, 1): the density ``sample`` reports, at a given ``action`` (B, nb_actions) -- a demonstration's --
+        with one HIP launch behind the head (``functional.tanh_gaussian_log_prob``).  Actions at or beyond the bounds are clipped to
+        ``tanh^-1`` of +-(1 - 1e-6), so the value is finite.  Differentiable in the parameters, not in ``action``."""
+        mean, log_std_raw = self._head_outputs(inp)
+        return _log_prob(self, mean, log_std_raw, action)
 
     def to(self, device):
         self.action_scale = self.action_scale.to(device)

@@ -271,6 +271,22 @@ int dgvit_tanh_gaussian_backward(const float* mean, const float* log_std_raw, co
                                  float ls_min, float ls_max, const float* d_action, const float* d_log_prob, const float* d_tanh_mean,
                                  float* dmean, float* dlog_std_raw, int B, int A, void* stream);
 
+/* log pi(a | s) of a GIVEN action under the same policy -- behaviour cloning by maximum likelihood, AWAC/AWR-style extraction, importance
+ * ratios (GoTPolicy.log_prob / GaussianPolicy.log_prob).  The density dgvit_tanh_gaussian_forward reports, at y = (action - bias) / scale
+ * in the place of tanh(mean + std eps), one launch each way:
+ *   y  = clamp((action - bias) / scale, -(1 - 1e-6), 1 - 1e-6)     a demonstration at or beyond the action bound stays finite
+ *   x  = atanh(y) = 0.5 log((1 + y) / (1 - y));   ls = clamp(log_std_raw, ls_min, ls_max);   e = (x - mean) exp(-ls)
+ *   log_prob[b] = sum_a [ -e^2 / 2 - ls - log(sqrt(2 pi)) - log(scale * (1 - y^2) + 1e-6) ]
+ * computed in double from the fp32 inputs and rounded once where a value is stored.  mean, log_std_raw, action: (B, A); log_prob and
+ * d_log_prob: B values; scale, bias: `scale_n` = 1 or A values.  backward: dmean = g e exp(-ls), dlog_std_raw = g (e^2 - 1) where
+ * log_std_raw lies in [ls_min, ls_max] (bounds included) and 0 elsewhere, g = d_log_prob[b]; nothing is produced for action, scale or bias.
+ * B >= 1, 1 <= A <= 16, B * A < 2^31, ls_min <= ls_max; every pointer non-null and 4-byte aligned, else DGVIT_ERR_ARG before any launch. */
+int dgvit_tanh_gaussian_log_prob(const float* mean, const float* log_std_raw, const float* action, const float* scale, const float* bias,
+                                 int scale_n, float ls_min, float ls_max, float* log_prob, int B, int A, void* stream);
+int dgvit_tanh_gaussian_log_prob_backward(const float* mean, const float* log_std_raw, const float* action, const float* scale,
+                                          const float* bias, int scale_n, float ls_min, float ls_max, const float* d_log_prob, float* dmean,
+                                          float* dlog_std_raw, int B, int A, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Per-operator entry points (used by the encoder above; exported for operator-level parity tests).
  * -------------------------------------------------------------------------------------------- */
@@ -799,6 +815,16 @@ int dgvit_adam_step_groups(float* p, const float* g, float* m, float* v, long lo
  *   as a constant and the policy loss treats log_alpha as one, so the two gradients above are all there are.
  * dgvit_sac_scale_grads: dst[i] = *scale_dev * src[i], 1 <= n <= 3 * 2^20 -- the backward of either loss: a saved gradient buffer
  *   times the 0-d upstream gradient, out of place (the saved buffer serves a second backward) and for any n and 4-byte alignment.
+ * dgvit_sac_bc_loss: the demonstration term of an actor loss, normalised on the device by the rows it applies to:
+ *     l[b]   = (1/A) sum_a (pred[b,a] - action[b,a])^2            nll == 0: pred and action (B, A)
+ *            = -pred[b]                                            nll == 1: pred holds B log-densities, A must be 1, action is not read
+ *     m[b]   = 1 (mask == NULL), mask[b] as fp32 weights >= 0 (mask_u8 == 0), or mask[b] != 0 of B bytes, a bool tensor (mask_u8 == 1)
+ *     f[b]   = 1 without the four q pointers, else [ (1/A) sum_a min(q1_demo, q2_demo)[b,a] > (1/A) sum_a min(q1_pi, q2_pi)[b,a] ]
+ *              (strict: a tie does not apply; the q are (B, A), given together or not at all, and not with nll == 1)
+ *     out[1] = used = sum_b m[b] f[b];    out[0] = sum_b m[b] f[b] l[b] / used, or 0 when used == 0
+ *     grads  = d out[0] / d pred for a unit upstream gradient, B A floats (NULL: not wanted): 2 m f (pred - action) / (A used), or
+ *              -m f / used with nll; all zeros when used == 0.  A row with m f == 0 adds nothing whatever its l: never NaN from it.
+ *   One workgroup, double sums in a fixed order as the two kernels above; nothing is produced for action, mask or the q.
  * -------------------------------------------------------------------------------------------- */
 int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
                           const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
@@ -811,6 +837,8 @@ int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q
                          int with_temperature, float target_entropy, float* losses, float* grads, float* dlog_alpha, int B, int A,
                          void* stream);
 int dgvit_sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, void* stream);
+int dgvit_sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo, const float* q2_demo,
+                      const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * bf16 configuration (BASELINE.json config 5: 224x224 depth frames, 12-layer ViT-Base variant with goal token, bf16).
