@@ -88,6 +88,10 @@ SIGNATURES = {
     "dgvit_mlp_head_forward": (_I, [POINTER(dgvit_mlp_desc), _TABLE, _TABLE, _P, _P, _P, _P]),
     "dgvit_mlp_head_backward_scratch_floats": (_LL, [POINTER(dgvit_mlp_desc)]),
     "dgvit_mlp_head_backward": (_I, [POINTER(dgvit_mlp_desc), _TABLE, _TABLE, _P, _P, _TABLE, _TABLE, _TABLE, _P, _LL, _P]),
+    # the same head with shared input pieces (include/dgvit_hip.h: Shared input pieces); share is const int[nseg]
+    "dgvit_mlp_head_forward_shared": (_I, [POINTER(dgvit_mlp_desc), POINTER(c_int), _TABLE, _TABLE, _P, _P, _P, _P]),
+    "dgvit_mlp_head_backward_shared_scratch_floats": (_LL, [POINTER(dgvit_mlp_desc), POINTER(c_int)]),
+    "dgvit_mlp_head_backward_shared": (_I, [POINTER(dgvit_mlp_desc), POINTER(c_int), _TABLE, _TABLE, _P, _P, _TABLE, _TABLE, _TABLE, _P, _LL, _P]),
     "dgvit_tanh_gaussian_forward": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _I, _I, _P]),
     "dgvit_tanh_gaussian_backward": (_I, [_P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dgvit_tanh_gaussian_log_prob": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _P, _I, _I, _P]),
@@ -169,6 +173,7 @@ SIGNATURES = {
     "dgvit_sac_actor_loss": (_I, [_P, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I, _I, _P]),
     "dgvit_sac_scale_grads": (_I, [_P, _P, _LL, _P, _P]),
     "dgvit_sac_bc_loss": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
+    "dgvit_sac_cql_penalty": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _F, _F, _F, _I, _P, _P, _P, _I, _I, _I, _P]),
     "dgvit_got_bf16_weight_elems": (_LL, [_CFG]),
     "dgvit_got_pack_weights_bf16": (_I, [_CFG, _TABLE, _P, _LL, _I, _P]),
     "dgvit_got_bf16_workspace_bytes": (_LL, [_CFG, _I, _I]),

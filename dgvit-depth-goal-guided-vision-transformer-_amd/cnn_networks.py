@@ -67,6 +67,17 @@ class QNetwork(_ConvStack):
         (q1,), (q2,) = _head([x1, x2, a], [(self.fc1, self.fc2, [self.fc3]), (self.fc11, self.fc21, [self.fc31])])
         return q1, q2
 
+    def q_many(self, inp, actions):
+        """``(q1, q2)``, each (B, M, nb_actions), for ``actions`` (B, M, nb_actions) and ``inp = [istate, pstate]``: ``GoTQNetwork.q_many``
+        behind the CNN stack.  The conv stack and fc_embed run once on the B frames; the head's 256 conv features and 32 goal features
+        are both shared by the M rows of a state."""
+        istate, pstate, B, M = _S._many_actions(inp, actions, self.fc3.out_features)
+        x1 = self._features(istate)
+        x2 = _lin(self.fc_embed, pstate, relu=True)
+        (q1,), (q2,) = _head([x1, x2, actions.view(B * M, -1)], [(self.fc1, self.fc2, [self.fc3]), (self.fc11, self.fc21, [self.fc31])],
+                             share=[M, M, 1])
+        return q1.view(B, M, -1), q2.view(B, M, -1)
+
 
 class GaussianPolicy(_ConvStack):
     """Tanh-Gaussian CNN actor (got_sac_network.py:258-327); istate (B,H,W,K) with frame_channels=K."""
@@ -95,6 +106,10 @@ class GaussianPolicy(_ConvStack):
     def sample(self, inp):
         mean, log_std_raw = self._head_outputs(inp)
         return _S._tanh_gaussian(self, mean, log_std_raw)
+
+    def sample_many(self, inp, n):
+        """``(action (B, n, nb_actions), log_prob (B, n), tanh_mean (B, nb_actions))``: ``GoTPolicy.sample_many`` behind the CNN head"""
+        return _S._sample_many(self, inp, n)
 
     def log_prob(self, inp, action):
         """``log pi(action | inp)``, (B, 1), at a given ``action`` (B, nb_actions): ``GoTPolicy.log_prob`` behind the CNN head"""

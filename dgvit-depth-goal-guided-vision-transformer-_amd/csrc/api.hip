@@ -94,6 +94,18 @@ extern "C" int dgvit_mlp_head_backward(const dgvit_mlp_desc* desc, const float* 
                                        long long scratch_floats, void* stream) {
   return mlp_head_backward(desc, in, params, h1, h2, dy, din, dparams, scratch, scratch_floats, (hipStream_t)stream);
 }
+extern "C" int dgvit_mlp_head_forward_shared(const dgvit_mlp_desc* desc, const int* share, const float* const* in, const float* const* params,
+                                             float* h1, float* h2, float* y, void* stream) {
+  return mlp_head_forward_shared(desc, share, in, params, h1, h2, y, (hipStream_t)stream);
+}
+extern "C" long long dgvit_mlp_head_backward_shared_scratch_floats(const dgvit_mlp_desc* desc, const int* share) {
+  return mlp_head_backward_shared_scratch(desc, share);
+}
+extern "C" int dgvit_mlp_head_backward_shared(const dgvit_mlp_desc* desc, const int* share, const float* const* in, const float* const* params,
+                                              const float* h1, const float* h2, const float* const* dy, float* const* din,
+                                              float* const* dparams, float* scratch, long long scratch_floats, void* stream) {
+  return mlp_head_backward_shared(desc, share, in, params, h1, h2, dy, din, dparams, scratch, scratch_floats, (hipStream_t)stream);
+}
 
 extern "C" int dgvit_tanh_gaussian_forward(const float* mean, const float* log_std_raw, const float* eps, const float* scale,
                                            const float* bias, int scale_n, float ls_min, float ls_max, float* action, float* log_prob,
@@ -285,6 +297,12 @@ extern "C" int dgvit_sac_bc_loss(const float* pred, const float* action, const v
                                  const float* q2_demo, const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A,
                                  void* stream) {
   return sac_bc_loss(pred, action, mask, mask_u8, q1_demo, q2_demo, q1_pi, q2_pi, nll, out, grads, B, A, (hipStream_t)stream);
+}
+extern "C" int dgvit_sac_cql_penalty(const float* q1_cat, const float* q2_cat, const float* q1_data, const float* q2_data, const float* log_w,
+                                     const void* mask, int mask_u8, const float* log_weight, float weight, float temperature, float target_gap,
+                                     int lagrange, float* out, float* grads, float* dlog_weight, int B, int M, int C, void* stream) {
+  return sac_cql_penalty(q1_cat, q2_cat, q1_data, q2_data, log_w, mask, mask_u8, log_weight, weight, temperature, target_gap, lagrange, out, grads,
+                         dlog_weight, B, M, C, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- replay staging

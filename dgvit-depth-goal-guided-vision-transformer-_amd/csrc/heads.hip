@@ -21,11 +21,13 @@ namespace {
 
 constexpr int HMAXN = 128;      // widest hidden layer
 constexpr int HMAXK = 512;      // widest concatenated input
+constexpr int HMAXSHARE = 256;  // most head rows that may read one row of a shared input piece (dgvit_mlp_head_*_shared)
 
 struct HeadArgs {
   int B, nseg, kx[3], ldx[3], K0, KP;      // KP = K0 rounded up to 8 (LDS image width without the pad)
   int n1, n2, n3, towers, heads3;
   const float* x[3];
+  int share[3];                             // shared entry points: head row r reads row r / share[s] of piece s (1 = its own row)
   const float* w1[2]; const float* b1[2]; const float* w2[2]; const float* b2[2];
   const float* w3[2][2]; const float* b3[2][2];
   float* h1; float* h2; float* y;           // (towers, B, n1) (towers, B, n2) (towers, heads3, B, n3)
@@ -39,13 +41,16 @@ struct HeadArgs {
   float* dw1[2]; float* db1[2]; float* dw2[2]; float* db2[2]; float* dw3[2][2]; float* db3[2][2];
 };
 
-// concatenated input rows [row0, row0 + 32) -> LDS image [32][KP + 4], zero beyond B and beyond K0
+// concatenated input rows [row0, row0 + 32) -> LDS image [32][KP + 4], zero beyond B and beyond K0.  SHARED: head row r takes row
+// r / share[sg] of piece sg (the layout of repeat_interleave, never materialised); the image is the one the materialised rows give
+template <bool SHARED>
 __device__ __forceinline__ void stage_x(const HeadArgs& a, float* xs, int row0, int tid) {
   const int SX = a.KP + 4;
   int koff = 0;
   for (int sg = 0; sg < a.nseg; ++sg) {
     const int kx = a.kx[sg], ld = a.ldx[sg];
     const float* __restrict__ src = a.x[sg];
+    const int sh = SHARED ? a.share[sg] : 1;
     // 16 loads in flight per thread and trip (the whole 32 x 290 input of the CNN heads in three trips): the kernel is one
     // workgroup walking a chain of dependent global round trips, every trip saved is ~1.5 us
     for (int f0 = tid; f0 < HR * kx; f0 += 256 * 16) {
@@ -53,7 +58,8 @@ __device__ __forceinline__ void stage_x(const HeadArgs& a, float* xs, int row0, 
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int f = f0 + u * 256, r = f / kx, k = f - r * kx;
-        v[u] = (f < HR * kx && row0 + r < a.B) ? src[(long long)(row0 + r) * ld + k] : 0.f;
+        const int sr = SHARED ? (row0 + r) / sh : row0 + r;
+        v[u] = (f < HR * kx && row0 + r < a.B) ? src[(long long)sr * ld + k] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
@@ -68,7 +74,7 @@ __device__ __forceinline__ void stage_x(const HeadArgs& a, float* xs, int row0, 
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <bool VEC>
+template <bool VEC, bool SHARED = false>
 __global__ void __launch_bounds__(256) mlp_head_fwd_kernel(const HeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int SX = a.KP + 4, S1 = a.n1 + 4, S2 = a.n2 + 4;
@@ -77,7 +83,7 @@ __global__ void __launch_bounds__(256) mlp_head_fwd_kernel(const HeadArgs a) {
   float* h2s = h1s + HR * S1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
   const int row0 = blockIdx.x * HR, t = blockIdx.y;
-  stage_x(a, xs, row0, tid);
+  stage_x<SHARED>(a, xs, row0, tid);
   __syncthreads();
   // layer 1
   for (int cb = wave; cb * 32 < a.n1; cb += 4) {
@@ -149,7 +155,7 @@ __host__ __device__ inline PartOff part_offsets(int K0, int n1, int n2, int n3, 
   return o;
 }
 
-template <bool VEC>
+template <bool VEC, bool SHARED = false>
 __global__ void __launch_bounds__(256) mlp_head_bwd_kernel(const HeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int SX = a.KP + 4, S1 = a.n1 + 4, S2 = a.n2 + 4;
@@ -168,7 +174,7 @@ __global__ void __launch_bounds__(256) mlp_head_bwd_kernel(const HeadArgs a) {
   float* o_w2 = a.direct ? a.dw2[t] : part + po.w2;
   float* o_b2 = a.direct ? a.db2[t] : part + po.b2;
 
-  stage_x(a, xs, row0, tid);
+  stage_x<SHARED>(a, xs, row0, tid);
   // h1 / h2 rows (n1, n2 multiples of 32: whole float4 pieces) -> LDS: every piece of a thread is requested before the first is used,
   // from a clamped row (rows past the batch are zeroed afterwards).  The per-element form this replaces compiled to one load and one
   // `s_waitcnt vmcnt(0)` per element -- 32 dependent L2 round trips in front of the first MFMA of a kernel that is one workgroup's
@@ -327,6 +333,24 @@ __global__ void __launch_bounds__(256) head_dx_add_kernel(const HeadArgs a) {
   if (d) d[(long long)row * a.lddx[sg] + kk] += a.dx1[idx];
 }
 
+// din of the shared pieces: the M per-row gradients of each state, summed in fp32 in row order, ((r0 + r1) + ...) + r(M-1).
+// blockIdx.y = piece; thread = one (state, column).  The M loads of a thread do not depend on its sum, so they overlap.
+struct ShareSum { const float* rows[3]; float* out[3]; int kx[3]; int states, M; };
+__global__ void __launch_bounds__(256) head_share_sum_kernel(const ShareSum a) {
+  const int s = blockIdx.y;
+  const float* __restrict__ rows = s == 0 ? a.rows[0] : (s == 1 ? a.rows[1] : a.rows[2]);
+  float* __restrict__ out = s == 0 ? a.out[0] : (s == 1 ? a.out[1] : a.out[2]);
+  const int kx = s == 0 ? a.kx[0] : (s == 1 ? a.kx[1] : a.kx[2]);
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (!out || idx >= (long long)a.states * kx) return;
+  const long long b = idx / kx;
+  const float* p = rows + b * a.M * kx + (idx - b * kx);
+  float acc = p[0];
+#pragma unroll 8
+  for (int m = 1; m < a.M; ++m) acc += p[(long long)m * kx];
+  out[idx] = acc;
+}
+
 size_t fwd_lds(int KP, int n1, int n2) { return sizeof(float) * HR * ((size_t)(KP + 4) + (n1 + 4) + (n2 + 4)); }
 size_t bwd_lds(int KP, int n1, int n2, int n3, int heads3) {
   return sizeof(float) * (HR * ((size_t)(KP + 4) + 2 * (n1 + 4) + 2 * (n2 + 4)) + (size_t)heads3 * HR * n3 + (size_t)heads3 * n3 * n2 + 4);
@@ -343,7 +367,7 @@ int fill_args(HeadArgs& a, const dgvit_mlp_desc* d, const float* const* in, cons
   a.K0 = 0;
   for (int s = 0; s < d->nseg; ++s) {
     DGVIT_CHECK_ARG(in[s] && d->kx[s] > 0 && d->ldx[s] >= d->kx[s], "mlp_head: bad input piece %d", s);
-    a.x[s] = in[s]; a.kx[s] = d->kx[s]; a.ldx[s] = d->ldx[s];
+    a.x[s] = in[s]; a.kx[s] = d->kx[s]; a.ldx[s] = d->ldx[s]; a.share[s] = 1;
     a.K0 += d->kx[s];
   }
   DGVIT_CHECK_ARG(a.K0 <= HMAXK, "mlp_head: concatenated input wider than %d", HMAXK);
@@ -369,24 +393,67 @@ bool w1_vec(const HeadArgs& a) {
   return v;
 }
 
-}  // namespace
+// the common share count M of a shared call (1: every piece has its own rows), or an error
+int share_count(const char* name, const dgvit_mlp_desc* d, const int* share, int* M) {
+  DGVIT_CHECK_ARG(d && share, "%s: null pointer", name);
+  DGVIT_CHECK_ARG(d->batch > 0 && d->nseg >= 1 && d->nseg <= 3, "%s: batch must be positive, 1..3 input pieces", name);
+  *M = 1;
+  for (int s = 0; s < d->nseg; ++s) {
+    DGVIT_CHECK_ARG(share[s] >= 1, "%s: share[%d]=%d must be at least 1", name, s, share[s]);
+    DGVIT_CHECK_ARG(share[s] == 1 || *M == 1 || share[s] == *M, "%s: share[%d]=%d differs from the common count %d (every share is 1 or one M)",
+                    name, s, share[s], *M);
+    if (share[s] > 1) *M = share[s];
+  }
+  DGVIT_CHECK_ARG(*M <= HMAXSHARE, "%s: share count M=%d must be at most %d", name, *M, HMAXSHARE);
+  DGVIT_CHECK_ARG(d->batch % *M == 0, "%s: batch=%d must be a multiple of the share count M=%d", name, d->batch, *M);
+  return DGVIT_OK;
+}
 
-int mlp_head_forward(const dgvit_mlp_desc* d, const float* const* in, const float* const* params, float* h1, float* h2, float* y,
-                     hipStream_t stream) {
+long long share_rows_floats(const dgvit_mlp_desc* d, const int* share) {     // the per-row gradients of the shared pieces
+  long long n = 0;
+  for (int s = 0; s < d->nseg; ++s)
+    if (share[s] > 1) n += pad4((long long)d->batch * d->kx[s]);
+  return n;
+}
+
+// share: null (every piece has its own rows), or the counts of a shared call with M > 1
+int head_forward(const dgvit_mlp_desc* d, const int* share, const float* const* in, const float* const* params, float* h1, float* h2, float* y,
+                 hipStream_t stream) {
   HeadArgs a;
   TRY(fill_args(a, d, in, params));
   DGVIT_CHECK_ARG(h1 && h2 && y, "mlp_head_forward: null output");
   a.h1 = h1; a.h2 = h2; a.y = y;
+  for (int s = 0; share && s < a.nseg; ++s) a.share[s] = share[s];
   const size_t lds = fwd_lds(a.KP, a.n1, a.n2);
-  TRY((allow_dynamic_lds<mlp_head_fwd_kernel<true>, mlp_head_fwd_kernel<false>>((int)fwd_lds(HMAXK, HMAXN, HMAXN), "mlp_head_forward")));
+  TRY((allow_dynamic_lds<mlp_head_fwd_kernel<true>, mlp_head_fwd_kernel<false>, mlp_head_fwd_kernel<true, true>, mlp_head_fwd_kernel<false, true>>(
+      (int)fwd_lds(HMAXK, HMAXN, HMAXN), "mlp_head_forward")));
   const dim3 grid((a.B + HR - 1) / HR, a.towers);
   {
     ProfileScope t(PROF_OTHER, 0.0, stream);
-    if (w1_vec(a)) hipLaunchKernelGGL(mlp_head_fwd_kernel<true>, grid, dim3(256), lds, stream, a);
+    if (share) {
+      if (w1_vec(a)) hipLaunchKernelGGL((mlp_head_fwd_kernel<true, true>), grid, dim3(256), lds, stream, a);
+      else hipLaunchKernelGGL((mlp_head_fwd_kernel<false, true>), grid, dim3(256), lds, stream, a);
+    } else if (w1_vec(a)) hipLaunchKernelGGL(mlp_head_fwd_kernel<true>, grid, dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(mlp_head_fwd_kernel<false>, grid, dim3(256), lds, stream, a);
   }
   DGVIT_CHECK_LAUNCH("mlp_head_forward");
   return DGVIT_OK;
+}
+
+}  // namespace
+
+int mlp_head_forward(const dgvit_mlp_desc* d, const float* const* in, const float* const* params, float* h1, float* h2, float* y,
+                     hipStream_t stream) {
+  return head_forward(d, nullptr, in, params, h1, h2, y, stream);
+}
+
+// Shared input pieces: piece s with share[s] = M has batch / M rows and head row r reads its row r / M.  M = 1 IS the
+// unshared call: the same launches, the same bits.
+int mlp_head_forward_shared(const dgvit_mlp_desc* d, const int* share, const float* const* in, const float* const* params, float* h1, float* h2,
+                            float* y, hipStream_t stream) {
+  int M = 1;
+  TRY(share_count("mlp_head_forward_shared", d, share, &M));
+  return head_forward(d, M == 1 ? nullptr : share, in, params, h1, h2, y, stream);
 }
 
 long long mlp_head_backward_scratch(const dgvit_mlp_desc* d) {
@@ -399,18 +466,46 @@ long long mlp_head_backward_scratch(const dgvit_mlp_desc* d) {
   return (long long)nwg * d->towers * part_offsets(K0, d->n1, d->n2, d->n3, d->heads3).total + dx1;
 }
 
-int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const float* const* params, const float* h1, const float* h2,
-                      const float* const* dy, float* const* din, float* const* dparams, float* scratch, long long scratch_floats,
-                      hipStream_t stream) {
+long long mlp_head_backward_shared_scratch(const dgvit_mlp_desc* d, const int* share) {
+  int M = 1;
+  if (share_count("mlp_head_backward_shared_scratch_floats", d, share, &M) != DGVIT_OK) return -1;
+  const long long base = mlp_head_backward_scratch(d);
+  return M == 1 || base < 0 ? base : base + share_rows_floats(d, share);
+}
+
+namespace {
+// share: null, or the counts of a shared call with common count M > 1.  The scratch of a shared call is the unshared call's followed by
+// one dense (batch, kx[s]) buffer per shared piece: the kernels write the per-row input gradients there exactly as they write an
+// unshared din (tower 0, then + tower 1), and head_share_sum_kernel sums the M rows of each state into din[s] in row order.
+int head_backward(const dgvit_mlp_desc* d, const int* share, int M, const float* const* in, const float* const* params, const float* h1,
+                  const float* h2, const float* const* dy, float* const* din, float* const* dparams, float* scratch, long long scratch_floats,
+                  hipStream_t stream) {
   HeadArgs a;
   TRY(fill_args(a, d, in, params));
   DGVIT_CHECK_ARG(h1 && h2 && dy && din && dparams, "mlp_head_backward: null pointer");
   const long long need = mlp_head_backward_scratch(d);
-  DGVIT_CHECK_ARG(scratch && scratch_floats >= need, "mlp_head_backward: scratch %lld < %lld floats", scratch_floats, need);
+  const long long need_all = need + (share ? share_rows_floats(d, share) : 0);
+  DGVIT_CHECK_ARG(scratch && scratch_floats >= need_all, "mlp_head_backward: scratch %lld < %lld floats", scratch_floats, need_all);
   a.h1 = const_cast<float*>(h1); a.h2 = const_cast<float*>(h2);
   for (int t = 0; t < a.towers; ++t)
     for (int j = 0; j < a.heads3; ++j) a.dyp[t][j] = dy[t * a.heads3 + j];
   for (int s = 0; s < a.nseg; ++s) { a.dx[s] = din[s]; a.lddx[s] = a.kx[s]; }
+  ShareSum ss{};
+  bool any_shared = false;
+  if (share) {
+    float* rows = scratch + need;
+    ss.states = a.B / M; ss.M = M;
+    for (int s = 0; s < a.nseg; ++s) {
+      a.share[s] = share[s];
+      if (share[s] == 1) continue;
+      if (din[s]) {
+        ss.rows[s] = rows; ss.out[s] = din[s]; ss.kx[s] = a.kx[s];
+        a.dx[s] = rows;
+        any_shared = true;
+      }
+      rows += pad4((long long)a.B * a.kx[s]);
+    }
+  }
   const int per = 4 + 2 * a.heads3;
   for (int t = 0; t < a.towers; ++t) {
     float* const* g = dparams + t * per;
@@ -422,7 +517,8 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
   a.direct = nwg == 1;
   a.part = scratch; a.part_stride = po.total;
   const size_t lds = bwd_lds(a.KP, a.n1, a.n2, a.n3, a.heads3);
-  TRY((allow_dynamic_lds<mlp_head_bwd_kernel<true>, mlp_head_bwd_kernel<false>>((int)bwd_lds(HMAXK, HMAXN, HMAXN, 4, 2), "mlp_head_backward")));
+  TRY((allow_dynamic_lds<mlp_head_bwd_kernel<true>, mlp_head_bwd_kernel<false>, mlp_head_bwd_kernel<true, true>, mlp_head_bwd_kernel<false, true>>(
+      (int)bwd_lds(HMAXK, HMAXN, HMAXN, 4, 2), "mlp_head_backward")));
   // a twin head runs both towers in ONE launch (blockIdx.y): tower 0 writes dx, tower 1 writes its input gradient to scratch and a
   // small kernel adds it (x = t0 + t1: the order is fixed); the two towers used to be two launches one behind the other
   bool any_dx = false;
@@ -431,11 +527,20 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
   {
     ProfileScope t(PROF_OTHER, 0.0, stream);
     a.dx1 = (a.towers == 2 && any_dx) ? scratch + (need - (((long long)a.B * a.K0 + 3) & ~3ll)) : nullptr;
-    if (vec) hipLaunchKernelGGL(mlp_head_bwd_kernel<true>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
+    if (share) {
+      if (vec) hipLaunchKernelGGL((mlp_head_bwd_kernel<true, true>), dim3(nwg, a.towers), dim3(256), lds, stream, a);
+      else hipLaunchKernelGGL((mlp_head_bwd_kernel<false, true>), dim3(nwg, a.towers), dim3(256), lds, stream, a);
+    } else if (vec) hipLaunchKernelGGL(mlp_head_bwd_kernel<true>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(mlp_head_bwd_kernel<false>, dim3(nwg, a.towers), dim3(256), lds, stream, a);
     if (a.dx1) {
       const long long n = (long long)a.B * a.K0;
       hipLaunchKernelGGL(head_dx_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    }
+    if (any_shared) {
+      int kmax = 0;
+      for (int s = 0; s < a.nseg; ++s) kmax = ss.out[s] && ss.kx[s] > kmax ? ss.kx[s] : kmax;
+      const long long n = (long long)ss.states * kmax;
+      hipLaunchKernelGGL(head_share_sum_kernel, dim3((unsigned)((n + 255) / 256), a.nseg), dim3(256), 0, stream, ss);
     }
   }
   DGVIT_CHECK_LAUNCH("mlp_head_backward");
@@ -461,6 +566,21 @@ int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const flo
     }
   }
   return reduce_group_flush(g, stream);
+}
+}  // namespace
+
+int mlp_head_backward(const dgvit_mlp_desc* d, const float* const* in, const float* const* params, const float* h1, const float* h2,
+                      const float* const* dy, float* const* din, float* const* dparams, float* scratch, long long scratch_floats,
+                      hipStream_t stream) {
+  return head_backward(d, nullptr, 1, in, params, h1, h2, dy, din, dparams, scratch, scratch_floats, stream);
+}
+
+int mlp_head_backward_shared(const dgvit_mlp_desc* d, const int* share, const float* const* in, const float* const* params, const float* h1,
+                             const float* h2, const float* const* dy, float* const* din, float* const* dparams, float* scratch,
+                             long long scratch_floats, hipStream_t stream) {
+  int M = 1;
+  TRY(share_count("mlp_head_backward_shared", d, share, &M));
+  return head_backward(d, M == 1 ? nullptr : share, M, in, params, h1, h2, dy, din, dparams, scratch, scratch_floats, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ tanh-Gaussian sampling

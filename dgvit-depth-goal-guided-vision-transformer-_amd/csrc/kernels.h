@@ -72,6 +72,10 @@ int sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q2_pi, 
 int sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, hipStream_t);
 int sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo, const float* q2_demo,
                 const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A, hipStream_t);
+// the CQL(H) penalty of a twin critic over M proposal actions per row (include/dgvit_hip.h: dgvit_sac_cql_penalty)
+int sac_cql_penalty(const float* q1_cat, const float* q2_cat, const float* q1_data, const float* q2_data, const float* log_w, const void* mask,
+                    int mask_u8, const float* log_weight, float weight, float temperature, float target_gap, int lagrange, float* out,
+                    float* grads, float* dlog_weight, int B, int M, int C, hipStream_t);
 int im2col(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 int col2im_relu(const float*, const float*, float*, int, int, int, int, int, int, hipStream_t);
 // the (B, H, W, C) frame gradient from conv1's column gradient (rows of KP floats, 25 C real taps): no ReLU mask
@@ -150,6 +154,11 @@ int mlp_head_forward(const dgvit_mlp_desc*, const float* const*, const float* co
 long long mlp_head_backward_scratch(const dgvit_mlp_desc*);
 int mlp_head_backward(const dgvit_mlp_desc*, const float* const*, const float* const*, const float*, const float*, const float* const*,
                       float* const*, float* const*, float*, long long, hipStream_t);
+// the same head with input pieces shared by groups of share[s] consecutive head rows (include/dgvit_hip.h)
+int mlp_head_forward_shared(const dgvit_mlp_desc*, const int* share, const float* const*, const float* const*, float*, float*, float*, hipStream_t);
+long long mlp_head_backward_shared_scratch(const dgvit_mlp_desc*, const int* share);
+int mlp_head_backward_shared(const dgvit_mlp_desc*, const int* share, const float* const*, const float* const*, const float*, const float*,
+                             const float* const*, float* const*, float* const*, float*, long long, hipStream_t);
 int tanh_gaussian_forward(const float*, const float*, const float*, const float*, const float*, int, float, float, float*, float*, float*,
                           int, int, hipStream_t);
 int tanh_gaussian_backward(const float*, const float*, const float*, const float*, int, float, float, const float*, const float*,

@@ -7,6 +7,8 @@
 //                     d logp | dq1pi | dq2pi and d log_alpha for unit upstream gradients
 //   sac_bc_loss     : the demonstration term of the actor loss: a masked, optionally Q-filtered mean of (pred - action)^2 or
 //                     of -log_prob over the `used` rows it applies to, `used` counted on the device; d pred for a unit upstream gradient
+//   sac_cql_penalty : the conservative term of a CQL(H) critic loss: w (gap_1 + gap_2 - 2 tau), gap_i the masked mean over rows
+//                     and columns of T logsumexp_m((q_cat - log_w) / T) - q_data; d q_cat (the softmax) | d q_data and d log_weight
 //   sac_scale_grads : dst = *scale_dev * src, the backward of either loss for the 0-d upstream gradient autograd hands over
 // The two loss kernels are ONE workgroup of 256 threads: B * A is at most 2^20 elements of a few flops each, and one workgroup needs no
 // second launch, no atomics and no counters for its sums.  Every thread walks the elements i = tid, tid + 256, ... (row b = i / A), sums
@@ -192,6 +194,80 @@ __global__ void __launch_bounds__(256) sac_bc_loss_kernel(const float* __restric
   }
 }
 
+// The CQL(H) penalty of a twin critic.  For critic i, row b and column c, over the M proposal actions of the row:
+//   z_m = q_cat[b][m][c] - log_w[b][m];   lse = T log sum_m exp(z_m / T)   (max-subtracted);   gap_i = sum_{b, c} w_b (lse - q_data) / (used C)
+// with w_b the row's mask weight and used = sum_b w_b;  loss = w (gap_1 + gap_2 - 2 tau), tau = 0 outside the Lagrange form, w = the float
+// or exp(*log_weight) read here.  thread = items (i, b, c) = tid, tid + 256, ...: the first walk sums the gaps, the sums meet as
+// block_sum does, and the second walk writes the gradients for a unit upstream gradient, which need 1 / used:
+//   d q_cat = w w_b softmax_m(z / T) / (used C),   d q_data = -w w_b / (used C);   a row of weight 0 gets exact zeros
+// used == 0 gives loss 0, weight_loss 0 and zero gradients.  out = [loss, weight_loss, gap_1, gap_2, used].
+__device__ __forceinline__ double cql_zt(const float* __restrict__ qc, const float* __restrict__ lw, int m, int C, double T) {
+  return ((double)qc[(long long)m * C] - (lw ? (double)lw[m] : 0.0)) / T;
+}
+
+__global__ void __launch_bounds__(256) sac_cql_penalty_kernel(const float* __restrict__ q1c, const float* __restrict__ q2c,
+                                                              const float* __restrict__ q1d, const float* __restrict__ q2d,
+                                                              const float* __restrict__ log_w, const void* __restrict__ mask, int mask_u8,
+                                                              const float* __restrict__ log_weight, float weight, float temperature,
+                                                              float target_gap, int lagrange, float* __restrict__ out,
+                                                              float* __restrict__ grads, float* __restrict__ dlog_weight, int B, int M, int C) {
+  __shared__ double wave_sum[3][4];
+  const double w = log_weight ? exp((double)*log_weight) : (double)weight, T = (double)temperature;   // in double, as every term here
+  const int n = B * C;
+  double acc1 = 0.0, acc2 = 0.0, cnt = 0.0;
+  for (int it = threadIdx.x; it < 2 * n; it += 256) {
+    const int i = it >= n, e = it - i * n, b = e / C, c = e - b * C;
+    const double wb = !mask ? 1.0 : (mask_u8 ? (double)(static_cast<const unsigned char*>(mask)[b] != 0) : (double)static_cast<const float*>(mask)[b]);
+    if (wb == 0.0) continue;
+    const float* __restrict__ qc = (i ? q2c : q1c) + (long long)b * M * C + c;
+    const float* __restrict__ lw = log_w ? log_w + (long long)b * M : nullptr;
+    double mx = cql_zt(qc, lw, 0, C, T);
+    for (int m = 1; m < M; ++m) mx = fmax(mx, cql_zt(qc, lw, m, C, T));
+    double S = 0.0;
+    for (int m = 0; m < M; ++m) S += exp(cql_zt(qc, lw, m, C, T) - mx);
+    const double term = wb * (T * (mx + log(S)) - (double)(i ? q2d : q1d)[e]);
+    if (i) acc2 += term; else acc1 += term;
+    if (it < n && c == 0) cnt += wb;
+  }
+  const double tot1 = block_sum(acc1, wave_sum[0]);
+  const double tot2 = block_sum(acc2, wave_sum[1]);
+  const double used = block_sum(cnt, wave_sum[2]);
+  const double inv = used > 0.0 ? 1.0 / (used * (double)C) : 0.0;
+  if (threadIdx.x == 0) {
+    const double g1 = tot1 * inv, g2 = tot2 * inv;
+    const double excess = used > 0.0 ? g1 + g2 - (lagrange ? 2.0 * (double)target_gap : 0.0) : 0.0;
+    out[0] = (float)(w * excess);
+    out[1] = lagrange ? (float)(-w * excess) : 0.f;
+    out[2] = (float)g1;
+    out[3] = (float)g2;
+    out[4] = (float)used;
+    if (dlog_weight) dlog_weight[0] = (float)(-w * excess);
+  }
+  if (!grads) return;
+  const long long ncat = (long long)B * M * C;
+  for (int it = threadIdx.x; it < 2 * n; it += 256) {
+    const int i = it >= n, e = it - i * n, b = e / C, c = e - b * C;
+    const double wb = !mask ? 1.0 : (mask_u8 ? (double)(static_cast<const unsigned char*>(mask)[b] != 0) : (double)static_cast<const float*>(mask)[b]);
+    float* __restrict__ gc = grads + i * ncat + (long long)b * M * C + c;
+    float* __restrict__ gd = grads + 2 * ncat + (long long)i * n + e;
+    const double coef = w * wb * inv;
+    if (wb == 0.0 || inv == 0.0) {
+      for (int m = 0; m < M; ++m) gc[(long long)m * C] = 0.f;
+      *gd = 0.f;
+      continue;
+    }
+    const float* __restrict__ qc = (i ? q2c : q1c) + (long long)b * M * C + c;
+    const float* __restrict__ lw = log_w ? log_w + (long long)b * M : nullptr;
+    double mx = cql_zt(qc, lw, 0, C, T);
+    for (int m = 1; m < M; ++m) mx = fmax(mx, cql_zt(qc, lw, m, C, T));
+    double S = 0.0;
+    for (int m = 0; m < M; ++m) S += exp(cql_zt(qc, lw, m, C, T) - mx);
+    const double cs = coef / S;
+    for (int m = 0; m < M; ++m) gc[(long long)m * C] = (float)(cs * exp(cql_zt(qc, lw, m, C, T) - mx));
+    *gd = (float)(-coef);
+  }
+}
+
 __global__ void __launch_bounds__(256) sac_scale_grads_kernel(const float* __restrict__ src, float* __restrict__ dst, long long n,
                                                               const float* __restrict__ scale_dev) {
   const float s = *scale_dev;
@@ -268,6 +344,34 @@ int sac_bc_loss(const float* pred, const float* action, const void* mask, int ma
                        grads, B, A);
   }
   DGVIT_CHECK_LAUNCH("sac_bc_loss");
+  return DGVIT_OK;
+}
+
+int sac_cql_penalty(const float* q1_cat, const float* q2_cat, const float* q1_data, const float* q2_data, const float* log_w, const void* mask,
+                    int mask_u8, const float* log_weight, float weight, float temperature, float target_gap, int lagrange, float* out,
+                    float* grads, float* dlog_weight, int B, int M, int C, hipStream_t stream) {
+  DGVIT_CHECK_ARG(q1_cat && q2_cat && q1_data && q2_data && out, "sac_cql_penalty: q1_cat, q2_cat, q1_data, q2_data and out must not be null");
+  DGVIT_CHECK_ARG(mask_u8 == 0 || mask_u8 == 1, "sac_cql_penalty: mask_u8=%d must be 0 or 1", mask_u8);
+  DGVIT_CHECK_ARG(lagrange == 0 || lagrange == 1, "sac_cql_penalty: lagrange=%d must be 0 or 1", lagrange);
+  DGVIT_CHECK_ARG(B >= 1, "sac_cql_penalty: B=%d must be at least 1", B);
+  DGVIT_CHECK_ARG(M >= 1, "sac_cql_penalty: M=%d must be at least 1", M);
+  DGVIT_CHECK_ARG(C >= 1 && C <= SAC_MAX_ACTIONS, "sac_cql_penalty: C=%d must be in [1, %d]", C, SAC_MAX_ACTIONS);
+  DGVIT_CHECK_ARG((long long)B * ((long long)M + 1) * C <= SAC_MAX_ELEMS, "sac_cql_penalty: B*(M+1)*C=%lld must be at most %lld",
+                  (long long)B * ((long long)M + 1) * C, SAC_MAX_ELEMS);
+  DGVIT_CHECK_ARG(std::isfinite(temperature) && temperature > 0.f, "sac_cql_penalty: temperature=%g must be finite and positive", (double)temperature);
+  DGVIT_CHECK_ARG(log_weight || std::isfinite(weight), "sac_cql_penalty: weight=%g must be finite (or log_weight given)", (double)weight);
+  DGVIT_CHECK_ARG(!lagrange || log_weight, "sac_cql_penalty: the Lagrange form needs log_weight (it is null)");
+  DGVIT_CHECK_ARG(!lagrange || std::isfinite(target_gap), "sac_cql_penalty: target_gap=%g must be finite", (double)target_gap);
+  DGVIT_CHECK_ARG(lagrange || !dlog_weight, "sac_cql_penalty: dlog_weight belongs to the Lagrange form (lagrange=0)");
+  DGVIT_CHECK_ARG(al4p(q1_cat) && al4p(q2_cat) && al4p(q1_data) && al4p(q2_data) && al4p(log_w) && (mask_u8 || al4p(mask)) && al4p(log_weight) &&
+                      al4p(out) && al4p(grads) && al4p(dlog_weight),
+                  "sac_cql_penalty: pointers must be 4-byte aligned");
+  {
+    ProfileScope t(PROF_OTHER, 0.0, stream);
+    hipLaunchKernelGGL(sac_cql_penalty_kernel, dim3(1), dim3(256), 0, stream, q1_cat, q2_cat, q1_data, q2_data, log_w, mask, mask_u8, log_weight,
+                       weight, temperature, target_gap, lagrange, out, grads, dlog_weight, B, M, C);
+  }
+  DGVIT_CHECK_LAUNCH("sac_cql_penalty");
   return DGVIT_OK;
 }
 

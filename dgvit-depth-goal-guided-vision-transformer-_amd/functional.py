@@ -445,9 +445,95 @@ class _MlpHead(torch.autograd.Function):
         return (None, None, None, *din, *dpar)
 
 
-def mlp_head_supported(xs, towers):
-    """The fused head kernels take hidden widths that are multiples of 32 up to 128, at most 4 outputs and 512 inputs."""
+MAX_HEAD_SHARE = 256        # heads.hip: HMAXSHARE
+
+
+def _head_share(xs, share, what="mlp_head"):
+    """``share`` after its checks -> (M, head rows): one count per piece, each 1 or one common M <= MAX_HEAD_SHARE, and every piece holds
+    head rows / share[s] rows"""
+    if not isinstance(share, (list, tuple)) or len(share) != len(xs) or any(isinstance(m, bool) or not isinstance(m, int) or m < 1 for m in share):
+        raise ValueError(f"{what}: share must hold one int >= 1 per input piece ({len(xs)}), got {share!r}")
+    M = max(share)
+    if any(m not in (1, M) for m in share) or M > MAX_HEAD_SHARE:
+        raise ValueError(f"{what}: every share count is 1 or one common M <= {MAX_HEAD_SHARE}, got {list(share)}")
+    rows = xs[0].shape[0] * share[0]
+    if any(x.dim() != 2 or x.shape[0] * m != rows for x, m in zip(xs, share)):
+        raise ValueError(f"{what}: piece s must be (rows / share[s], k_s) for one number of head rows, got "
+                         f"{[tuple(x.shape) for x in xs]} with share {list(share)}")
+    return M, rows
+
+
+class _MlpHeadShared(torch.autograd.Function):
+    """``_MlpHead`` on B * M head rows of which the pieces with share[s] = M hold B rows, read in place by the M rows of their state
+    (dgvit_mlp_head_forward_shared / _backward_shared).  The gradient of a shared piece is (B, k): the M per-row gradients
+    of a state summed in fp32 in row order."""
+
+    @staticmethod
+    def forward(ctx, nseg, towers, heads3, share, *tensors):
+        lib = _lib.load()
+        xs = [_dev(t, f"head input {i}") for i, t in enumerate(tensors[:nseg])]
+        params = [_dev(t, f"head parameter {i}") for i, t in enumerate(tensors[nseg:])]
+        per = 4 + 2 * heads3
+        if len(params) != towers * per:
+            raise DgvitError(f"mlp_head: expected {towers * per} parameter tensors, got {len(params)}")
+        _, B = _head_share(xs, share)
+        n1, n2, n3 = params[0].shape[0], params[2].shape[0], params[4].shape[0]
+        K0 = sum(x.shape[1] for x in xs)
+        for t in range(towers):
+            q = params[t * per:(t + 1) * per]
+            ok = (q[0].shape == (n1, K0) and q[1].shape == (n1,) and q[2].shape == (n2, n1) and q[3].shape == (n2,)
+                  and all(q[4 + 2 * j].shape == (n3, n2) and q[5 + 2 * j].shape == (n3,) for j in range(heads3)))
+            if not ok or any(x.stride(1) != 1 for x in xs):
+                raise DgvitError("mlp_head: inconsistent input / parameter shapes")
+        desc = _mlp_desc(B, xs, n1, n2, n3, towers, heads3)
+        sh = (ctypes.c_int * nseg)(*share)
+        dev = xs[0].device
+        h1 = torch.empty(towers, B, n1, dtype=torch.float32, device=dev)
+        h2 = torch.empty(towers, B, n2, dtype=torch.float32, device=dev)
+        y = torch.empty(towers, heads3, B, n3, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dgvit_mlp_head_forward_shared(ctypes.byref(desc), sh, _table(xs), _table(params), _ptr(h1), _ptr(h2), _ptr(y), _stream())
+        _lib.check(rc, "dgvit_mlp_head_forward_shared")
+        ctx.meta = (nseg, towers, heads3, n1, n2, n3, tuple(share), B)
+        ctx.save_for_backward(h1, h2, *xs, *params)
+        ctx.set_materialize_grads(False)
+        return tuple(y[t, j] for t in range(towers) for j in range(heads3))
+
+    @staticmethod
+    def backward(ctx, *dys):
+        lib = _lib.load()
+        nseg, towers, heads3, n1, n2, n3, share, B = ctx.meta
+        h1, h2, *rest = ctx.saved_tensors
+        xs, params = rest[:nseg], rest[nseg:]
+        dys = [None if g is None else _dev(g, "dy") for g in dys]
+        dev = xs[0].device
+        need = ctx.needs_input_grad[4:]
+        if all(g is None for g in dys):
+            return (None,) * (4 + nseg + len(params))
+        din = [torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=dev) if need[i] else None for i, x in enumerate(xs)]
+        per = 4 + 2 * heads3
+        dpar = []
+        for i, p in enumerate(params):
+            t, q = divmod(i, per)
+            unused = q >= 4 and dys[t * heads3 + (q - 4) // 2] is None
+            dpar.append(torch.empty_like(p) if need[nseg + i] and not unused else None)
+        desc = _mlp_desc(B, xs, n1, n2, n3, towers, heads3)
+        sh = (ctypes.c_int * nseg)(*share)
+        nsc = lib.dgvit_mlp_head_backward_shared_scratch_floats(ctypes.byref(desc), sh)
+        scratch = torch.empty(max(int(nsc), 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dgvit_mlp_head_backward_shared(ctypes.byref(desc), sh, _table(xs), _table(params), _ptr(h1), _ptr(h2), _grad_table(dys),
+                                                    _grad_table(din), _grad_table(dpar), _ptr(scratch), scratch.numel(), _stream())
+        _lib.check(rc, "dgvit_mlp_head_backward_shared")
+        return (None, None, None, None, *din, *dpar)
+
+
+def mlp_head_supported(xs, towers, share=None):
+    """The fused head kernels take hidden widths that are multiples of 32 up to 128, at most 4 outputs and 512 inputs; shared pieces
+    (``share``, see ``mlp_head``) in groups of at most MAX_HEAD_SHARE rows."""
     if not (1 <= len(xs) <= 3 and 1 <= len(towers) <= 2):
+        return False
+    if share is not None and (len(share) != len(xs) or max(share) > MAX_HEAD_SHARE or any(m not in (1, max(share)) for m in share)):
         return False
     l1, l2, l3s = towers[0]
     n1, n2, n3 = l1.weight.shape[0], l2.weight.shape[0], l3s[0].weight.shape[0]
@@ -455,9 +541,14 @@ def mlp_head_supported(xs, towers):
             and sum(x.shape[1] for x in xs) <= 512 and all(x.shape[0] > 0 for x in xs))
 
 
-def mlp_head(xs, towers):
+def mlp_head(xs, towers, share=None):
     """Fused SAC head.  ``xs``: 1-3 (B, k_i) tensors that the reference concatenates along dim 1; ``towers``: 1 or 2 tuples
-    ``(fc1, fc2, [third layers])`` of nn.Linear modules.  Returns [[y (B, n3) of third layer j of tower t]]."""
+    ``(fc1, fc2, [third layers])`` of nn.Linear modules.  Returns [[y (B, n3) of third layer j of tower t]].
+
+    ``share`` (one int per piece, each 1 or one common M <= 256): piece s with ``share[s] = M`` holds B / M rows and head row r reads its
+    row r // M, as if the piece were ``x.repeat_interleave(M, 0)``, which is never made: the outputs and every gradient but the shared
+    piece's own are bit-equal to that call, and the shared piece's gradient is (B / M, k), the M rows of a state summed in fp32 in row
+    order.  ``None`` or all ones is the unshared call."""
     flat = []
     for l1, l2, l3s in towers:
         flat += [l1.weight, l1.bias, l2.weight, l2.bias]
@@ -465,7 +556,10 @@ def mlp_head(xs, towers):
             flat += [l3.weight, l3.bias]
     xs = [x if x.stride(-1) == 1 else x.contiguous() for x in xs]
     nh = len(towers[0][2])
-    ys = _MlpHead.apply(len(xs), len(towers), nh, *xs, *flat)
+    if share is not None and _head_share(xs, share)[0] > 1:
+        ys = _MlpHeadShared.apply(len(xs), len(towers), nh, tuple(share), *xs, *flat)
+    else:
+        ys = _MlpHead.apply(len(xs), len(towers), nh, *xs, *flat)
     return [list(ys[t * nh:(t + 1) * nh]) for t in range(len(towers))]
 
 

@@ -14,6 +14,12 @@ Learning from demonstrations: ``bc_loss`` and ``nll_loss`` are the
     bc = bc_loss(pi, batch["act"], mask=batch["source"] == 1)            # BCLoss(loss, used)
     (policy_loss + lam * bc.loss).backward()
 
+Conservative Q-learning: ``cql_penalty`` is the CQL(H) term of a critic loss over the Q-values of M proposal actions per
+state, ``q_many`` of the critics on ``sample_many`` draws and uniform actions:
+
+    cql = cql_penalty(q1_cat, q2_cat, q1, q2, log_w=log_w, weight=5.0)             # CQLLoss(loss, weight_loss, gap, used)
+    (out.loss + cql.loss).backward()
+
 The temperature is either the float ``alpha=`` or ``exp(log_alpha[0])`` read from device memory when the kernel runs (``log_alpha=``, a
 one-element fp32 device tensor): nothing here synchronises with the host, and a step captured by ``GraphedStep`` follows a ``log_alpha``
 that an optimiser changes between replays.  fp32 tensors on a ROCm device only; there is no CPU path.
@@ -29,6 +35,7 @@ from .functional import _dev, _ptr, _stream
 CriticLoss = namedtuple("CriticLoss", ["loss", "td", "target"])
 ActorLoss = namedtuple("ActorLoss", ["policy_loss", "alpha_loss"])
 BCLoss = namedtuple("BCLoss", ["loss", "used"])
+CQLLoss = namedtuple("CQLLoss", ["loss", "weight_loss", "gap", "used"])
 
 MAX_ACTIONS, MAX_ELEMS = 16, 1 << 20      # sac_loss.hip
 
@@ -268,3 +275,77 @@ def nll_loss(log_prob, *, mask=None):
         got = tuple(log_prob.shape) if isinstance(log_prob, torch.Tensor) else type(log_prob).__name__
         raise ValueError(f"{what}: log_prob must be (B, 1) or (B,) with 1 <= B <= {MAX_ELEMS}, got {got}")
     return _bc(what, log_prob, None, mask, [("q", None)] * 4, True, log_prob.shape[0], 1)
+
+
+def cql_penalty(q1_cat, q2_cat, q1_data, q2_data, *, log_w=None, temperature=1.0, weight=None, log_weight=None, target_gap=None, mask=None):
+    """``CQLLoss(loss, weight_loss, gap, used)``: the CQL(H) penalty of a twin critic, one launch (``dgvit_sac_cql_penalty``):
+
+        z        = q_cat[b, m, c] - log_w[b, m]                      q*_cat (B, M, C): the critic at M proposal actions per state
+        lse[b,c] = T log sum_m exp(z / T)                            T = temperature; max-subtracted, in double
+        gap_i    = sum_{b used, c} (lse_i - q_data_i) / (used C)     q*_data (B, C): the critic at the stored action; i = 1, 2
+        loss     = w (gap_1 + gap_2)
+
+    ``log_w`` (B, M) is the log-density of the proposal that drew action m: ``-sum_a log(2 scale_a)`` for uniform draws on the action box,
+    ``log_prob`` for policy draws (``sample_many``); ``None`` is 0.  ``mask`` ((B,) or (B, 1), bool or fp32 weights, as ``bc_loss`` takes
+    it) picks the rows the penalty applies to; ``used`` is their count, a 0-d device tensor.  ``w`` is the float ``weight=`` or
+    ``exp(log_weight[0])``, read on the device when the kernel runs (exactly one of the two).  With ``log_weight=`` and ``target_gap=tau``
+    this is the Lagrange form:
+
+        loss        = w (gap_1 + gap_2 - 2 tau)                      w a constant here
+        weight_loss = -exp(log_weight) (gap_1 + gap_2 - 2 tau)       differentiable in log_weight only, the gaps detached
+
+    otherwise ``weight_loss`` is ``None``.  ``gap`` is (2,), detached.  ``loss`` is differentiable in q*_cat (w softmax_m(z / T) / (used C)
+    on the used rows) and q*_data (-w / (used C)); nothing flows to ``log_w``.  When no row is used every output and gradient is an exact
+    zero, never NaN.  Nothing synchronises with the host: a step captured by ``GraphedStep`` follows ``log_weight`` and ``mask``."""
+    what = "cql_penalty"
+    if (weight is None) == (log_weight is None):
+        raise ValueError(f"{what}: give exactly one of weight= (a float) and log_weight= (a one-element fp32 device tensor)")
+    if log_weight is None:
+        if isinstance(weight, (bool, torch.Tensor)) or not isinstance(weight, (int, float)) or not math.isfinite(weight):
+            raise ValueError(f"{what}: weight must be a finite float (a device-side weight goes in as log_weight=), got {weight!r}")
+        if target_gap is not None:
+            raise ValueError(f"{what}: target_gap needs log_weight= (the Lagrange multiplier's loss is a function of log_weight)")
+    elif not isinstance(log_weight, torch.Tensor) or log_weight.numel() != 1:
+        raise ValueError(f"{what}: log_weight must be a one-element tensor")
+    if target_gap is not None and (isinstance(target_gap, bool) or not isinstance(target_gap, (int, float)) or not math.isfinite(target_gap)):
+        raise ValueError(f"{what}: target_gap must be a finite float, got {target_gap!r}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{what}: temperature must be a finite float > 0, got {temperature!r}")
+    if not isinstance(q1_cat, torch.Tensor) or q1_cat.dim() != 3:
+        got = tuple(q1_cat.shape) if isinstance(q1_cat, torch.Tensor) else type(q1_cat).__name__
+        raise ValueError(f"{what}: q1_cat must be (B, M, C), got {got}")
+    B, M, C = q1_cat.shape
+    if B < 1 or M < 1 or not 1 <= C <= MAX_ACTIONS or B * (M + 1) * C > MAX_ELEMS:
+        raise ValueError(f"{what}: q1_cat is {(B, M, C)}; needs 1 <= B, 1 <= M, 1 <= C <= {MAX_ACTIONS} and B * (M + 1) * C <= {MAX_ELEMS}")
+    for name, t, shape in (("q2_cat", q2_cat, (B, M, C)), ("q1_data", q1_data, (B, C)), ("q2_data", q2_data, (B, C)), ("log_w", log_w, (B, M))):
+        if (t is not None or name != "log_w") and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape):
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be {shape}, got {got}")
+    mk, u8 = _mask(mask, what, B)
+    named = [("q1_cat", q1_cat), ("q2_cat", q2_cat), ("q1_data", q1_data), ("q2_data", q2_data), ("log_w", None if log_w is None else log_w.detach()),
+             ("log_weight", None if log_weight is None else log_weight.detach())]
+    _same_device(what, named + [("mask", mk)])
+    c1, c2, d1, d2, lw, lwt = _on_device(named)
+    inputs = (q1_cat, q2_cat, q1_data, q2_data)
+    grad_on = torch.is_grad_enabled()
+    need = grad_on and any(t.requires_grad for t in inputs)
+    lagrange = target_gap is not None
+    need_w = grad_on and lagrange and log_weight.requires_grad
+    dev = c1.device
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    grads = torch.empty(2 * B * M * C + 2 * B * C, dtype=torch.float32, device=dev) if need else None
+    dlw = torch.empty(1, dtype=torch.float32, device=dev) if need_w else None
+    with torch.cuda.device(dev):
+        rc = _lib.load().dgvit_sac_cql_penalty(_ptr(c1), _ptr(c2), _ptr(d1), _ptr(d2), _ptr(lw), _ptr(mk), u8, _ptr(lwt),
+                                               float(weight or 0.0), float(temperature), float(target_gap or 0.0), int(lagrange), _ptr(out),
+                                               _ptr(grads), _ptr(dlw), B, M, C, _stream())
+    _lib.check(rc, "dgvit_sac_cql_penalty")
+    loss = out[0]
+    if need:
+        loss = _Precomputed.apply(loss, grads, q1_cat, q2_cat, q1_data, q2_data)
+    wl = None
+    if lagrange:
+        wl = out[1]
+        if need_w:
+            wl = _Precomputed.apply(wl, dlw, log_weight)
+    return CQLLoss(loss, wl, out[2:4], out[4])

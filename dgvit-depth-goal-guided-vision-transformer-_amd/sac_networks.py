@@ -37,12 +37,17 @@ def _lin(layer, x, relu=False):
     return F_.linear(x, layer.weight, layer.bias, relu=relu)
 
 
-def _head(xs, towers):
+def _head(xs, towers, share=None):
     """relu(fc1) -> relu(fc2) -> third layer(s) on cat(xs): ONE fused HIP launch each way when the widths fit the fused head
     kernel (every network of the reference does), else the same arithmetic as a chain of MFMA GEMM launches.
-    Returns [[y of third layer j of tower t]]."""
-    if xs[0].shape[0] > 0 and F_.mlp_head_supported(xs, towers):
-        return F_.mlp_head(xs, towers)
+    Returns [[y of third layer j of tower t]].  ``share``: see ``functional.mlp_head``; the chain repeats the shared pieces."""
+    if share is None:
+        if xs[0].shape[0] > 0 and F_.mlp_head_supported(xs, towers):
+            return F_.mlp_head(xs, towers)
+    elif xs[0].shape[0] > 0 and F_.mlp_head_supported(xs, towers, share):
+        return F_.mlp_head(xs, towers, share)
+    else:
+        xs = [x if m == 1 else x.repeat_interleave(m, 0) for x, m in zip(xs, share)]
     x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
     out = []
     for l1, l2, l3s in towers:
@@ -81,6 +86,36 @@ def _log_prob(module, mean, log_std_raw, action):
     if scale.device != mean.device:
         module.action_scale, module.action_bias = scale, bias = scale.to(mean.device), bias.to(mean.device)
     return F_.tanh_gaussian_log_prob(mean, log_std_raw, action, scale, bias, LOG_SIG_MIN, LOG_SIG_MAX)
+
+
+def _many_actions(inp, actions, nb_actions):
+    """the checks of q_many, on the host before anything runs -> (istate, pstate, B, M)"""
+    want = f"(B, M, nb_actions) = (B, M, {nb_actions}) with 1 <= M <= {F_.MAX_HEAD_SHARE}"
+    if not isinstance(inp, (list, tuple)) or len(inp) != 2:
+        raise ValueError(f"q_many: inp must be [istate, pstate] (the actions go in as the {want} second argument)")
+    istate, pstate = inp
+    if not torch.is_tensor(actions) or actions.dim() != 3 or actions.shape[2] != nb_actions or not 1 <= actions.shape[1] <= F_.MAX_HEAD_SHARE:
+        got = tuple(actions.shape) if torch.is_tensor(actions) else type(actions).__name__
+        raise ValueError(f"q_many: actions must be {want}, got {got}")
+    if actions.dtype != torch.float32 or not actions.is_contiguous():
+        raise ValueError(f"q_many: actions must be contiguous float32 {want}, got {actions.dtype}{'' if actions.is_contiguous() else ', not contiguous'}")
+    if not torch.is_tensor(pstate) or pstate.dim() != 2 or pstate.shape[0] != actions.shape[0]:
+        got = tuple(pstate.shape) if torch.is_tensor(pstate) else type(pstate).__name__
+        raise ValueError(f"q_many: pstate must be (B, nb_pstate) with the B = {actions.shape[0]} of actions {tuple(actions.shape)}, got {got}")
+    if not torch.is_tensor(istate) or istate.dim() < 3 or istate.shape[0] != actions.shape[0]:
+        got = tuple(istate.shape) if torch.is_tensor(istate) else type(istate).__name__
+        raise ValueError(f"q_many: istate must be a batch of B = {actions.shape[0]} frames, one per row of actions {tuple(actions.shape)}, got {got}")
+    return istate, pstate, actions.shape[0], actions.shape[1]
+
+
+def _sample_many(module, inp, n):
+    """sample_many of the tanh-Gaussian policies: one encoder and head pass, then sample()'s launch on the head outputs repeated n times"""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"sample_many: n must be an int >= 1 (the result is (B, n, nb_actions)), got {n!r}")
+    mean, log_std_raw = module._head_outputs(inp)
+    B, A = mean.shape
+    action, log_prob, tanh_mean = _tanh_gaussian(module, mean.repeat_interleave(n, 0), log_std_raw.repeat_interleave(n, 0))
+    return action.view(B, n, A), log_prob.view(B, n), tanh_mean.view(B, n, A)[:, 0]
 
 
 def _action_affine(action_space):
@@ -128,6 +163,19 @@ class GoTQNetwork(nn.Module):
         feat = self.trans(istate, goal)
         (q1,), (q2,) = _head([feat.view(feat.size(0), -1), a], [(self.fc1, self.fc2, [self.fc3]), (self.fc11, self.fc21, [self.fc31])])
         return q1, q2
+
+    def q_many(self, inp, actions):
+        """``(q1, q2)``, each (B, M, nb_actions): both critics for M actions per state, ``actions`` a contiguous fp32 (B, M, nb_actions)
+        device tensor and ``inp = [istate, pstate]`` -- the Q(s, a_m) of a CQL penalty (``sac_losses.cql_penalty``) or of a best-of-N
+        evaluation (argmax over dim 1).  The encoder runs ONCE on the B frames; the fused head runs on the B * M rows and reads each
+        state's features in place (``functional.mlp_head(share=)``).  Bit-equal to forward() on frames repeated M times, at the
+        encoder's cost for B; differentiable in the parameters, in ``actions`` and in the frame where it asks for a gradient."""
+        istate, pstate, B, M = _many_actions(inp, actions, self.fc3.out_features)
+        goal = _lin(self.fc_embed, pstate, relu=True)
+        feat = self.trans(istate, goal)
+        (q1,), (q2,) = _head([feat.view(feat.size(0), -1), actions.view(B * M, -1)],
+                             [(self.fc1, self.fc2, [self.fc3]), (self.fc11, self.fc21, [self.fc31])], share=[M, 1])
+        return q1.view(B, M, -1), q2.view(B, M, -1)
 
     def attention_maps(self, inp, rows="goal"):
         """(features, maps) of the encoder (GoT.attention_maps) for the goal embedding forward computes; ``inp`` is [istate, pstate] or
@@ -198,6 +246,12 @@ class GoTPolicy(nn.Module):
         log-density as ONE HIP launch behind the head (no Normal object: its argument check alone is a host sync per call)."""
         mean, log_std_raw = self._head_outputs(inp)
         return _tanh_gaussian(self, mean, log_std_raw)
+
+    def sample_many(self, inp, n):
+        """``(action (B, n, nb_actions), log_prob (B, n), tanh_mean (B, nb_actions))``: n draws per state from ONE encoder and head pass,
+        ``sample``'s launch on the head outputs repeated n times (row b * n + j is draw j of state b).  The proposals of a CQL penalty:
+        ``log_prob`` is their ``log_w``."""
+        return _sample_many(self, inp, n)
 
     def log_prob(self, inp, action):
         """``log pi(action | inp)``, (B, 1): the density ``sample`` reports, at a given ``action`` (B, nb_actions) -- a demonstration's --

@@ -259,6 +259,26 @@ int dgvit_mlp_head_backward(const dgvit_mlp_desc* desc, const float* const* in, 
                             const float* h2, const float* const* dy, float* const* din, float* const* dparams, float* scratch,
                             long long scratch_floats, void* stream);
 
+/* Shared input pieces: the same head for batch = B * M head rows of which some input pieces hold only B rows -- Q(s, a_m) for M actions
+ * per state (CQL, best-of-N): the encoder features of a state are read in place by its M rows, no M-fold copy is made.
+ *   share     : const int[nseg].  share[s] = 1: piece s has `batch` rows, as above.  share[s] = M: piece s has batch / M rows (row stride
+ *               ldx[s]) and head row r reads its row r / M -- the layout of repeat_interleave(M, 0).  Every share[s] is 1 or one common M,
+ *               1 <= M <= 256, batch % M == 0; every restriction above stays.  DGVIT_ERR_ARG otherwise, before any launch.
+ *   forward   : h1, h2, y bit-equal to dgvit_mlp_head_forward on the materialised inputs (the workgroup's LDS image is the same).
+ *   backward  : dparams and the din of every share[s] = 1 piece bit-equal to dgvit_mlp_head_backward on the materialised inputs.  The
+ *               din of a shared piece is (batch / M, kx[s]), dense:  din[b][k] = ((dx[bM][k] + dx[bM+1][k]) + ...) + dx[bM+M-1][k]  in
+ *               fp32 in this order, dx[r] the value the unshared backward returns for head row r (tower 0 + tower 1 for a twin head).
+ *               The rows go to scratch and one small kernel sums them: no atomics, the same bits on every call.
+ *   scratch   : dgvit_mlp_head_backward_shared_scratch_floats(desc, share) floats (-1 for a bad desc / share): the unshared call's plus
+ *               batch * kx[s] (rounded up to 4) per shared piece.
+ * A share of all ones IS the unshared call: the same launches, the same bits, the same scratch. */
+int dgvit_mlp_head_forward_shared(const dgvit_mlp_desc* desc, const int* share, const float* const* in, const float* const* params, float* h1,
+                                  float* h2, float* y, void* stream);
+long long dgvit_mlp_head_backward_shared_scratch_floats(const dgvit_mlp_desc* desc, const int* share);
+int dgvit_mlp_head_backward_shared(const dgvit_mlp_desc* desc, const int* share, const float* const* in, const float* const* params,
+                                   const float* h1, const float* h2, const float* const* dy, float* const* din, float* const* dparams,
+                                   float* scratch, long long scratch_floats, void* stream);
+
 /* tanh-Gaussian action sampling of GoTPolicy.sample / GaussianPolicy.sample (got_sac_network.py:238-251, 310-321) in one launch:
  *   ls = clamp(log_std_raw, ls_min, ls_max); x = mean + exp(ls) * eps; y = tanh(x); action = y * scale + bias;
  *   log_prob (B) = sum_a [Normal(mean, exp(ls)).log_prob(x) - log(scale * (1 - y^2) + 1e-6)];  tanh_mean = tanh(mean) * scale + bias.
@@ -825,6 +845,18 @@ int dgvit_adam_step_groups(float* p, const float* g, float* m, float* v, long lo
  *     grads  = d out[0] / d pred for a unit upstream gradient, B A floats (NULL: not wanted): 2 m f (pred - action) / (A used), or
  *              -m f / used with nll; all zeros when used == 0.  A row with m f == 0 adds nothing whatever its l: never NaN from it.
  *   One workgroup, double sums in a fixed order as the two kernels above; nothing is produced for action, mask or the q.
+ * dgvit_sac_cql_penalty: the conservative term of a CQL(H) critic loss over M proposal actions per row.  q1_cat, q2_cat: (B, M, C);
+ *   q1_data, q2_data: (B, C); log_w: (B, M) log-density of the proposal that drew action m (NULL: 0); mask as dgvit_sac_bc_loss (m[b]).
+ *     z[b,m,c] = q_cat[b,m,c] - log_w[b,m];    lse[b,c] = T log sum_m exp(z / T)   (max-subtracted, T = temperature > 0)
+ *     used     = sum_b m[b];    gap_i = sum_{b,c} m[b] (lse_i[b,c] - q_data_i[b,c]) / (used C)              i = 1, 2 (the two critics)
+ *     w        = exp(log_weight[0]) read on the device and taken in double (log_weight != NULL), else the float `weight`
+ *     out      = [ w (gap_1 + gap_2 - 2 tau), -w (gap_1 + gap_2 - 2 tau) (lagrange == 1, else 0), gap_1, gap_2, used ]     5 floats
+ *                tau = target_gap with lagrange == 1 (needs log_weight), 0 otherwise.  out[0] treats w as a constant; out[1] is the
+ *                Lagrange multiplier's loss, a function of log_weight alone, and dlog_weight[0] = out[1] its derivative (NULL: not wanted)
+ *     grads    = [dq1_cat (BMC) | dq2_cat (BMC) | dq1_data (BC) | dq2_data (BC)] of out[0] for a unit upstream gradient (NULL: not
+ *                wanted): d q_cat = w m[b] softmax_m(z / T) / (used C), d q_data = -w m[b] / (used C); exact zeros where m[b] == 0
+ *   used == 0 gives out = 0 and zero gradients, never NaN.  1 <= B, 1 <= M, 1 <= C <= 16, B (M + 1) C <= 2^20.  One workgroup, every term
+ *   in double from the fp32 inputs in a fixed order; nothing is produced for log_w or mask.
  * -------------------------------------------------------------------------------------------- */
 int dgvit_sac_critic_loss(const float* q1, const float* q2, const float* reward, const float* done, const float* weights,
                           const float* next_q1, const float* next_q2, const float* next_log_pi, const float* log_alpha, float alpha,
@@ -839,6 +871,9 @@ int dgvit_sac_actor_loss(const float* log_pi, const float* q1_pi, const float* q
 int dgvit_sac_scale_grads(const float* src, float* dst, long long n, const float* scale_dev, void* stream);
 int dgvit_sac_bc_loss(const float* pred, const float* action, const void* mask, int mask_u8, const float* q1_demo, const float* q2_demo,
                       const float* q1_pi, const float* q2_pi, int nll, float* out, float* grads, int B, int A, void* stream);
+int dgvit_sac_cql_penalty(const float* q1_cat, const float* q2_cat, const float* q1_data, const float* q2_data, const float* log_w,
+                          const void* mask, int mask_u8, const float* log_weight, float weight, float temperature, float target_gap,
+                          int lagrange, float* out, float* grads, float* dlog_weight, int B, int M, int C, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * bf16 configuration (BASELINE.json config 5: 224x224 depth frames, 12-layer ViT-Base variant with goal token, bf16).
