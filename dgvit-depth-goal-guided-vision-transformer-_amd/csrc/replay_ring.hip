@@ -794,6 +794,46 @@ int check_slots(const char* name, long long n, long long nrows, long long start)
   return DGVIT_OK;
 }
 
+// the lanes and the pool of a shared ring, and a store's place in them: what ring_plan_next and ring_store_frames_shared ask alike
+int check_shared(const char* name, long long n, long long nrows, long long start, long long envs, long long pool) {
+  if (const int rc = check_slots(name, n, nrows, start)) return rc;
+  DGVIT_CHECK_ARG(envs >= 1 && envs <= nrows && nrows % envs == 0, "%s: envs=%lld must be in [1, nrows] and divide nrows=%lld", name, envs, nrows);
+  DGVIT_CHECK_ARG(n % envs == 0 && start % envs == 0, "%s: n=%lld and start=%lld must be multiples of envs=%lld", name, n, start, envs);
+  DGVIT_CHECK_ARG(pool >= 1 && pool <= nrows, "%s: pool=%lld must be in [1, nrows] = [1, %lld]", name, pool, nrows);
+  DGVIT_CHECK_ARG(nrows + envs + pool < (1ll << 31), "%s: the arena's nrows + envs + pool = %lld rows must be below 2^31", name,
+                  nrows + envs + pool);
+  return DGVIT_OK;
+}
+
+// What ring_store_frames and ring_store_frames_shared ask alike, in the one order of both: the sources, the slots (`shared`: check_shared
+// with envs and pool, else check_slots) and the ring's rows.  The entry point's own pointers come in as `set` and `aligned`, and as the
+// words it has for them in the two messages, `theirs` and `their_alignment`.
+int check_frame_store(const char* name, bool shared, const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8,
+                      long long src1_ld, bool set, const char* theirs, bool aligned, const char* their_alignment, int ring_u8,
+                      long long ring_ld, long long n, long long cols, long long nrows, long long start, long long envs, long long pool) {
+  DGVIT_CHECK_ARG(src0 && src1 && set, "%s: src0, src1, %s must not be null", name, theirs);
+  DGVIT_CHECK_ARG((src0_u8 | src1_u8 | ring_u8) >> 1 == 0, "%s: src0_u8=%d, src1_u8=%d and ring_u8=%d must be 0 or 1", name, src0_u8, src1_u8,
+                  ring_u8);
+  DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "%s: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring", name, src0_u8, src1_u8);
+  if (const int rc = shared ? check_shared(name, n, nrows, start, envs, pool) : check_slots(name, n, nrows, start)) return rc;
+  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "%s: cols=%lld must be in [1, 2^25]", name, cols);
+  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
+                  "%s: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", name, ring_ld, ring_u8 ? 16 : 4, cols);
+  DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "%s: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld", name, src0_ld, src1_ld,
+                  cols);
+  DGVIT_CHECK_ARG(aligned && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)), "%s: %s and fp32 sources 4-byte aligned", name,
+                  their_alignment);
+  DGVIT_CHECK_ARG((n * (ring_ld / 4) + 255) / 256 < (1ll << 31), "%s: n=%lld rows of ring_ld=%lld are more than one launch covers", name, n,
+                  ring_ld);
+  return DGVIT_OK;
+}
+
+// a frame field's rows as the two store kernels read them: whole groups of 4 pixels at once where the rows' alignment allows it
+frame_src make_frame_src(const void* p, int u8, long long ld) {
+  const bool vec = u8 ? (ld % 4 == 0 && al4p(p)) : (ld % 4 == 0 && al16(p));
+  return frame_src{p, ld, u8, (int)vec};
+}
+
 // both walks: `name` is the entry point's, `stride` null for nstep_walk, whose kernel has no such argument
 int launch_nstep_walk(const char* name, const float* rew, long long rew_ld, const float* done, long long done_ld, const unsigned char* flags,
                       const float* next_small, long long small_ld, const long long* idx, long long nsel, long long nrows,
@@ -918,28 +958,15 @@ int nstep_walk(const float* rew, long long rew_ld, const float* done, long long 
 int ring_store_frames(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* ring0,
                       void* ring1, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
                       hipStream_t stream) {
-  DGVIT_CHECK_ARG(src0 && src1 && ring0 && ring1, "ring_store_frames: src0, src1, ring0 and ring1 must not be null");
-  DGVIT_CHECK_ARG((src0_u8 | src1_u8 | ring_u8) >> 1 == 0, "ring_store_frames: src0_u8=%d, src1_u8=%d and ring_u8=%d must be 0 or 1", src0_u8,
-                  src1_u8, ring_u8);
-  DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "ring_store_frames: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring", src0_u8,
-                  src1_u8);
-  if (const int rc = check_slots("ring_store_frames", n, nrows, start)) return rc;
-  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_store_frames: cols=%lld must be in [1, 2^25]", cols);
-  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
-                  "ring_store_frames: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring_ld, ring_u8 ? 16 : 4,
-                  cols);
-  DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "ring_store_frames: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld", src0_ld,
-                  src1_ld, cols);
-  DGVIT_CHECK_ARG(al16(ring0) && al16(ring1) && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)),
-                  "ring_store_frames: the rings must be 16-byte and fp32 sources 4-byte aligned");
+  // the two spliced messages read "ring_store_frames: src0, src1, ring0 and ring1 must not be null" and "ring_store_frames: the rings must
+  // be 16-byte and fp32 sources 4-byte aligned" (tests/test_vec_replay_host.py matches them)
+  if (const int rc = check_frame_store("ring_store_frames", false, src0, src0_u8, src0_ld, src1, src1_u8, src1_ld, ring0 && ring1,
+                                       "ring0 and ring1", al16(ring0) && al16(ring1), "the rings must be 16-byte", ring_u8, ring_ld, n, cols,
+                                       nrows, start, 0, 0))
+    return rc;
   const int row4 = (int)(ring_ld / 4);   // groups of 4 pixels per ring row, a dword of bytes or a float4
   const long long total4 = n * row4, blocks = (total4 + 255) / 256;
-  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_store_frames: n=%lld rows of ring_ld=%lld are more than one launch covers", n, ring_ld);
-  const auto source = [](const void* p, int u8, long long ld) {
-    const bool vec = u8 ? (ld % 4 == 0 && al4p(p)) : (ld % 4 == 0 && al16(p));
-    return frame_src{p, ld, u8, (int)vec};
-  };
-  const frame_src s0 = source(src0, src0_u8, src0_ld), s1 = source(src1, src1_u8, src1_ld);
+  const frame_src s0 = make_frame_src(src0, src0_u8, src0_ld), s1 = make_frame_src(src1, src1_u8, src1_ld);
   if (ring_u8)
     hipLaunchKernelGGL(ring_store_frames_kernel<true>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, ring0, ring1, total4, row4,
                        (int)cols, nrows, start);
@@ -977,21 +1004,6 @@ int ring_store_small(const dgvit_small_fields& fields, unsigned char* flags, con
   return DGVIT_OK;
 }
 
-namespace {
-
-// the lanes and the pool of a shared ring, and a store's place in them: what ring_plan_next and ring_store_frames_shared ask alike
-int check_shared(const char* name, long long n, long long nrows, long long start, long long envs, long long pool) {
-  if (const int rc = check_slots(name, n, nrows, start)) return rc;
-  DGVIT_CHECK_ARG(envs >= 1 && envs <= nrows && nrows % envs == 0, "%s: envs=%lld must be in [1, nrows] and divide nrows=%lld", name, envs, nrows);
-  DGVIT_CHECK_ARG(n % envs == 0 && start % envs == 0, "%s: n=%lld and start=%lld must be multiples of envs=%lld", name, n, start, envs);
-  DGVIT_CHECK_ARG(pool >= 1 && pool <= nrows, "%s: pool=%lld must be in [1, nrows] = [1, %lld]", name, pool, nrows);
-  DGVIT_CHECK_ARG(nrows + envs + pool < (1ll << 31), "%s: the arena's nrows + envs + pool = %lld rows must be below 2^31", name,
-                  nrows + envs + pool);
-  return DGVIT_OK;
-}
-
-}  // namespace
-
 int ring_plan_next(int* next_row, long long* state, int* moves, const float* done, long long done_ld, const unsigned char* flags, long long n,
                    long long nrows, long long start, long long envs, long long pool, hipStream_t stream) {
   DGVIT_CHECK_ARG(next_row && state && moves && done && flags, "ring_plan_next: next_row, state, moves, done and flags must not be null");
@@ -1008,28 +1020,15 @@ int ring_plan_next(int* next_row, long long* state, int* moves, const float* don
 int ring_store_frames_shared(const void* src0, int src0_u8, long long src0_ld, const void* src1, int src1_u8, long long src1_ld, void* arena,
                              const int* moves, int ring_u8, long long ring_ld, long long n, long long cols, long long nrows, long long start,
                              long long envs, long long pool, hipStream_t stream) {
-  DGVIT_CHECK_ARG(src0 && src1 && arena && moves, "ring_store_frames_shared: src0, src1, arena and moves must not be null");
-  DGVIT_CHECK_ARG((src0_u8 | src1_u8 | ring_u8) >> 1 == 0, "ring_store_frames_shared: src0_u8=%d, src1_u8=%d and ring_u8=%d must be 0 or 1",
-                  src0_u8, src1_u8, ring_u8);
-  DGVIT_CHECK_ARG(ring_u8 || !(src0_u8 || src1_u8), "ring_store_frames_shared: uint8 sources (src0_u8=%d, src1_u8=%d) need a uint8 ring",
-                  src0_u8, src1_u8);
-  if (const int rc = check_shared("ring_store_frames_shared", n, nrows, start, envs, pool)) return rc;
-  DGVIT_CHECK_ARG(cols > 0 && cols <= (1ll << 25), "ring_store_frames_shared: cols=%lld must be in [1, 2^25]", cols);
-  DGVIT_CHECK_ARG(ring_ld % (ring_u8 ? 16 : 4) == 0 && ring_ld >= cols && ring_ld <= (1ll << 26),
-                  "ring_store_frames_shared: ring_ld=%lld must be a multiple of %d, at least cols=%lld and at most 2^26", ring_ld,
-                  ring_u8 ? 16 : 4, cols);
-  DGVIT_CHECK_ARG(src0_ld >= cols && src1_ld >= cols, "ring_store_frames_shared: src0_ld=%lld and src1_ld=%lld must be at least cols=%lld",
-                  src0_ld, src1_ld, cols);
-  DGVIT_CHECK_ARG(al16(arena) && al4p(moves) && (src0_u8 || al4p(src0)) && (src1_u8 || al4p(src1)),
-                  "ring_store_frames_shared: the arena must be 16-byte, moves and fp32 sources 4-byte aligned");
+  // the two spliced messages read "ring_store_frames_shared: src0, src1, arena and moves must not be null" and "ring_store_frames_shared:
+  // the arena must be 16-byte, moves and fp32 sources 4-byte aligned" (tests/test_shared_next_host.py matches them)
+  if (const int rc = check_frame_store("ring_store_frames_shared", true, src0, src0_u8, src0_ld, src1, src1_u8, src1_ld, arena && moves,
+                                       "arena and moves", al16(arena) && al4p(moves), "the arena must be 16-byte, moves", ring_u8, ring_ld, n,
+                                       cols, nrows, start, envs, pool))
+    return rc;
   const int row4 = (int)(ring_ld / 4);   // groups of 4 pixels per arena row, a dword of bytes or a float4
   const long long total4 = n * row4, blocks = (total4 + 255) / 256;
-  DGVIT_CHECK_ARG(blocks < (1ll << 31), "ring_store_frames_shared: n=%lld rows of ring_ld=%lld are more than one launch covers", n, ring_ld);
-  const auto source = [](const void* p, int u8, long long ld) {
-    const bool vec = u8 ? (ld % 4 == 0 && al4p(p)) : (ld % 4 == 0 && al16(p));
-    return frame_src{p, ld, u8, (int)vec};
-  };
-  const frame_src s0 = source(src0, src0_u8, src0_ld), s1 = source(src1, src1_u8, src1_ld);
+  const frame_src s0 = make_frame_src(src0, src0_u8, src0_ld), s1 = make_frame_src(src1, src1_u8, src1_ld);
   if (ring_u8)
     hipLaunchKernelGGL(ring_store_frames_shared_kernel<true>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, s0, s1, arena, moves, total4, row4,
                        (int)cols, nrows, start, n, envs, nrows + envs + pool);

@@ -32,6 +32,13 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _seed_args(seed):
+    """(host seed, device seed tensor or None) as the entry points with a seed take it: ``seed`` is a host int, or a 1-element int64
+    DEVICE tensor (graph capture: the kernel reads it at run time)"""
+    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    return (0 if seed_dev is not None else int(seed)), seed_dev
+
+
 def _table(tensors: Sequence[Optional[torch.Tensor]]):
     """device-pointer table; a None entry (an unused slot, e.g. to_out of a projection-less attention) is a NULL pointer"""
     return (ctypes.c_void_p * len(tensors))(*[0 if t is None else t.data_ptr() for t in tensors])
@@ -176,9 +183,7 @@ class _GoTEncoder(torch.autograd.Function):
             _lib.check(-1, "dgvit_got_workspace_floats")
         ws = torch.empty(nws, dtype=torch.float32, device=img.device)
         feat = torch.empty(B, cfg.dim, dtype=torch.float32, device=img.device)
-        # `seed` is a host int, or a 1-element int64 DEVICE tensor (graph capture: the kernel reads it at run time)
-        seed_dev = seed if isinstance(seed, torch.Tensor) else None
-        seed_val = 0 if seed_dev is not None else int(seed)
+        seed_val, seed_dev = _seed_args(seed)
         keep, lkeep = _keeps(keep)
         with torch.cuda.device(img.device):
             rc = lib.dgvit_got_forward_v2(ctypes.byref(cfg), _table(params), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws), nws, B,
@@ -935,8 +940,7 @@ def op_attention_bwd_bf16_tiled(qkv, out, dout, lse, heads, dim_head=64, *, delt
 
 def _drop_args(keep, seed, layer):
     """(keep, host seed, device seed tensor or None, layer) as the *_drop entry points take them"""
-    seed_dev = seed if isinstance(seed, torch.Tensor) else None
-    return float(keep), (0 if seed_dev is not None else int(seed)), seed_dev, int(layer)
+    return float(keep), *_seed_args(seed), int(layer)
 
 
 def op_attention_bf16_tiled_drop(qkv, heads, keep, seed, layer, dim_head=64, nq=None, want_lse=False, *, out=None, lse=None):
@@ -1122,8 +1126,7 @@ class _GoTEncoderBf16(torch.autograd.Function):
             _lib.check(-1, "dgvit_got_bf16_workspace_bytes")
         ws = torch.empty(nws, dtype=torch.uint8, device=img.device)
         feat = torch.empty(B, cfg.dim, dtype=torch.float32, device=img.device)
-        seed_dev = seed if isinstance(seed, torch.Tensor) else None
-        seed_val = 0 if seed_dev is not None else int(seed)
+        seed_val, seed_dev = _seed_args(seed)
         with torch.cuda.device(img.device):
             rc = lib.dgvit_got_forward_bf16_v2(ctypes.byref(cfg), _table(params), _ptr(wpack), _ptr(img), _ptr(goal), _ptr(feat), _ptr(ws),
                                                nws, B, int(need_grad), float(keep), lkeep, seed_val, _ptr(seed_dev), _stream())
@@ -1208,12 +1211,6 @@ def _empty_maps(cfg, rows, img, goal, params):
         if isinstance(t, torch.Tensor):
             _dev(t, "input")          # (a device-only path, as the forward's empty batch)
     return img.new_zeros(0, cfg.dim), img.new_zeros(_maps_shape(cfg, 0, rows))
-
-
-def _seed_args(seed):
-    """(host seed, device seed tensor or None) as the encoder forwards take them"""
-    seed_dev = seed if isinstance(seed, torch.Tensor) else None
-    return (0 if seed_dev is not None else int(seed)), seed_dev
 
 
 @torch.no_grad()

@@ -12,7 +12,7 @@ import numbers
 import torch
 
 from . import _lib
-from .functional import _dev, _ptr, _stream
+from .functional import _dev, _ptr, _seed_args, _stream
 
 
 def _frames(img):
@@ -140,10 +140,10 @@ def _gather_shift(src, idx, out, shifts, frame, nrows, pad, stream_id, seed):
     """dgvit_gather_shift_frames, or its _u8 form for a uint8 src, on the current stream (the caller has made src's device current): out
     (B, row) fp32 <- rows ``idx`` (None: 0..B-1) of src (nrows, src.shape[1]), each shifted by its own draw; ``seed`` is an int or a
     1-element int64 device tensor; ``shifts`` (B, 2) int32 or None receives (dy, dx)."""
-    seed_dev = seed if isinstance(seed, torch.Tensor) else None
+    seed_val, seed_dev = _seed_args(seed)
     name, row_bytes = ("dgvit_gather_shift_frames_u8", (src.shape[1],)) if src.dtype == torch.uint8 else ("dgvit_gather_shift_frames", ())
     rc = getattr(_lib.load(), name)(_ptr(src), _ptr(idx), _ptr(out), _ptr(shifts), out.shape[0], frame[0], frame[1], *row_bytes,
-                                    out.shape[1], nrows, pad, stream_id, 0 if seed_dev is not None else int(seed), _ptr(seed_dev), _stream())
+                                    out.shape[1], nrows, pad, stream_id, seed_val, _ptr(seed_dev), _stream())
     _lib.check(rc, name)
 
 

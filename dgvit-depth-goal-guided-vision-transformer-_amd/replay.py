@@ -18,7 +18,9 @@ stores such a step from device tensors without visiting the host.  ``shared_next
 ``sample(..., frame_stack=K)`` returns channel-last stacks of the last K frames of each slot's episode, built at sample time by the same
 walk run backward, and ``FrameStack`` keeps that stack on the acting side: the ring never stores a frame twice.
 ``sample_mixed`` draws one batch from several rings -- the agent's and a demonstration ring -- each ring's launches writing straight into
-its row range of the shared tensors, and ``update_priorities_mixed`` routes the TD errors back.
+its row range of the shared tensors, and ``update_priorities_mixed`` routes the TD errors back.  There is one sampling
+path: ``sample``, the prioritized ``sample`` and ``sample_mixed`` check their keywords, make one batch (``_Rows``), let each ring issue
+its launches into its rows of it (``_sample_rows``) and shape the result in one place (``_finish``).
 
 Field names follow the reference's buffer (DRL.py:80-100): obs, pobs, act, rew, next_obs, next_pobs, done.
 """
@@ -32,7 +34,7 @@ from numpy.lib.format import open_memmap
 import torch
 
 from . import _lib
-from .functional import _ptr, _stream
+from .functional import _ptr, _seed_args, _stream
 from .preprocess import _gather_shift, _shift_pad, _shift_seed
 
 
@@ -101,6 +103,7 @@ def _shared_next(shared, terminal_frames, size, num_envs):
 
 
 SMALL_FIELDS = ("pobs", "act", "rew", "next_pobs", "done")   # what one dgvit_ring_store_small launch stores
+_NO_SHIFTS = dict.fromkeys(FRAME_FIELDS)                     # a sample that returns no shift tables: no launch writes one
 
 # ---- the ring as a file
 FILE_FIELDS = FRAME_FIELDS + SMALL_FIELDS    # the field files of save_transitions and the blocks of a chunk, in this order
@@ -147,8 +150,9 @@ def _load_options(priorities, restore_rng):
 
 
 class _Rows:
-    """Where one ring's launches of a ``sample_mixed`` call write: rows [r0, r0 + n) of tensors of ``total`` rows that all rings of the
-    call share, one per output name, allocated when the first ring asks for it."""
+    """The raw buffers of one batch, every sampling call's: tensors of ``total`` rows, one per output name, allocated when a launch first
+    asks for it.  A ring writes rows [r0, r0 + n) of each: all of them in its own ``sample`` -- the tensor itself is then handed out, not
+    a slice of it -- and its share in ``sample_mixed``, which moves ``r0`` from ring to ring.  ``_finish`` makes the result of them."""
 
     def __init__(self, total, device):
         self.total, self.device, self.r0, self.bufs = total, device, 0, {}
@@ -157,12 +161,35 @@ class _Rows:
         buf = self.bufs.get(name)
         if buf is None:
             buf = self.bufs[name] = torch.empty(self.total, *tail, dtype=dtype, device=self.device)
-        return buf[self.r0:self.r0 + n]
+        return buf if n == self.total else buf[self.r0:self.r0 + n]       # (the whole tensor: r0 is 0 then)
 
 
-def _empty(into, name, n, tail, dtype, device):
-    """the (n, *tail) tensor an output's launch writes: a fresh one, or this ring's rows of the shared one (``_Rows``)"""
-    return torch.empty(n, *tail, dtype=dtype, device=device) if into is None else into.empty(name, n, tail, dtype)
+def _dense(buf, cols):
+    """a raw (B, al4(cols)) buffer without its row padding: the buffer itself where there is none (the slice would be its twin)"""
+    return buf if cols % 4 == 0 else buf[:, :cols]
+
+
+def _finish(batch, fields, shapes, pad, return_shifts, n_step, K):
+    """The result dict of ``sample`` and of ``sample_mixed`` out of a batch's raw buffers, the one place where an output is shaped: the
+    row padding goes, a field takes its ``shapes[k]`` -- ``rew``, ``done`` and ``discount`` (B, 1), a stack (B, H, W, K) by the call's one
+    ``.contiguous()``, a copy only where H W K is no multiple of 4 -- and ``return_shifts`` without a shift gets its tables of zeros."""
+    out, bufs, B = {}, batch.bufs, batch.total
+    for k, cols in fields.items():
+        buf = bufs[k]
+        if K is not None and k in FRAME_FIELDS:
+            out[k] = _dense(buf, cols * K).reshape(B, *shapes[k], K).contiguous()
+        elif n_step is not None and k in ("rew", "done"):     # the walk's own, one value a row
+            out[k] = buf.view(B, 1)
+        else:
+            out[k] = _dense(buf, cols).reshape(B, *shapes[k])
+        if return_shifts and k in FRAME_FIELDS:
+            out[k + "_shift"] = bufs[k + "_shift"] if pad else torch.zeros(B, 2, dtype=torch.int32, device=batch.device)
+    if n_step is not None:
+        out["discount"], out["steps"] = bufs["discount"].view(B, 1), bufs["steps"]
+    out["indexes"] = bufs["indexes"]
+    if "weights" in bufs:
+        out["weights"] = bufs["weights"]
+    return out
 
 
 class DeviceReplayBuffer:
@@ -222,24 +249,30 @@ class DeviceReplayBuffer:
                        "act": (act_dim,), "rew": (1,), "done": (1,)}
         # every field is a (size, row) fp32 matrix whose row length is padded to a multiple of 4 floats (float4 gather)
         self.rows = {k: _al4(n) for k, n in self.fields.items()}
+        # where the frames live, said once.  frame_ld: the row stride of a frame matrix in elements -- al16(H*W) bytes on a uint8 ring
+        # (``row_bytes`` there; the rows sample() returns stay al4(H*W) floats), al4(H*W) floats on an fp32 ring
+        shared = self.shared_next_obs
+        self.frame_ld = self.rows["obs"]
+        if self.frame_dtype is torch.uint8:
+            self.frame_ld = self.row_bytes = _al16(self.fields["obs"])
         self.arena = self.arena_rows = None
-        if self.shared_next_obs:                 # one arena of size + E + P frame rows; store["obs"] is its first `size` rows
-            u8 = self.frame_dtype is torch.uint8
-            if u8:
-                self.row_bytes = _al16(self.fields["obs"])
+        if shared:                               # one arena of size + E + P frame rows; store["obs"] is its first `size` rows
             self.arena_rows = self.size + self.num_envs + self.terminal_frames
-            self.arena = torch.zeros(self.arena_rows, self.row_bytes if u8 else self.rows["obs"], dtype=self.frame_dtype, device=self.device)
-            self.store = {k: self.arena[:self.size] if k == "obs" else torch.zeros(self.size, r, dtype=torch.float32, device=self.device)
-                          for k, r in self.rows.items() if k != "next_obs"}
+            self.arena = torch.zeros(self.arena_rows, self.frame_ld, dtype=self.frame_dtype, device=self.device)
+        self.store = {}
+        for k, r in self.rows.items():
+            if k not in FRAME_FIELDS:
+                self.store[k] = torch.zeros(self.size, r, dtype=torch.float32, device=self.device)
+            elif not shared:
+                self.store[k] = torch.zeros(self.size, self.frame_ld, dtype=self.frame_dtype, device=self.device)
+            elif k == "obs":                     # (a shared ring has no store["next_obs"])
+                self.store[k] = self.arena[:self.size]
+        # the matrix next_obs is gathered from, and its rows: the arena at the rows ``next_row`` names, or the field's own matrix
+        self.next_frames, self.next_frame_rows = (self.arena, self.arena_rows) if shared else (self.store["next_obs"], self.size)
+        if shared:
             self.next_row = torch.full((self.size,), -1, dtype=torch.int32, device=self.device)    # the arena row of each slot's next_obs
             self._pool_state = torch.zeros(3, dtype=torch.int64, device=self.device)               # head, tail, lost of the pool's FIFO
             self._step_moves = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)   # a step's move list, rewritten per store
-        elif self.frame_dtype is torch.uint8:    # a frame's ring row is al16(H*W) bytes; the rows sample() returns stay al4(H*W) floats
-            self.row_bytes = _al16(self.fields["obs"])
-            self.store = {k: torch.zeros(self.size, self.row_bytes, dtype=torch.uint8, device=self.device) if k in FRAME_FIELDS
-                          else torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
-        else:
-            self.store = {k: torch.zeros(self.size, r, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
         self.next_index, self.stored = 0, 0
         self.episode_flags = None                # (size,) uint8 once episodes are tracked
         self.gen = torch.Generator(device=self.device)
@@ -383,7 +416,7 @@ class DeviceReplayBuffer:
             (p0, c0, ld0), (p1, c1, ld1) = source("obs"), source("next_obs")
             if not self.shared_next_obs:
                 rc = lib.dgvit_ring_store_frames(p0, c0, ld0, p1, c1, ld1, _ptr(self.store["obs"]), _ptr(self.store["next_obs"]), int(u8),
-                                                 self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, st)
+                                                 self.frame_ld, n, self.fields["obs"], self.size, i, st)
                 _lib.check(rc, "dgvit_ring_store_frames")
             rc = lib.dgvit_ring_store_small(small, _ptr(self.episode_flags if step else None), end_ptr, end_f32, n, self.size, i, st)
             _lib.check(rc, "dgvit_ring_store_small")
@@ -395,9 +428,8 @@ class DeviceReplayBuffer:
                 rc = lib.dgvit_ring_plan_next(_ptr(self.next_row), _ptr(self._pool_state), _ptr(moves), _ptr(self.store["done"]),
                                               self.rows["done"], _ptr(self.episode_flags), n, self.size, i, E, P, st)
                 _lib.check(rc, "dgvit_ring_plan_next")
-                rc = lib.dgvit_ring_store_frames_shared(p0, c0, ld0, p1, c1, ld1, _ptr(self.arena), _ptr(moves), int(u8),
-                                                        self.row_bytes if u8 else self.rows["obs"], n, self.fields["obs"], self.size, i, E, P,
-                                                        st)
+                rc = lib.dgvit_ring_store_frames_shared(p0, c0, ld0, p1, c1, ld1, _ptr(self.arena), _ptr(moves), int(u8), self.frame_ld, n,
+                                                        self.fields["obs"], self.size, i, E, P, st)
                 _lib.check(rc, "dgvit_ring_store_frames_shared")
         self.next_index = (i + n) % self.size
         self.stored = min(self.stored + n, self.size)
@@ -407,6 +439,19 @@ class DeviceReplayBuffer:
     def _leaves(self):
         """the (size,) leaves of the priority tree, a view; None: a ring without one"""
         return None
+
+    def _priority_meta(self):
+        """(alpha, eps, the two header words of the priority tree, a view) for meta.json and the check of a file; None: a ring without one"""
+        return None
+
+    def _file_spec(self, frame, leaves):
+        """{array of a ring file: (numpy dtype, shape of a transition)} with frames of dtype ``frame``: ``FILE_FIELDS``, ``end`` and, with
+        ``leaves``, ``priority``"""
+        spec = {k: (np.dtype(frame if k in FRAME_FIELDS else np.float32), self.shapes[k]) for k in FILE_FIELDS}
+        spec["end"] = (np.dtype(np.uint8), ())
+        if leaves:
+            spec["priority"] = (np.dtype(np.float32), ())
+        return spec
 
     def _layout(self, n, frame_dtype=None, leaves=None):
         return export_layout(n, self.shapes["obs"], self.fields["pobs"], self.fields["act"], frame_dtype or self.frame_dtype,
@@ -421,18 +466,18 @@ class DeviceReplayBuffer:
         nbytes = self._layout(n)[1]
         if out is None:
             out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        u8, leaves = self.frame_dtype is torch.uint8, self._leaves()
+        leaves = self._leaves()
         view = _lib.dgvit_ring_view()
         view.obs = self.store["obs"].data_ptr()
-        view.next_obs = (self.arena if self.shared_next_obs else self.store["next_obs"]).data_ptr()
+        view.next_obs = self.next_frames.data_ptr()
         view.next_row = self.next_row.data_ptr() if self.shared_next_obs else None
         for j, k in enumerate(SMALL_FIELDS):
             view.small[j], view.small_cols[j], view.small_ld[j] = self.store[k].data_ptr(), self.fields[k], self.rows[k]
         view.flags = None if self.episode_flags is None else self.episode_flags.data_ptr()
         view.leaves = None if leaves is None else leaves.data_ptr()
-        view.frame_ld = self.row_bytes if u8 else self.rows["obs"]
-        view.next_rows = self.arena_rows if self.shared_next_obs else self.size
-        view.frame_u8 = int(u8)
+        view.frame_ld = self.frame_ld
+        view.next_rows = self.next_frame_rows
+        view.frame_u8 = int(self.frame_dtype is torch.uint8)
         oldest = self.next_index if self.stored == self.size else 0
         with torch.cuda.device(self.device):
             rc = _lib.load().dgvit_ring_export(view, _ptr(out), out.numel(), self.fields["obs"], self.size, oldest, a0, n, _stream())
@@ -441,15 +486,14 @@ class DeviceReplayBuffer:
 
     def _meta(self) -> dict:
         """meta.json of save_transitions; the two device reads (the pool's counters, the tree's header) synchronise"""
-        u8, tree = self.frame_dtype is torch.uint8, getattr(self, "tree", None)
-        header = [None, None] if tree is None else tree[:2].view(torch.int32).tolist()
+        u8, per = self.frame_dtype is torch.uint8, self._priority_meta()
+        alpha, eps, header = (None, None, [None, None]) if per is None else (*per[:2], per[2].view(torch.int32).tolist())
         return {"format_version": FILE_FORMAT_VERSION, "stored": self.stored, "size": self.size, "num_envs": self.num_envs,
                 "oldest_slot": self.next_index if self.stored == self.size else 0, "next_index": self.next_index,
                 "obs_shape": list(self.shapes["obs"]), "pstate_dim": self.fields["pobs"], "act_dim": self.fields["act"],
                 "frame_dtype": "uint8" if u8 else "float32", "shared_next_obs": self.shared_next_obs, "terminal_frames": self.terminal_frames,
                 "lost_terminal_frames": self.lost_terminal_frames(), "episodes_tracked": self.episode_flags is not None,
-                "prioritized": tree is not None, "alpha": getattr(self, "alpha", None), "eps": getattr(self, "eps", None),
-                "max_leaf_bits": header[0], "update_max_bits": header[1]}
+                "prioritized": per is not None, "alpha": alpha, "eps": eps, "max_leaf_bits": header[0], "update_max_bits": header[1]}
 
     def save_transitions(self, path, *, chunk: int = 4096, overwrite: bool = False) -> None:
         """Write the stored transitions to the directory ``path`` (cpprb's name): ``meta.json`` (``META_KEYS``) and one plain
@@ -482,11 +526,7 @@ class DeviceReplayBuffer:
             shutil.rmtree(tmp)
         os.makedirs(tmp)
         try:
-            frame = np.uint8 if self.frame_dtype is torch.uint8 else np.float32
-            spec = {k: (frame if k in FRAME_FIELDS else np.float32, self.shapes[k]) for k in FILE_FIELDS}
-            spec["end"] = (np.uint8, ())
-            if leaves:
-                spec["priority"] = (np.float32, ())
+            spec = self._file_spec(np.uint8 if self.frame_dtype is torch.uint8 else np.float32, leaves)
             files = {k: open_memmap(os.path.join(tmp, k + ".npy"), mode="w+", dtype=dt, shape=(stored, *shape)) for k, (dt, shape) in spec.items()}
             nbytes = self._layout(chunk)[1]
             dev = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
@@ -560,16 +600,13 @@ class DeviceReplayBuffer:
             raise ValueError(f"{path}: frame_dtype={meta['frame_dtype']!r} must be 'float32' or 'uint8'")
         with_leaves = (priorities == "file" and self._leaves() is not None and bool(meta["prioritized"])
                        and os.path.exists(os.path.join(path, "priority.npy")))
-        if with_leaves and (meta["alpha"], meta["eps"]) != (self.alpha, self.eps):
-            raise ValueError(f"{path}: the leaves are (|p| + eps)^alpha with alpha={meta['alpha']!r} eps={meta['eps']!r}, this ring has "
-                             f"alpha={self.alpha!r} eps={self.eps!r}: pass priorities='reset'")
-        frame = np.dtype(meta["frame_dtype"])
-        spec = {k: (frame if k in FRAME_FIELDS else np.dtype(np.float32), self.shapes[k]) for k in FILE_FIELDS}
-        spec["end"] = (np.dtype(np.uint8), ())
         if with_leaves:
-            spec["priority"] = (np.dtype(np.float32), ())
+            alpha, eps, _ = self._priority_meta()
+            if (meta["alpha"], meta["eps"]) != (alpha, eps):
+                raise ValueError(f"{path}: the leaves are (|p| + eps)^alpha with alpha={meta['alpha']!r} eps={meta['eps']!r}, this ring has "
+                                 f"alpha={alpha!r} eps={eps!r}: pass priorities='reset'")
         arrays = {}
-        for k, (dt, shape) in spec.items():
+        for k, (dt, shape) in self._file_spec(meta["frame_dtype"], with_leaves).items():
             a = np.load(os.path.join(path, k + ".npy"), mmap_mode="r", allow_pickle=False)
             if a.dtype != dt or a.shape != (stored, *shape):
                 raise ValueError(f"{path}: {k}.npy is {a.dtype} {a.shape}, expected {dt} {(stored, *shape)}")
@@ -770,7 +807,7 @@ class DeviceReplayBuffer:
 
     def sample(self, batch_size: int, indices: Optional[torch.Tensor] = None, random_shift: int = 0,
                return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
-               frame_stack: Optional[int] = None, *, _into: Optional[_Rows] = None) -> Dict[str, torch.Tensor]:
+               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Uniform sample with replacement -> dict of DEVICE tensors shaped like the reference's batch
         (obs (B,H,W), pobs (B,2), act (B,2), rew (B,1), ...), ready for the networks: no host round trip.
 
@@ -816,126 +853,95 @@ class DeviceReplayBuffer:
         gone.  ``frame_stack=None`` is the path above, launch for launch."""
         n_step, gamma, K = _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
         pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")
+        # the slots are the batch's ``indexes`` from the start: a given contiguous int64 tensor on the ring's device is adopted, not copied
+        idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
+        batch = _Rows(idx.numel(), self.device)
+        batch.bufs["indexes"] = idx
+        self._sample_rows(batch, idx, pad, return_shifts, n_step, gamma, K)
+        return _finish(batch, self.fields, self.shapes, pad, return_shifts, n_step, K)
+
+    def _slots_of_mixed(self, batch, n, indices):
+        """this ring's n rows of a ``sample_mixed`` batch's ``indexes``, filled: the draw ``sample_indices`` makes, written there by the
+        draw itself, or the given ``indices`` copied there"""
+        idx = batch.empty("indexes", n, (), torch.int64)
+        if indices is None:
+            return torch.randint(0, self.stored, (n,), generator=self.gen, out=idx)
+        return idx.copy_(indices.to(self.device, torch.int64).reshape(-1))
+
+    def _sample_rows(self, batch, idx, pad, return_shifts, n_step, gamma, K):
+        """The one sampling path of ``sample``, the prioritized ``sample`` and ``sample_mixed``: this ring's launches of a call at the
+        slots ``idx`` -- its rows of the batch's ``indexes``, already drawn or given -- written into the same rows of ``batch``
+        (``_Rows``); the keywords have passed their checks, and nothing is shaped here (``_finish``).  The launches stand in the order
+        they depend on each other."""
         if n_step is not None or K is not None:
             self.track_episodes()
-        lib = _lib.load()
-        u8 = self.frame_dtype is torch.uint8
-        into = _into                             # sample_mixed's hook: every output goes to this ring's rows of the shared tensors
-        if into is None:
-            idx = self.sample_indices(batch_size) if indices is None else indices.to(self.device, torch.int64).contiguous()
-        else:
-            idx = self._indices_into(into, batch_size, indices)
-        B = idx.numel()
-        st = _stream()
-        out = {}
+        lib, st, dev, u8, n = _lib.load(), _stream(), self.device, self.frame_dtype is torch.uint8, idx.numel()
         if pad:
-            self.shift_seed = _shift_seed(self.device)
-        with torch.cuda.device(self.device):
-            at = idx                             # the slots a field is gathered at: the walk's last ones for next_obs of an n-step call
-            walk = tables = None
-            if K is not None:                    # the stacks' row tables need the n-step tails: the walk goes first (DESIGN 3.43)
-                if n_step is not None:
-                    walk = self._walk(idx, n_step, gamma, into)
-                tables = self._stack_rows(idx, None if walk is None else walk["tail"], K)
-            for k, n in self.fields.items():
-                r = self.rows[k]
-                if n_step is not None and k in ("rew", "next_pobs", "done"):
-                    if k == "rew":               # (fields are in the reference's order: obs, pobs and act are out, next_obs is to come)
-                        if walk is None:
-                            walk = self._walk(idx, n_step, gamma, into)
-                        at = walk.pop("tail")
-                    out[k] = walk.pop(k)
-                    continue
-                if K is not None and k in FRAME_FIELDS:
-                    shifts = _empty(into, k + "_shift", B, (2,), torch.int32, self.device) if pad and return_shifts else None
-                    out[k] = self._gather_stack(k, tables[k], K, pad, shifts, into)
-                    if shifts is not None:
-                        out[k + "_shift"] = shifts
-                    continue
-                buf = _empty(into, k, B, (r,), torch.float32, self.device)
-                src, nrows, rows_at = self.store.get(k), self.size, at
-                if k == "next_obs" and self.shared_next_obs:   # the same gathers over the arena, at the rows next_row names (DESIGN 3.39)
-                    src, nrows, rows_at = self.arena, self.arena_rows, torch.empty(B, dtype=torch.int64, device=self.device)
-                    _lib.check(lib.dgvit_ring_next_rows(_ptr(self.next_row), _ptr(at), _ptr(rows_at), B, self.size, st), "dgvit_ring_next_rows")
-                if pad and k in FRAME_FIELDS:
-                    shifts = _empty(into, k + "_shift", B, (2,), torch.int32, self.device) if return_shifts else None
-                    _gather_shift(src, rows_at, buf, shifts, self.shapes[k], nrows, pad, int(k == "next_obs"), self.shift_seed)
-                    if return_shifts:
-                        out[k + "_shift"] = shifts
-                elif u8 and k in FRAME_FIELDS:
-                    rc = lib.dgvit_gather_rows_u8(_ptr(src), _ptr(rows_at), _ptr(buf), B, n, self.row_bytes, r, nrows, st)
-                    _lib.check(rc, "dgvit_gather_rows_u8")
-                else:
-                    rc = lib.dgvit_gather_rows(_ptr(src), _ptr(rows_at), _ptr(buf), B, r, nrows, st)
-                    _lib.check(rc, "dgvit_gather_rows")
-                out[k] = buf[:, :n].reshape(B, *self.shapes[k])
-        if return_shifts and not pad and into is None:
-            out["obs_shift"], out["next_obs_shift"] = (torch.zeros(B, 2, dtype=torch.int32, device=self.device) for _ in range(2))
-        if n_step is not None:
-            out.update(walk)                     # discount, steps
-        out["indexes"] = idx
-        return out
-
-    def _indices_into(self, into, batch_size, indices):
-        """the slots of this ring's rows of a ``sample_mixed`` batch, in the shared ``indexes``: the draw ``sample_indices`` makes, written
-        there by the draw itself, or the given ``indices`` copied there (the prioritized draw has written them already)"""
-        if indices is None:
-            if self.stored == 0:
-                raise RuntimeError("cannot sample from an empty buffer")
-            idx = into.empty("indexes", int(batch_size), (), torch.int64)
-            return torch.randint(0, self.stored, (int(batch_size),), generator=self.gen, out=idx)
-        given = indices.to(self.device, torch.int64).contiguous()
-        idx = into.empty("indexes", given.numel(), (), torch.int64)
-        if idx.data_ptr() != given.data_ptr():
-            idx.copy_(given.reshape(-1))
-        return idx
+            self.shift_seed = _shift_seed(dev)
+        shifts = _NO_SHIFTS
+        if pad and return_shifts:
+            shifts = {k: batch.empty(k + "_shift", n, (2,), torch.int32) for k in FRAME_FIELDS}
+        with torch.cuda.device(dev):
+            tail = None                          # 1. the walk: rew, done, next_pobs, discount and steps, and the slots where it ended
+            if n_step is not None:
+                tail = self._walk(batch, idx, n, n_step, gamma)
+            if K is not None:                    # 2. the stacks' row tables, from the walk's tails on (DESIGN 3.43), and 4. the stacks
+                rows = self._stack_rows(idx, tail, K)
+                for k in FRAME_FIELDS:
+                    self._gather_stack(k, rows[k], K, pad, shifts[k], batch.empty(k, n, (_al4(self.fields[k] * K),), torch.float32))
+            else:
+                last = idx if tail is None else tail
+                if self.shared_next_obs:         # 3. next_obs lies in the arena, at the rows next_row names (DESIGN 3.39)
+                    slots, last = last, torch.empty(n, dtype=torch.int64, device=dev)
+                    _lib.check(lib.dgvit_ring_next_rows(_ptr(self.next_row), _ptr(slots), _ptr(last), n, self.size, st), "dgvit_ring_next_rows")
+                # 4. the two frame outputs: obs at the slots, next_obs at the walk's last slots or at the arena rows just looked up
+                for k, src, nrows, at in (("obs", self.store["obs"], self.size, idx), ("next_obs", self.next_frames, self.next_frame_rows, last)):
+                    buf = batch.empty(k, n, (self.rows[k],), torch.float32)
+                    if pad:
+                        _gather_shift(src, at, buf, shifts[k], self.shapes[k], nrows, pad, int(k == "next_obs"), self.shift_seed)
+                    elif u8:
+                        rc = lib.dgvit_gather_rows_u8(_ptr(src), _ptr(at), _ptr(buf), n, self.fields[k], self.frame_ld, self.rows[k], nrows, st)
+                        _lib.check(rc, "dgvit_gather_rows_u8")
+                    else:
+                        _lib.check(lib.dgvit_gather_rows(_ptr(src), _ptr(at), _ptr(buf), n, self.rows[k], nrows, st), "dgvit_gather_rows")
+            for k in SMALL_FIELDS if n_step is None else ("pobs", "act"):     # 5. the small fields the walk has not produced
+                buf = batch.empty(k, n, (self.rows[k],), torch.float32)
+                _lib.check(lib.dgvit_gather_rows(_ptr(self.store[k]), _ptr(idx), _ptr(buf), n, self.rows[k], self.size, st), "dgvit_gather_rows")
 
     def _stack_rows(self, idx, tail, K):
         """the one dgvit_ring_stack_rows launch of a stacked sample: {field: (B, K) int64 rows of its K frames}; ``tail`` the n-step
         walk's last slots or None"""
         B = idx.numel()
         rows = {k: torch.empty(B, K, dtype=torch.int64, device=self.device) for k in FRAME_FIELDS}
-        shared = self.shared_next_obs
         rc = _lib.load().dgvit_ring_stack_rows(_ptr(idx), _ptr(tail), _ptr(self.episode_flags), _ptr(self.store["done"]), self.rows["done"],
-                                               _ptr(self.next_row if shared else None), _ptr(rows["obs"]), _ptr(rows["next_obs"]), B, self.size,
-                                               self.num_envs, K, int(self.stored == self.size), self.arena_rows if shared else self.size,
-                                               _stream())
+                                               _ptr(self.next_row if self.shared_next_obs else None), _ptr(rows["obs"]), _ptr(rows["next_obs"]),
+                                               B, self.size, self.num_envs, K, int(self.stored == self.size), self.next_frame_rows, _stream())
         _lib.check(rc, "dgvit_ring_stack_rows")
         return rows
 
-    def _gather_stack(self, k, rows, K, pad, shifts, into=None):
-        """frame field k of a stacked sample, (B, H, W, K): dgvit_gather_stack_frames, or its shifted form, over the obs matrix and --
-        for the newest channel of next_obs -- the next_obs matrix or the arena"""
-        B, cols, (H, W) = rows.shape[0], self.fields[k], self.shapes[k]
-        u8 = self.frame_dtype is torch.uint8
-        src0 = src1 = self.store["obs"]
-        nrows1 = self.size
-        if k == "next_obs":
-            src1, nrows1 = (self.arena, self.arena_rows) if self.shared_next_obs else (self.store["next_obs"], self.size)
-        row, ld = _al4(cols * K), self.row_bytes if u8 else self.rows["obs"]
-        buf = _empty(into, k, B, (row,), torch.float32, self.device)
+    def _gather_stack(self, k, rows, K, pad, shifts, buf):
+        """frame field k of a stacked sample into ``buf``, (B, al4(H W K)): dgvit_gather_stack_frames, or its shifted form, over the obs
+        matrix and -- for the newest channel of next_obs -- the matrix ``next_obs`` is gathered from"""
+        B, cols, (H, W), row = rows.shape[0], self.fields[k], self.shapes[k], buf.shape[1]
+        u8, src0 = int(self.frame_dtype is torch.uint8), self.store["obs"]
+        src1, nrows1 = (src0, self.size) if k == "obs" else (self.next_frames, self.next_frame_rows)
         lib = _lib.load()
         if pad:
-            seed_dev = self.shift_seed if isinstance(self.shift_seed, torch.Tensor) else None
-            rc = lib.dgvit_gather_shift_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), _ptr(shifts), B, H, W, K, int(u8), ld, row,
-                                                     self.size, nrows1, pad, int(k == "next_obs"),
-                                                     0 if seed_dev is not None else int(self.shift_seed), _ptr(seed_dev), _stream())
+            seed_val, seed_dev = _seed_args(self.shift_seed)
+            rc = lib.dgvit_gather_shift_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), _ptr(shifts), B, H, W, K, u8, self.frame_ld,
+                                                     row, self.size, nrows1, pad, int(k == "next_obs"), seed_val, _ptr(seed_dev), _stream())
             _lib.check(rc, "dgvit_gather_shift_stack_frames")
         else:
-            rc = lib.dgvit_gather_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), B, cols, K, int(u8), ld, row, self.size, nrows1,
-                                               _stream())
+            rc = lib.dgvit_gather_stack_frames(_ptr(src0), _ptr(src1), _ptr(rows), _ptr(buf), B, cols, K, u8, self.frame_ld, row, self.size,
+                                               nrows1, _stream())
             _lib.check(rc, "dgvit_gather_stack_frames")
-        if into is not None:                     # sample_mixed shapes the shared tensor, once for all rings
-            return buf
-        return buf[:, :cols * K].reshape(B, H, W, K).contiguous()   # a copy only where H W K is no multiple of 4: the row padding goes
 
-    def _walk(self, idx, n_step, gamma, into=None):
+    def _walk(self, batch, idx, B, n_step, gamma):
         """the one dgvit_nstep_walk launch of an n-step sample (dgvit_nstep_walk_strided on a ring of several environments): rew, done,
-        next_pobs, discount, steps and the tail slots"""
-        B, dev = idx.numel(), self.device
-        f32 = lambda name, *tail: _empty(into, name, B, tail, torch.float32, dev)   # noqa: E731
+        next_pobs, discount and steps into the batch -> the (B,) int64 slots where the walks ended"""
+        f32 = lambda name, *tail: batch.empty(name, B, tail, torch.float32)   # noqa: E731
         ret, done, disc, small = f32("rew"), f32("done"), f32("discount"), f32("next_pobs", self.rows["next_pobs"])
-        steps, tail = _empty(into, "steps", B, (), torch.int32, dev), torch.empty(B, dtype=torch.int64, device=dev)
+        steps, tail = batch.empty("steps", B, (), torch.int32), torch.empty(B, dtype=torch.int64, device=self.device)
         ring = (_ptr(self.store["rew"]), self.rows["rew"], _ptr(self.store["done"]), self.rows["done"], _ptr(self.episode_flags),
                 _ptr(self.store["next_pobs"]), self.rows["next_pobs"], _ptr(idx), B, self.size)
         outs = (n_step, gamma, _ptr(ret), _ptr(done), _ptr(disc), _ptr(small), _ptr(steps), _ptr(tail), _stream())
@@ -943,8 +949,7 @@ class DeviceReplayBuffer:
             _lib.check(_lib.load().dgvit_nstep_walk(*ring, *outs), "dgvit_nstep_walk")
         else:                                    # an environment's next transition is num_envs slots on
             _lib.check(_lib.load().dgvit_nstep_walk_strided(*ring, self.num_envs, *outs), "dgvit_nstep_walk_strided")
-        return {"rew": ret.view(B, 1), "done": done.view(B, 1), "next_pobs": small[:, :self.fields["next_pobs"]], "discount": disc.view(B, 1),
-                "steps": steps, "tail": tail}
+        return tail
 
 
 PER_MAX_SIZE = 1 << 24      # include/dgvit_hip.h: the radix-64 tree has at most four levels
@@ -1020,6 +1025,9 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         off = self._levels[0][0]
         return self.tree[off:off + self.size]
 
+    def _priority_meta(self):
+        return self.alpha, self.eps, self.tree[:2]
+
     def _set_leaves(self, start: int, leaves: torch.Tensor) -> None:
         """the file's leaves over the max leaf that ``_on_store`` has just given ring slots start .. start + n - 1 (mod size):
         dgvit_per_set_leaves, twice when the slots wrap"""
@@ -1047,14 +1055,17 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
             _lib.check(_lib.load().dgvit_per_init(_ptr(self.tree), self.size, _stream()), "dgvit_per_init")
 
     def draw(self, batch_size: int, beta: float = 0.4, stratified: bool = False,
-             uniforms: Optional[torch.Tensor] = None, *, _into: Optional[_Rows] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The index draw alone: ((B,) int64 indices, (B, 1) fp32 importance weights).  ``uniforms`` ((B,) fp32 on the device, values in
         [0, 1]) makes the draw reproducible; absent, it comes from ``self.gen``.  ``stratified`` draws sample j from the j-th of B equal
         slices of the total priority."""
         beta = _unit("beta", beta)
+        return self._draw(_Rows(int(batch_size), self.device), int(batch_size), beta, stratified, uniforms)
+
+    def _draw(self, batch, B, beta, stratified, uniforms):
+        """``draw`` into this ring's B rows of the batch's ``indexes`` and ``weights``, which are returned; ``beta`` has passed its check"""
         if self.stored == 0:
             raise RuntimeError("cannot sample from an empty buffer")
-        B = int(batch_size)
         if uniforms is None:
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.DgvitError("sample() inside a stream capture needs uniforms=: pass a persistent (B,) fp32 device tensor and refill "
@@ -1063,8 +1074,7 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         elif (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or uniforms.device != self.store["obs"].device
               or uniforms.numel() != B or not uniforms.is_contiguous()):
             raise ValueError(f"uniforms must be a contiguous fp32 tensor of {B} values on {self.store['obs'].device}")
-        idx = _empty(_into, "indexes", B, (), torch.int64, self.device)
-        weights = _empty(_into, "weights", B, (1,), torch.float32, self.device)
+        idx, weights = batch.empty("indexes", B, (), torch.int64), batch.empty("weights", B, (1,), torch.float32)
         with torch.cuda.device(self.device):
             rc = _lib.load().dgvit_per_sample(_ptr(self.tree), self.size, _ptr(uniforms), B, int(bool(stratified)), beta, _ptr(idx),
                                               _ptr(weights), _stream())
@@ -1073,16 +1083,16 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
 
     def sample(self, batch_size: int, beta: float = 0.4, stratified: bool = False, uniforms: Optional[torch.Tensor] = None,
                random_shift: int = 0, return_shifts: bool = False, n_step: Optional[int] = None, gamma: float = 0.99,
-               frame_stack: Optional[int] = None, *, _into: Optional[_Rows] = None) -> Dict[str, torch.Tensor]:
-        """Prioritized sample with replacement: ``draw`` and then the base class's gathers on the drawn indices (``random_shift``,
-        ``return_shifts``, ``n_step``, ``gamma`` and ``frame_stack`` as there; the draw and the weights do not depend on them).  The base's dict plus
-        ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor, the start slots of an n-step sample."""
-        _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack)
-        idx, weights = self.draw(batch_size, beta, stratified, uniforms, _into=_into)
-        out = super().sample(idx.numel(), indices=idx, random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma,
-                             frame_stack=frame_stack, _into=_into)
-        out["weights"] = weights
-        return out
+               frame_stack: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Prioritized sample with replacement: ``draw`` into the batch and then the base class's launches at the drawn indices
+        (``random_shift``, ``return_shifts``, ``n_step``, ``gamma`` and ``frame_stack`` as there; the draw and the weights do not depend on
+        them).  The base's dict plus ``weights`` (B, 1) fp32; ``indexes`` is the drawn tensor, the start slots of an n-step sample."""
+        n_step, gamma, K, beta = _n_step(n_step), _unit("gamma", gamma), _frame_stack(frame_stack), _unit("beta", beta)
+        batch = _Rows(int(batch_size), self.device)
+        idx, _ = self._draw(batch, batch.total, beta, stratified, uniforms)
+        pad = _shift_pad(random_shift, self.shapes["obs"], "random_shift")     # (after the draw, as ever: an empty ring is reported first)
+        self._sample_rows(batch, idx, pad, return_shifts, n_step, gamma, K)
+        return _finish(batch, self.fields, self.shapes, pad, return_shifts, n_step, K)
 
     def update_priorities(self, indexes: torch.Tensor, priorities: torch.Tensor) -> None:
         """leaf[indexes[j]] <- (|priorities[j]| + eps)^alpha: ``indexes`` any integer tensor of B entries, ``priorities`` (B,) or (B, 1)
@@ -1231,36 +1241,18 @@ def sample_mixed(pairs, *, indices=None, random_shift: int = 0, return_shifts: b
         if n and ring.stored == 0:
             raise RuntimeError("cannot sample from an empty buffer")
     total, dev = sum(n for _, n in pairs), first.device
-    into = _Rows(total, dev)
+    batch = _Rows(total, dev)
     source = torch.empty(total, dtype=torch.int32, device=dev)
     if any(per) and any(n and not p for (_, n), p in zip(pairs, per)):        # rows of uniform rings: 1, the rest is overwritten
-        into.bufs["weights"] = torch.ones(total, 1, dtype=torch.float32, device=dev)
-    common = dict(random_shift=random_shift, return_shifts=return_shifts, n_step=n_step, gamma=gamma, frame_stack=K)
+        batch.bufs["weights"] = torch.ones(total, 1, dtype=torch.float32, device=dev)
     for i, (ring, n) in enumerate(pairs):
         if n == 0:
             continue
-        source[into.r0:into.r0 + n].fill_(i)
-        if per[i]:
-            ring.sample(n, beta=beta, stratified=stratified, uniforms=uniforms[i], _into=into, **common)
-        else:
-            ring.sample(n, indices=indices[i], _into=into, **common)
-        into.r0 += n
-    out, bufs = MixedBatch(), into.bufs
-    for k, cols in first.fields.items():
-        buf = bufs[k]
-        if K is not None and k in FRAME_FIELDS:
-            out[k] = buf[:, :cols * K].reshape(total, *first.shapes[k], K).contiguous()     # a copy only where H W K is no multiple of 4
-        elif n_step is not None and k in ("rew", "done"):
-            out[k] = buf.view(total, 1)
-        else:
-            out[k] = buf[:, :cols].reshape(total, *first.shapes[k])
-        if k in FRAME_FIELDS and return_shifts:
-            out[k + "_shift"] = bufs[k + "_shift"] if pad else torch.zeros(total, 2, dtype=torch.int32, device=dev)
-    if n_step is not None:
-        out["discount"], out["steps"] = bufs["discount"].view(total, 1), bufs["steps"]
-    out["indexes"] = bufs["indexes"]
-    if "weights" in bufs:
-        out["weights"] = bufs["weights"]
+        source[batch.r0:batch.r0 + n].fill_(i)
+        idx = ring._draw(batch, n, beta, stratified, uniforms[i])[0] if per[i] else ring._slots_of_mixed(batch, n, indices[i])
+        ring._sample_rows(batch, idx, pad, return_shifts, n_step, gamma, K)
+        batch.r0 += n
+    out = MixedBatch(_finish(batch, first.fields, first.shapes, pad, return_shifts, n_step, K))
     out["source"], out["counts"] = source, tuple(n for _, n in pairs)
     out.rings = tuple(ring for ring, _ in pairs)
     return out

@@ -284,6 +284,66 @@ def test_a_mixed_call_launches_what_its_rings_launch(amd, kw):
     assert _launches(amd, lambda: replay.sample_mixed([(a, 5), (p, 0), (u, 0)], **kw)) == _launches(amd, lambda: a2.sample(5, **kw))
 
 
+class _CountingLib:
+    """the object ``_lib.load()`` returns, every ``dgvit_*`` entry point counting its calls: the gathers, the walk, the row tables and
+    dgvit_ring_next_rows do not pass the profile bracket, so ``_launches`` sees none of them"""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("dgvit_"):
+            return fn
+
+        def counted(*args):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return fn(*args)
+        return counted
+
+
+# the library entry points ONE sample(5, ...) calls, per ring kind and keyword set, each of them one launch: read once through
+# _CountingLib on the commit before sample, the prioritized sample and sample_mixed became one path, and kept as literals.  7 gathers for
+# a plain call; the walk in the place of three of them with n_step; dgvit_ring_next_rows more for an unstacked call on a shared ring; the
+# row tables and two stacked gathers in the place of the two frame gathers with frame_stack; the draw more on a prioritized ring
+SAMPLE_LAUNCHES = {
+    "f32": dict(plain=7, shift=7, nstep=5, stack=8, all3=6),
+    "u8": dict(plain=7, shift=7, nstep=5, stack=8, all3=6),
+    "shared": dict(plain=8, shift=8, nstep=6, stack=8, all3=6),
+    "env2": dict(plain=7, shift=7, nstep=5, stack=8, all3=6),
+    "per": dict(plain=8, shift=8, nstep=6, stack=9, all3=7),
+}
+
+
+@pytest.mark.parametrize("kind", list(SAMPLE_LAUNCHES))
+def test_a_plain_sample_launches_what_it_launched(amd, kind, monkeypatch):
+    """test_a_mixed_call_launches_what_its_rings_launch compares one path with itself; these literals anchor the count.  Of them the
+    profile counters (``_launches``) see the prioritized draw alone, on that commit as on this one."""
+    from dgvit_amd import _lib
+    ring = _build(amd, kind, (5, 7), ("launches", 0))
+    for name, want in SAMPLE_LAUNCHES[kind].items():
+        run = lambda: _own(ring, 5, KEYWORDS[name])  # noqa: E731
+        run()
+        assert sum(_launches(amd, run)) == int(kind == "per"), (kind, name)
+        counting = _CountingLib(_lib.load())
+        with monkeypatch.context() as mp:
+            mp.setattr(_lib, "_lib", counting)
+            run()
+        torch.cuda.synchronize()
+        print(f"entry points of one sample(5): {kind} {name} {sum(counting.calls.values())} {counting.calls}")
+        assert sum(counting.calls.values()) == want, (kind, name, counting.calls, want)
+
+
+@pytest.mark.parametrize("kind", ["f32", "u8"])
+@pytest.mark.parametrize("kw", ["plain", "all3"])
+def test_given_indices_are_adopted_not_copied(amd, kind, kw):
+    """a contiguous int64 tensor on the ring's device IS the result's ``indexes``: no copy, which the library's counters would not see"""
+    ring = _build(amd, kind, (5, 7), ("launches", 0))
+    t = torch.tensor([3, 15, 0, 7, 7], device="cuda")
+    out = ring.sample(5, indices=t, **KEYWORDS[kw])
+    assert out["indexes"].data_ptr() == t.data_ptr() and torch.equal(out["indexes"], t)
+
+
 # ================================================================================================ log_prob
 LP_B, LP_A = (1, 37, 257, 300), (1, 2, 3, 16)     # 257 crosses the 256-thread block; A = 3 is no power of two, 16 the limit
 LP_OUT = ("log_prob", "dmean", "dlog_std")
